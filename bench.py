@@ -31,10 +31,6 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# HIP maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4); the 18 streams of three in-flight
-# proofs do measurably better on 8 (same-box A/B, profiles/r03_ab_hwqueues.txt: 114.8 -> 116.4 proofs/s; 6 and 16 are
-# worse).  Read by the HIP runtime when it initialises, so it is set before torch is imported.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 GATHER_CEILING_GB_S = 2200.0     # measured ceiling of random table gathers (profiles/r03_ubench_affine_g2.txt)
 NWITNESS = 3          # distinct satisfying witnesses the timed steps rotate over (w_0 = 3, 5, 7; same k_i, same key)
@@ -51,11 +47,15 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=288,
                     help="timed proofs (default 288: a ~2.5-s timed region at 2^20; round 2's 96 steps = 0.9 s were within box noise)")
     ap.add_argument("--warmup", type=int, default=24)
-    ap.add_argument("--repeats", type=int, default=0,
+    ap.add_argument("--repeats", type=int, default=1,
                     help="the timed region (exactly --steps proofs, barriers on both sides) is run this many times; "
-                         "`value` / `ms_per_step` are the median run, every run is listed in `value_runs`.  Default: 5, "
-                         "or 11 for regions of fewer than 96 steps (a 20-step region is 0.17 s: single ones scatter by "
-                         "+-4 %, medians of five by +-1.7 % on the noisiest box, profiles/r04_bench_repeat.txt)")
+                         "`value` / `ms_per_step` are the median run, every run is listed in `value_runs`.  Default 1: "
+                         "--steps is the number of timed proofs.  Short regions scatter (a 20-step region is 0.17 s: "
+                         "single ones by +-4 %, medians of five by +-1.7 % on the noisiest box, "
+                         "profiles/r04_bench_repeat.txt)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the proof of the last timed step to DIR/pi_a.npy, pi_b.npy, pi_c.npy (float64; see "
+                         "dump_outputs)")
     ap.add_argument("--log2n", type=int, default=20, help="domain size 2^log2n (constraints m = 2^log2n - 2)")
     ap.add_argument("--mode", choices=["replica", "shard"], default="replica")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -344,13 +344,15 @@ def measure(args, rank, world, local, dist, coll_dev, state):
     ctx.profile(2 if rank == 0 else 0)
     ctx.profile_reset()
     runs = []
-    repeats = args.repeats if args.repeats > 0 else (5 if args.steps >= 96 else 11)
-    for _ in range(repeats):
+    for _ in range(max(1, args.repeats)):
         barrier()
         t0 = time.perf_counter()
         run(args.steps, hbm=args.witness == "hbm")
         barrier()
         runs.append(allmax(time.perf_counter() - t0))
+    if args.dump_outputs and rank == 0:
+        # keep() fails the run unless every proof of a witness is the same, so this is what the last step returned
+        dump_outputs(args.dump_outputs, proofs[(args.steps - 1) % NWITNESS])
     rep = ctx.profile_report() if rank == 0 else {}
     ctx.profile(False)
     dt = sorted(runs)[len(runs) // 2]          # the median run
@@ -469,6 +471,16 @@ def measure(args, rank, world, local, dist, coll_dev, state):
     extra["standalone_msm_wall_ms"] = round(msm_wall, 4)
     extra["roofline_valu"] = valu_roofline(dom, iso, clock_ghz, static)
     state.update(roof=roof, extra=extra)
+
+
+def dump_outputs(path, proof):
+    """--dump-outputs: the proof (pi_a 64 B, pi_b 128 B, pi_c 64 B: affine coordinates in Montgomery form, as g16_prove
+    returns them) as its little-endian 32-bit words in float64, which holds every word exactly.  pi_a, pi_c: (x, y) x 8
+    words; pi_b: (x, y) x (c0, c1) x 8 words.  The inputs are seeded, so two builds are compared file for file."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, b, shape in zip(("pi_a", "pi_b", "pi_c"), proof, ((2, 8), (2, 2, 8), (2, 8))):
+        np.save(os.path.join(path, name + ".npy"), np.frombuffer(b, dtype="<u4").astype(np.float64).reshape(shape))
 
 
 def overlap_efficiency(accum_ms_per_proof, region_s, steps):

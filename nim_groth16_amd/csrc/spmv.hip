@@ -301,7 +301,10 @@ static int32_t spmat_create(g16_ctx* ctx, uint32_t nmat, uint32_t nrows, size_t 
       ctx->err = "hipMalloc(sparse matrix) failed";
       rc = G16_ENOMEM;
     } else if (values_r2) {   // the file's bytes ARE the second table
-      if (hipMemcpy(m->d_val2, m->d_val, vals.size() * 32, hipMemcpyDeviceToDevice) != hipSuccess) rc = G16_EHIP;
+      // on the stream of the rescaling kernel that reads it: a device-to-device hipMemcpy may return before the copy
+      // is done, and the null stream does not order work on the (non-blocking) context stream
+      if (hipMemcpyAsync(m->d_val2, m->d_val, vals.size() * 32, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
+        rc = G16_EHIP;
       if (!rc) rescale(m->d_val2, m->d_val, 1);
     } else {
       rescale(m->d_val, m->d_val2, 0);

@@ -84,6 +84,22 @@ def test_bench_source_emits_the_same_keys():
         assert k in src, k
 
 
+def test_dump_outputs_holds_every_proof_word_exactly(tmp_path):
+    """--dump-outputs: the proof bytes as float64 32-bit words, losslessly; by default --steps is the number of timed
+    proofs (one timed region)"""
+    import sys
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse_args(["--steps", "7"]).repeats == 1
+    proof = (bytes(range(64)), bytes(255 - i for i in range(128)), b"\xff" * 64)
+    bench.dump_outputs(str(tmp_path / "out"), proof)
+    for name, b in zip(("pi_a", "pi_b", "pi_c"), proof):
+        a = np.load(tmp_path / "out" / f"{name}.npy")
+        assert a.dtype == np.float64 and a.size * 4 == len(b)
+        assert a.astype("<u4").tobytes() == b
+
+
 def test_overlap_efficiency_is_per_gpu_for_any_world_size():
     """in replica mode EVERY rank proves `steps` proofs in the timed region, so a GPU's time per proof is
     region / steps whatever the world size -- the value must not shrink by the number of GPUs"""

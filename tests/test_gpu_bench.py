@@ -22,7 +22,7 @@ def _sub(*flags, timeout=900):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *flags], env=env, capture_output=True,
                        text=True, timeout=timeout)
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-    tag = "_".join(f.strip("-") for f in flags)[:80]
+    tag = "_".join(os.path.basename(f.strip("-")) for f in flags)[:80]
     with open(os.path.join(ROOT, "gpurun_out", f"test_gpu_bench_{tag}.stderr.txt"), "w") as f:
         f.write(f"exit code {r.returncode}\n---- stdout\n{r.stdout}\n---- stderr\n{r.stderr}")
     return r
@@ -38,8 +38,9 @@ def _run(*flags):
 
 
 @pytest.mark.timeout(1000)
-def test_bench_single_gpu_small_domain_contract_line():
-    d = _run("--log2n", "14", "--steps", "12", "--warmup", "3")
+def test_bench_single_gpu_small_domain_contract_line(tmp_path):
+    dump = tmp_path / "dump"
+    d = _run("--log2n", "14", "--steps", "12", "--warmup", "3", "--repeats", "11", "--dump-outputs", str(dump))
     for k in KEYS:
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 12 and d["scaling"] == "weak" and d["value"] > 0
@@ -52,12 +53,17 @@ def test_bench_single_gpu_small_domain_contract_line():
     assert c["kind"] == "port" and c["cores"] >= 1 and c["value"] > 0
     # round 4: the timed region is repeated, `value` is the median run; the share of a step that is bucket accumulation
     # and the gather roofline are in the line
-    # (11 regions when a region is shorter than 96 steps, else 5)
     assert len(d["value_runs"]) == 11 and sorted(d["value_runs"])[5] == d["value"] and "median" in d["value_is"]
     assert d["accum_ms_per_proof"] > 0 and 0 < d["overlap_efficiency"] < 1.5
     g = d["roofline_gather"]
     for k in ("kernel", "hbm_bytes_per_launch_by_counters", "avg_launch_ms", "ceiling_gb_s", "ceiling_from", "frac"):
         assert k in g, k
+    # --dump-outputs: the last timed step's proof, every 32-bit word of it exact in float64
+    import numpy as np
+    for name, shape in (("pi_a", (2, 8)), ("pi_b", (2, 2, 8)), ("pi_c", (2, 8))):
+        a = np.load(dump / f"{name}.npy")
+        assert a.dtype == np.float64 and a.shape == shape, (name, a.dtype, a.shape)
+        assert np.all(a == np.floor(a)) and a.min() >= 0 and a.max() < 2 ** 32 and a.any(), name
 
 
 @pytest.mark.timeout(1000)
@@ -75,6 +81,7 @@ def test_bench_two_ranks_replica_mode_from_a_bare_shell():
     d = _run("--gpus", "2", "--backend", "gloo", "--log2n", "13", "--steps", "6", "--warmup", "3", "--inflight", "2")
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["config"]["mode"] == "replica"
     assert abs(d["value"] - 2 * 1e3 / d["ms_per_step"]) < 0.01 * d["value"]     # whole-job aggregate over both ranks
+    assert len(d["value_runs"]) == 1                        # by default --steps is the number of timed proofs
 
 
 @pytest.mark.timeout(400)

@@ -13,7 +13,6 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch  # noqa: E402
 from nim_groth16_amd import Context, Mask, loadProvingKey  # noqa: E402
 from nim_groth16_amd import bn128 as F  # noqa: E402

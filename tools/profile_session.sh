@@ -1,6 +1,6 @@
 #!/bin/bash
 # Profiling session on the GPU box (round 5), in PARTS of <= 20 minutes each (gpurun's limit per call):
-#   gpurun -- bash tools/profile_session.sh <part>      part = tests | prof | pmc | ab | bench
+#   bash tools/profile_session.sh <part>      part = tests | prof | pmc | bench
 # Outputs under gpurun_out/{prof_r05,pmc_r05}/ and gpurun_out/r05_*; processed by tools/pmc_traffic.py /
 # tools/valu_roofline.py / tools/pmc_abc.py into profiles/r05_*.json (which carry the hash of the library they were
 # measured on: bench.py reports counter-derived numbers only next to files of the same device code).
@@ -27,9 +27,6 @@ pmc)
   ./tools/ubench_int > gpurun_out/r05_ubench_int_issue_rates.txt 2>&1
   SESSION_SKIP= bash tools/pmc_abc_session.sh > gpurun_out/r05_pmc_abc.log 2>&1
   find gpurun_out/pmc_r05 -name "*.csv" | xargs ls -la | awk '{print $5, $9}';;
-ab)
-  GPU_MAX_HW_QUEUES=8 timeout -k 10 1000 bash tools/ab_rounds.sh 4 gpurun_out/r05_ab_rounds_final.txt r01=$V/libg16hip_r01.so:K r02=$V/libg16hip_r02.so r03=$V/libg16hip_r03.so r04=$V/libg16hip_r04.so r05=nim_groth16_amd/csrc/libg16hip.so > gpurun_out/r05_ab_final.log 2>&1
-  tail -7 gpurun_out/r05_ab_rounds_final.txt;;
 bench)
   timeout -k 10 700 python bench.py > gpurun_out/r05_bench_2p20_final.json 2> gpurun_out/r05_bench_final.err
   tail -4 gpurun_out/r05_bench_final.err; cut -c1-400 gpurun_out/r05_bench_2p20_final.json
@@ -37,5 +34,5 @@ bench)
   cut -c1-200 gpurun_out/r05_bench_2p20_steps20.json
   python tools/perf_poseidon.py > gpurun_out/r05_perf_poseidon_2p20_final.txt 2>&1
   grep -E "==|abc_|proofs/s" gpurun_out/r05_perf_poseidon_2p20_final.txt;;
-*) echo "usage: profile_session.sh tests|prof|pmc|ab|bench"; exit 2;;
+*) echo "usage: profile_session.sh tests|prof|pmc|bench"; exit 2;;
 esac
