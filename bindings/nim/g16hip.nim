@@ -2,7 +2,7 @@
 ##
 ## Keeps the reference's proc names and signatures (groth16/bn128/msm.nim:89,128,202-203; groth16/math/ntt.nim:55,139;
 ## groth16/prover.nim:215; groth16/verifier.nim:31) so that prover.nim compiles against it unchanged.
-## Assembled from INTEGRATION.md sections 2 and "Verifier".  NOT compile-tested: this image has no `nim` / `nimble`
+## Assembled from INTEGRATION.md sections 2, 3 and "Verifier".  NOT compile-tested: this image has no `nim` / `nimble`
 ## and constantine is not vendored (SURVEY.md section 8c); the same boundary is exercised through ctypes
 ## (nim_groth16_amd/_lib.py), plain C (examples/c_abi_demo.c) and C++ (tools/g16prove.cpp) by the GPU tests.
 ##
@@ -13,6 +13,7 @@ import groth16/bn128
 import groth16/math/domain
 import groth16/zkey_types
 import groth16/files/witness
+import std/tables
 
 {.passL: "-lg16hip".}
 type
@@ -110,6 +111,66 @@ proc generateProofWithMask*(nthreads: int, printTimings: bool, zkey: ZKey, wtns:
   check g16_prove(gctx, gkey, unsafeAddr wtns.values[0], G16_SCALARS_MONT, unsafeAddr mask.r, unsafeAddr mask.s, addr p)
   result = Proof(curve: "bn128", publicIO: wtns.values[0..zkey.header.npubs])        # prover.nim:238-240
   copyMem(addr result.pi_a, addr p.pi_a, 64); copyMem(addr result.pi_b, addr p.pi_b, 128); copyMem(addr result.pi_c, addr p.pi_c, 64)
+
+# --- proofs in flight from ONE thread: the prover pool (include/g16hip.h "prover pool") --------------------------------
+# generateProofWithMask above blocks for one proof; the multi-proof rate used to need three host threads with a context
+# each (INTEGRATION.md section 3).  A pool reaches it from the calling thread, with no thread inside the library:
+#   initG16Hip(); loadKeyGpu(zkey); let pool = newProverPool(3)
+#   submit until proveAsync returns 0 (G16_EBUSY), then repeat: collectProof the oldest ticket, proveAsync one more
+type
+  G16Prover {.importc: "g16_prover", header: "g16hip.h", incompleteStruct.} = object
+  ProverPool* = ref object
+    p: ptr G16Prover
+    publicIO: Table[uint64, seq[Fr]]       # per ticket: Proof.publicIO (prover.nim:238-240)
+const G16_EBUSY = -6'i32
+proc g16_prover_create(device: int32, key: ptr G16PKey, depth: uint32, pool: ptr ptr G16Prover): int32 {.importc, header: "g16hip.h".}
+proc g16_prover_destroy(pool: ptr G16Prover) {.importc, header: "g16hip.h".}
+proc g16_prover_last_error(pool: ptr G16Prover): cstring {.importc, header: "g16hip.h".}
+proc g16_prover_submit(pool: ptr G16Prover, witness: pointer, flags: uint32, r, s: pointer,
+                       ticket: ptr uint64): int32 {.importc, header: "g16hip.h".}
+proc g16_prover_poll(pool: ptr G16Prover, ticket: uint64): int32 {.importc, header: "g16hip.h".}
+proc g16_prover_collect(pool: ptr G16Prover, ticket: uint64, res: ptr G16Proof): int32 {.importc, header: "g16hip.h".}
+# pinned host memory: a witness there uploads without making proveAsync wait for the copy
+proc g16_host_alloc(device: int32, bytes: csize_t, res: ptr pointer): int32 {.importc, header: "g16hip.h".}
+proc g16_host_free(p: pointer) {.importc, header: "g16hip.h".}
+
+proc checkPool(pool: ProverPool, rc: int32) =
+  if rc < 0: raise newException(AssertionDefect, "g16hip pool: " & $g16_prover_last_error(pool.p))
+
+proc newProverPool*(depth = 3, device = 0): ProverPool =
+  ## after initG16Hip + loadKeyGpu: `depth` proofs on the GPU at once, all against the loaded key
+  result = ProverPool(publicIO: initTable[uint64, seq[Fr]]())
+  if g16_prover_create(int32(device), gkey, uint32(depth), addr result.p) != 0:
+    raise newException(AssertionDefect, "g16hip: g16_prover_create failed")
+
+proc proveAsync*(pool: ProverPool, zkey: ZKey, wtns: Witness, mask: Mask): uint64 =
+  ## generateProofWithMask without the wait: the ticket of the proof, or 0 while depth + 1 proofs are outstanding
+  ## (G16_EBUSY).  `wtns` must stay alive and unmodified until collectProof of its ticket has returned.
+  assert zkey.header.curve == wtns.curve and zkey.header.nvars == wtns.values.len   # prover.nim:224,236
+  let rc = g16_prover_submit(pool.p, unsafeAddr wtns.values[0], G16_SCALARS_MONT, unsafeAddr mask.r,
+                             unsafeAddr mask.s, addr result)
+  if rc == G16_EBUSY: return 0
+  pool.checkPool rc
+  pool.publicIO[result] = wtns.values[0..zkey.header.npubs]
+
+proc collectProof*(pool: ProverPool, ticket: uint64): Proof =
+  ## waits for the proof of `ticket`: the same bytes generateProofWithMask returns for the same inputs
+  var p: G16Proof
+  pool.checkPool g16_prover_collect(pool.p, ticket, addr p)
+  result = Proof(curve: "bn128", publicIO: pool.publicIO[ticket])
+  pool.publicIO.del(ticket)
+  copyMem(addr result.pi_a, addr p.pi_a, 64); copyMem(addr result.pi_b, addr p.pi_b, 128); copyMem(addr result.pi_c, addr p.pi_c, 64)
+
+proc proofDone*(pool: ProverPool, ticket: uint64): bool =
+  ## never blocks
+  let rc = g16_prover_poll(pool.p, ticket)
+  pool.checkPool rc
+  result = rc == 1
+
+proc destroy*(pool: ProverPool) =
+  ## waits for the outstanding proofs and discards them; the key stays loaded
+  if pool.p != nil: g16_prover_destroy(pool.p)
+  pool.p = nil
 
 # --- one proof over several GPUs of the node: the device group (include/g16hip.h "device group") ------------------------
 # The reference shards every MSM over Taskpool threads (msm.nim:96-122) and runs the three coset pipelines as three tasks

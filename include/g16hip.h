@@ -42,6 +42,7 @@ extern "C" {
 #define G16_EHIP (-3)    /* a HIP runtime call or kernel failed; see g16_last_error */
 #define G16_ENOMEM (-4)  /* device or host allocation failed */
 #define G16_ESELFTEST (-5)
+/* G16_EBUSY (-6): see the prover pool below */
 
 typedef struct g16_ctx g16_ctx;
 typedef struct g16_points g16_points; /* device-resident point set (ProverPoints member, zkey_types.nim:36-41) */
@@ -280,6 +281,43 @@ int32_t g16_group_pkey_create(g16_group* group, const g16_pkey_desc* desc, g16_g
 void g16_group_pkey_destroy(g16_group_pkey* key);
 int32_t g16_group_prove(g16_group* group, const g16_group_pkey* key, const void* witness, uint32_t flags,
                         const void* mask_r, const void* mask_s, g16_proof* out);
+
+/* ---- prover pool: proofs in flight from ONE host thread -------------------------------------------------------------
+ * generateProofWithMask (prover.nim:215-304) is one blocking call; g16_prove keeps that shape, so one caller gets one
+ * proof at a time.  A pool runs `depth` proofs on one GPU at once behind a submit / poll / collect interface, with no
+ * host thread inside the library: every step is taken inside the caller's own calls.
+ *   g16_prover_create: depth (1..8) = proofs running on the GPU at once; the pool owns `depth` contexts on `device`,
+ *       all proving against the one resident `key`, which must outlive the pool.  G16_EINVAL for a sharded key
+ *       (shard_count != 1), a key of another device, or depth 0 or > 8.
+ *   g16_prover_submit: never waits for the GPU.  Accepts up to depth + 1 outstanding (uncollected) proofs; the extra one
+ *       is PREFETCHED: its witness starts uploading at once (a copy stream and a device witness buffer owned by the pool)
+ *       and its kernels are enqueued as soon as any pool call (submit, poll, collect) sees a running proof finished.
+ *       With depth + 1 outstanding it returns G16_EBUSY, enqueues nothing and leaves the ticket counter unchanged.
+ *       flags: G16_SCALARS_MONT or G16_SCALARS_STD, | G16_SCALARS_DEVICE, as for g16_prove.  The masks (NULL = zero)
+ *       are copied before it returns; the witness must stay valid and unmodified until g16_prover_poll has returned 1
+ *       for its ticket or g16_prover_collect has returned.  A pageable host witness is accepted, but submit then returns
+ *       only once HIP has taken the copy: memory from g16_host_alloc avoids that.  Tickets count up from 1.
+ *   g16_prover_poll: never blocks; 1 = done, 0 = pending.  g16_prover_collect: waits for that ticket's proof and
+ *       writes exactly the bytes g16_prove(ctx, key, witness, flags, mask_r, mask_s, out) writes.  Both take tickets in
+ *       any order; an unknown ticket, and one already collected, give G16_EINVAL.
+ *   Failure: after the first HIP or allocation failure the pool is FAILED: every later submit / poll / collect returns
+ *       that code and g16_prover_last_error gives the first message.  Only g16_prover_destroy stays valid.
+ *   g16_prover_destroy: waits for every outstanding proof, discards them and releases what the pool owns; the key and
+ *       other contexts stay usable.
+ * A pool is used by one host thread at a time (any thread), like a g16_ctx; other contexts may prove against the same
+ * key concurrently.
+ *   g16_host_alloc / g16_host_free: pinned (page-locked) host memory for witnesses; G16_ENODEV without a device. */
+#define G16_EBUSY (-6) /* g16_prover_submit: depth + 1 proofs are already outstanding; nothing was enqueued */
+typedef struct g16_prover g16_prover;
+int32_t g16_prover_create(int32_t device, const g16_pkey* key, uint32_t depth, g16_prover** out);
+void g16_prover_destroy(g16_prover* p);
+const char* g16_prover_last_error(const g16_prover* p);
+int32_t g16_prover_submit(g16_prover* p, const void* witness, uint32_t flags, const void* mask_r, const void* mask_s,
+                          uint64_t* ticket);
+int32_t g16_prover_poll(g16_prover* p, uint64_t ticket); /* 1 done, 0 pending, <0 error */
+int32_t g16_prover_collect(g16_prover* p, uint64_t ticket, g16_proof* out);
+int32_t g16_host_alloc(int32_t device, size_t bytes, void** out); /* pinned host memory */
+void g16_host_free(void* p);
 
 /* ---- verifier ------------------------------------------------------------------------
  * Replaces verifyProof (groth16/verifier.nim:31-52), extractVKey / VKey (groth16/zkey_types.nim:62-73) and the

@@ -5,8 +5,8 @@ groth16/bn128/msm.nim, groth16/math/ntt.nim, groth16/math/domain.nim) over the C
 libg16hip.so (include/g16hip.h).  All arithmetic runs in hand-written HIP kernels; there is no CPU
 fallback -- importing works anywhere, but every compute call raises without the HIP library + a GPU.
 """
-from ._lib import (G16Error, Context, DeviceGroup, GroupKey, ProvingKey, PointSet, VerifyingKey,  # noqa: F401
-                   lib_path, load_library)
+from ._lib import (G16Error, Context, DeviceGroup, GroupKey, HostBuffer, ProverPool, ProvingKey,  # noqa: F401
+                   PointSet, VerifyingKey, lib_path, load_library)
 from .msm import (msmMultiThreadedG1, msmMultiThreadedG2, msmG1, msmG2)  # noqa: F401
 from .ntt import (Domain, createDomain, forwardNTT, inverseNTT, extendAndForwardNTT,  # noqa: F401
                   polyForwardNTT, polyInverseNTT)

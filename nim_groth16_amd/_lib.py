@@ -8,7 +8,7 @@ import weakref
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
-G16_OK, G16_EINVAL, G16_ENODEV, G16_EHIP, G16_ENOMEM, G16_ESELFTEST = 0, -1, -2, -3, -4, -5
+G16_OK, G16_EINVAL, G16_ENODEV, G16_EHIP, G16_ENOMEM, G16_ESELFTEST, G16_EBUSY = 0, -1, -2, -3, -4, -5, -6
 SCALARS_MONT, SCALARS_STD, SCALARS_DEVICE, OUT_PARTIAL, OUT_DEVICE, NO_HOST_SYNC = 1, 0, 2, 4, 8, 32
 PARTIALS_BYTES = 768
 
@@ -26,6 +26,8 @@ SYMBOLS = [
     "g16_vkey_create", "g16_vkey_destroy", "g16_verify", "g16_pairing",
     "g16_ctx_cancel", "g16_group_create", "g16_group_destroy", "g16_group_size", "g16_group_last_error",
     "g16_group_pkey_create", "g16_group_pkey_destroy", "g16_group_prove",
+    "g16_prover_create", "g16_prover_destroy", "g16_prover_last_error", "g16_prover_submit", "g16_prover_poll",
+    "g16_prover_collect", "g16_host_alloc", "g16_host_free",
 ]
 VERIFY_SUBGROUP = 16
 GT_BYTES = 384
@@ -169,6 +171,17 @@ def load_library():
     lib.g16_group_pkey_destroy.argtypes = [vp]
     lib.g16_group_pkey_destroy.restype = None
     lib.g16_group_prove.argtypes = [vp, vp, vp, u32, vp, vp, vp]
+    lib.g16_prover_create.argtypes = [i32, vp, u32, ctypes.POINTER(vp)]
+    lib.g16_prover_destroy.argtypes = [vp]
+    lib.g16_prover_destroy.restype = None
+    lib.g16_prover_last_error.argtypes = [vp]
+    lib.g16_prover_last_error.restype = ctypes.c_char_p
+    lib.g16_prover_submit.argtypes = [vp, vp, u32, vp, vp, ctypes.POINTER(ctypes.c_uint64)]
+    lib.g16_prover_poll.argtypes = [vp, ctypes.c_uint64]
+    lib.g16_prover_collect.argtypes = [vp, ctypes.c_uint64, vp]
+    lib.g16_host_alloc.argtypes = [i32, sz, ctypes.POINTER(vp)]
+    lib.g16_host_free.argtypes = [vp]
+    lib.g16_host_free.restype = None
     lib.g16_profile_enable.argtypes = [vp, i32]
     lib.g16_profile_reset.argtypes = [vp]
     lib.g16_profile_report.argtypes = [vp, ctypes.c_char_p, sz]
@@ -177,7 +190,7 @@ def load_library():
         if name not in ("g16_ctx_destroy", "g16_last_error", "g16_points_release", "g16_points_count",
                         "g16_points_inf_count",
                         "g16_pkey_destroy", "g16_vkey_destroy", "g16_group_destroy", "g16_group_last_error",
-                        "g16_group_pkey_destroy"):
+                        "g16_group_pkey_destroy", "g16_prover_destroy", "g16_prover_last_error", "g16_host_free"):
             getattr(lib, name).restype = i32
     _lib = lib
     return lib
@@ -543,6 +556,107 @@ class GroupKey:
     def __del__(self):
         try:
             self.destroy()
+        except Exception:
+            pass
+
+
+class ProverPool:
+    """g16_prover: `depth` proofs in flight on one GPU from ONE host thread, against one resident key (include/g16hip.h,
+    "prover pool").  submit() never waits for the GPU and accepts depth + 1 outstanding proofs (the extra one's witness
+    uploads while the others run); collect() returns what ProvingKey.prove returns for the same inputs.  The witness
+    object is kept alive here until its proof is collected."""
+
+    def __init__(self, pkey: ProvingKey, depth: int = 3, device: int = 0):
+        self._lib = load_library()
+        self.pkey, self.depth, self.device = pkey, depth, device   # the key must outlive the pool
+        h = ctypes.c_void_p()
+        rc = self._lib.g16_prover_create(device, pkey._h, depth, ctypes.byref(h))
+        if rc != G16_OK:
+            raise G16Error(rc, "g16_prover_create failed (sharded key, key of another device, or depth not in 1..8)")
+        self._h = h
+        self._witness = {}                 # ticket -> witness object (the library reads it until the proof is done)
+
+    def _check(self, rc):
+        if rc == G16_EBUSY:
+            raise G16Error(rc, f"{self.depth + 1} proofs outstanding: collect one first")
+        if rc < 0:
+            raise G16Error(rc, self._lib.g16_prover_last_error(self._h).decode())
+        return rc
+
+    def submit(self, witness, mont: bool = True, r: bytes = None, s: bytes = None, device: bool = False) -> int:
+        """-> ticket.  witness: bytes / bytearray / numpy array / HostBuffer, or with device=True a device pointer (int)
+        or a GPU tensor (the caller orders its writes before the call, e.g. torch.cuda.synchronize()); r, s: Fr
+        Montgomery bytes or None.  Raises G16Error with code G16_EBUSY when depth + 1 proofs are outstanding."""
+        self.pkey._check_len(witness)
+        if isinstance(witness, HostBuffer) and witness.nbytes < 32 * self.pkey.nvars:
+            raise ValueError("host buffer shorter than the witness")
+        ptr = ctypes.c_void_p(witness.data_ptr()) if device and hasattr(witness, "data_ptr") else _buf(witness)
+        t = ctypes.c_uint64()
+        flags = (SCALARS_MONT if mont else 0) | (SCALARS_DEVICE if device else 0)
+        self._check(self._lib.g16_prover_submit(self._h, ptr, flags, _buf(r) if r else None,
+                                                _buf(s) if s else None, ctypes.byref(t)))
+        self._witness[t.value] = witness
+        return t.value
+
+    def poll(self, ticket: int) -> bool:
+        return self._check(self._lib.g16_prover_poll(self._h, ticket)) == 1
+
+    def collect(self, ticket: int):
+        """-> (pi_a 64 B, pi_b 128 B, pi_c 64 B); waits for the proof"""
+        out = ctypes.create_string_buffer(256)
+        self._check(self._lib.g16_prover_collect(self._h, ticket, out))
+        self._witness.pop(ticket, None)
+        raw = out.raw
+        return raw[0:64], raw[64:192], raw[192:256]
+
+    def close(self):
+        """waits for the outstanding proofs and discards them"""
+        if getattr(self, "_h", None):
+            self._lib.g16_prover_destroy(self._h)
+            self._h = None
+            self._witness.clear()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class HostBuffer:
+    """Pinned (page-locked) host memory from g16_host_alloc: a witness in it uploads without blocking submit().
+    `.array` is a uint8 numpy view; the buffer passes anywhere a host pointer is taken."""
+
+    def __init__(self, nbytes: int, device: int = 0):
+        import numpy as np
+        self._lib = load_library()
+        p = ctypes.c_void_p()
+        rc = self._lib.g16_host_alloc(device, nbytes, ctypes.byref(p))
+        if rc != G16_OK:
+            raise G16Error(rc, "g16_host_alloc failed")
+        self._p, self.nbytes = p, nbytes
+        self.array = np.ctypeslib.as_array((ctypes.c_uint8 * nbytes).from_address(p.value))
+        self.ctypes = self.array.ctypes    # (_buf takes the pointer from here)
+
+    @classmethod
+    def from_bytes(cls, data: bytes, device: int = 0) -> "HostBuffer":
+        import numpy as np
+        b = cls(len(data), device)
+        b.array[:] = np.frombuffer(data, dtype=np.uint8)
+        return b
+
+    def __len__(self):
+        return self.nbytes
+
+    def free(self):
+        if getattr(self, "_p", None):
+            self.array = self.ctypes = None
+            self._lib.g16_host_free(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.free()
         except Exception:
             pass
 

@@ -317,3 +317,19 @@ int32_t g16_quotient_device(g16_ctx* ctx, const void* d_a, const void* d_b, cons
 int32_t g16_coset_pipeline_device(g16_ctx* ctx, const void* d_in, uint32_t log2n, void* d_out);
 int32_t g16_abc_pointwise_device(g16_ctx* ctx, const void* d_a, const void* d_b, const void* d_c, size_t count,
                                  void* d_out);
+
+// ---- the two halves of g16_prove_combine (prover.hip), shared with the prover pool (pool.hip) ----------------------
+// What the finish half needs from the enqueue half: the mask in standard form and the mask-only parts of the proof
+// (r, s; alpha1 + r delta1; beta2 + s delta2; s alpha1 + r beta1 + rs delta1), as bytes.
+struct g16_combine_pre {
+  unsigned char r_std[32], s_std[32];
+  unsigned char a_pre[64], b_pre[128], c_pre[64];
+};
+#define G16_COMBINE_RES_BYTES 384   // the five affine MSM sums A1 | B1 | B2 | H1 | C1 the combine kernel writes
+// stage copy + combine kernel on ctx->stream, host algebra, then the 384-byte D2H into res_host (+ event `done`)
+int32_t g16_combine_enqueue(g16_ctx* ctx, const g16_pkey* k, const void* partials, size_t count, uint32_t flags,
+                            const void* mask_r, const void* mask_s, void* res_host, hipEvent_t done,
+                            g16_combine_pre* pre);
+// the additions and the one joint multiplication on the MSM sums; res_host must be complete
+void g16_combine_finish(const g16_combine_pre* pre, const void* res_host, g16_proof* out);
+void g16_pkey_shape(const g16_pkey* k, int* device, uint32_t* nvars, uint32_t* shard_count);

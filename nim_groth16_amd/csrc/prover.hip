@@ -125,6 +125,13 @@ extern "C" void g16_pkey_destroy(g16_pkey* k) {
   delete k;
 }
 
+// what the prover pool (pool.hip) needs to know about a key
+void g16_pkey_shape(const g16_pkey* k, int* device, uint32_t* nvars, uint32_t* shard_count) {
+  *device = k->device;
+  *nvars = k->nvars;
+  *shard_count = k->shard_count;
+}
+
 // points at infinity per set: out[0..4] = A1, B1, B2, C1 (without the public wires this library pads it with), H1;
 // out[5] = wires whose B1 and B2 points are both (0,0); out[6] = 1 if A1, out[7] = 1 if B1/B2 use compacted entry lists
 extern "C" int32_t g16_pkey_inf_counts(const g16_pkey* k, size_t out[8]) {
@@ -641,14 +648,27 @@ static __global__ void prove_combine_kernel(const unsigned char* __restrict__ ga
   }
 }
 
-extern "C" int32_t g16_prove_combine(g16_ctx* ctx, const g16_pkey* k, const void* partials, size_t count,
-                                     uint32_t flags, const void* mask_r, const void* mask_s, g16_proof* out) {
-  if (!ctx) return G16_EINVAL;
-  if (!k || !partials || !out || k->device != ctx->device || count == 0 || count > 1024) {
-    ctx->err = "bad argument";
-    return G16_EINVAL;
-  }
-  CTX_ENTER(ctx);
+// g16_prove_combine in two halves, shared with the prover pool (pool.hip).
+// Enqueue half: stage copy + prove_combine_kernel on the context's main stream, the host algebra that needs only the
+// mask and the key, then the copy of the five affine MSM sums (384 bytes) into `res_host` and, if `done` is given, an
+// event behind it.  Into pageable memory the copy makes the host wait for the stream; into pinned memory it does not.
+struct CombineRes {
+  g1_aff a, b1;
+  g2_aff b2;
+  g1_aff h, c;
+};
+static_assert(sizeof(CombineRes) == G16_COMBINE_RES_BYTES, "slot layout");
+struct CombinePre {
+  u256 r_std, s_std;
+  g1_aff a_pre;
+  g2_aff b_pre;
+  g1_aff c_pre;
+};
+static_assert(sizeof(CombinePre) == sizeof(g16_combine_pre), "g16_combine_pre layout");
+
+int32_t g16_combine_enqueue(g16_ctx* ctx, const g16_pkey* k, const void* partials, size_t count, uint32_t flags,
+                            const void* mask_r, const void* mask_s, void* res_host, hipEvent_t done,
+                            g16_combine_pre* pre_out) {
   int32_t rc;
   if ((rc = ensure(ctx, ctx->stage_p, count * PART_BYTES))) return rc;
   if ((rc = ensure(ctx, ctx->stage_o, 2048))) return rc;
@@ -658,12 +678,6 @@ extern "C" int32_t g16_prove_combine(g16_ctx* ctx, const g16_pkey* k, const void
   unsigned char* d_res = (unsigned char*)ctx->stage_o.p + 1024;
   KLAUNCH(ctx, "prove_combine", prove_combine_kernel, 5, 64, 0, (const unsigned char*)ctx->stage_p.p, (uint32_t)count,
           d_res);
-  struct {
-    g1_aff a, b1;
-    g2_aff b2;
-    g1_aff h, c;
-  } res;
-  static_assert(sizeof(res) == 384, "slot layout");
 
   // Everything that depends on the mask and the key alone is computed while the GPU works -- in g16_prove that is the
   // whole proof, which is enqueued without a host wait (prover.nim:267-268, 279-302 regrouped):
@@ -674,24 +688,50 @@ extern "C" int32_t g16_prove_combine(g16_ctx* ctx, const g16_pkey* k, const void
   u256 r = Fr::zero(), s = Fr::zero();
   if (mask_r) memcpy(&r, mask_r, 32);
   if (mask_s) memcpy(&s, mask_s, 32);
-  const u256 r_std = Fr::from_mont(r), s_std = Fr::from_mont(s);
+  CombinePre pre;
+  pre.r_std = Fr::from_mont(r), pre.s_std = Fr::from_mont(s);
   const u256 rs_std = Fr::from_mont(Fr::mul(r, s));
-  const g1_aff a_pre = host_add<HG1>(k->alpha1, host_mul<HG1>(r_std, k->delta1));
-  const g2_aff b_pre = host_add<HG2>(k->beta2, host_mul<HG2>(s_std, k->delta2));
-  const g1_aff c_pre = host_add<HG1>(host_mul2<HG1>(s_std, k->alpha1, r_std, k->beta1), host_mul<HG1>(rs_std, k->delta1));
-  // (the copy into pageable host memory makes the host wait for the stream: it comes AFTER the host arithmetic above)
-  HIPCHK(ctx, hipMemcpyAsync(&res, d_res, sizeof(res), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  pre.a_pre = host_add<HG1>(k->alpha1, host_mul<HG1>(pre.r_std, k->delta1));
+  pre.b_pre = host_add<HG2>(k->beta2, host_mul<HG2>(pre.s_std, k->delta2));
+  pre.c_pre = host_add<HG1>(host_mul2<HG1>(pre.s_std, k->alpha1, pre.r_std, k->beta1), host_mul<HG1>(rs_std, k->delta1));
+  memcpy(pre_out, &pre, sizeof pre);
+  // (a copy into pageable host memory makes the host wait for the stream: it comes AFTER the host arithmetic above)
+  HIPCHK(ctx, hipMemcpyAsync(res_host, d_res, sizeof(CombineRes), hipMemcpyDeviceToHost, ctx->stream));
+  if (done) HIPCHK(ctx, hipEventRecord(done, ctx->stream));
+  return G16_OK;
+}
 
-  // what needs the MSM results: three additions and ONE joint double-scalar multiplication
-  g1_aff pi_a = host_add<HG1>(a_pre, res.a);
-  g2_aff pi_b = host_add<HG2>(b_pre, res.b2);
-  g1_aff pi_c = host_add<HG1>(c_pre, host_mul2<HG1>(s_std, res.a, r_std, res.b1));
+// Finish half: what needs the MSM results -- three additions and ONE joint double-scalar multiplication.  `res_host`
+// must be complete (the stream or the enqueue half's event has passed the copy).
+void g16_combine_finish(const g16_combine_pre* pre_in, const void* res_host, g16_proof* out) {
+  CombinePre pre;
+  CombineRes res;
+  memcpy(&pre, pre_in, sizeof pre);
+  memcpy(&res, res_host, sizeof res);
+  g1_aff pi_a = host_add<HG1>(pre.a_pre, res.a);
+  g2_aff pi_b = host_add<HG2>(pre.b_pre, res.b2);
+  g1_aff pi_c = host_add<HG1>(pre.c_pre, host_mul2<HG1>(pre.s_std, res.a, pre.r_std, res.b1));
   pi_c = host_add<HG1>(pi_c, res.h);
   pi_c = host_add<HG1>(pi_c, res.c);
   memcpy(out->pi_a, &pi_a, 64);
   memcpy(out->pi_b, &pi_b, 128);
   memcpy(out->pi_c, &pi_c, 64);
+}
+
+extern "C" int32_t g16_prove_combine(g16_ctx* ctx, const g16_pkey* k, const void* partials, size_t count,
+                                     uint32_t flags, const void* mask_r, const void* mask_s, g16_proof* out) {
+  if (!ctx) return G16_EINVAL;
+  if (!k || !partials || !out || k->device != ctx->device || count == 0 || count > 1024) {
+    ctx->err = "bad argument";
+    return G16_EINVAL;
+  }
+  CTX_ENTER(ctx);
+  int32_t rc;
+  CombineRes res;
+  g16_combine_pre pre;
+  if ((rc = g16_combine_enqueue(ctx, k, partials, count, flags, mask_r, mask_s, &res, nullptr, &pre))) return rc;
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  g16_combine_finish(&pre, &res, out);
   return G16_OK;
 }
 
