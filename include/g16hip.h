@@ -136,6 +136,7 @@ int32_t g16_fixed_base_g2(g16_ctx* ctx, const void* scalars, uint32_t scalar_fla
 /* natural order in and out; forward unscaled, inverse includes 1/n; omega = gen28^(2^(28-log2n))
  * (math/domain.nim:26-33).  src/dst: n = 2^log2n Fr elements (Montgomery), host memory. 0 <= log2n <= 28 */
 int32_t g16_ntt_fr(g16_ctx* ctx, const void* src, void* dst, uint32_t log2n, int32_t inverse);
+/* _dev: device pointers on the context's device, ordered on its stream; d_dst may equal d_src (in place). */
 int32_t g16_ntt_fr_dev(g16_ctx* ctx, const void* d_src, void* d_dst, uint32_t log2n, int32_t inverse);
 
 /* ---- quotient: replaces computeSnarkjsScalarCoeffs (flavour 1, groth16/prover.nim:158-181) and

@@ -4,6 +4,7 @@
 
 #include "g16_internal.hpp"
 #include "ntt.cuh"
+#include "ntt_plan.hpp"
 
 using namespace g16;
 
@@ -19,9 +20,15 @@ static int32_t ensure_twiddles(g16_ctx* ctx, uint32_t log2n) {
   return G16_OK;
 }
 
-// dynamic LDS of a pass: tile + R/2 inner twiddles.  Up to 144 KB: above the 64 KB default, so the kernels are
-// opted in once per process.
-static size_t pass_shmem(uint32_t rho, uint32_t log2b) { return (size_t(32) << (rho + log2b)) + (size_t(16) << rho); }
+// the pass plans (ntt_plan.hpp) describe the geometries instantiated in ntt.cuh
+static_assert(ntt_geom(NTT_TILE_SMALL).max_rho == NTT_MAX_RHO_SMALL &&
+                  (1 << ntt_geom(NTT_TILE_SMALL).log2tile) == NTT_TILE_SMALL,
+              "ntt_plan.hpp and ntt.cuh disagree on the 1024 geometry");
+static_assert(ntt_geom(NTT_TILE_MID).max_rho == NTT_MAX_RHO && (1 << ntt_geom(NTT_TILE_MID).log2tile) == NTT_TILE_MID,
+              "ntt_plan.hpp and ntt.cuh disagree on the 2048 geometry");
+static_assert(ntt_geom(NTT_TILE).max_rho == NTT_MAX_RHO && (1 << ntt_geom(NTT_TILE).log2tile) == NTT_TILE,
+              "ntt_plan.hpp and ntt.cuh disagree on the 4096 geometry");
+static_assert(ntt_optin_shmem() == ntt_pass_shmem(NTT_MAX_RHO, 2), "the opt-in covers the largest pass");
 static int32_t ntt_kernels_init(g16_ctx* ctx) {
   // per device (the attribute belongs to the device's copy of the code object).  Contexts of one device are used from
   // several host threads at once (the in-flight proofs of bench.py): the flag is published with release semantics
@@ -32,7 +39,7 @@ static int32_t ntt_kernels_init(g16_ctx* ctx) {
   if (done.load(std::memory_order_acquire)) return G16_OK;
   std::lock_guard<std::mutex> lock(mu);
   if (done.load(std::memory_order_relaxed)) return G16_OK;
-  const int max_shmem = (int)pass_shmem(NTT_MAX_RHO, 2);
+  const int max_shmem = (int)ntt_optin_shmem();
   static_assert((size_t(32) * NTT_TILE) + (size_t(16) << NTT_MAX_RHO) <= 160 * 1024, "tile + twiddles must fit the LDS");
   HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&ntt_pass<NTT_BLOCK>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, max_shmem));
@@ -65,8 +72,8 @@ static int32_t ntt_batched(g16_ctx* ctx, const u256* in, size_t in_stride, u256*
   }
   // passes of <= 10 stages: one up to 2^10, two up to 2^20, three beyond (small geometry: <= 8 stages per pass)
   const bool small = g16_env().ntt_tile == NTT_TILE_SMALL, mid = g16_env().ntt_tile == NTT_TILE_MID;
-  const uint32_t max_rho = small ? NTT_MAX_RHO_SMALL : NTT_MAX_RHO, log2tile = small ? 10 : mid ? 11 : 12;
-  const uint32_t npass = log2n ? (log2n + max_rho - 1) / max_rho : 1;
+  const NttGeom geom = ntt_geom(g16_env().ntt_tile);
+  const uint32_t npass = ntt_npass(geom, log2n);
   u256 *tmpA = nullptr, *tmpB = nullptr;
   if (npass > 1) {
     if ((rc = ensure(ctx, ctx->ntt_tmp, (npass > 2 ? 2 : 1) * n * 32 * batch))) return rc;
@@ -75,14 +82,11 @@ static int32_t ntt_batched(g16_ctx* ctx, const u256* in, size_t in_stride, u256*
   }
   const u256* src = in;
   size_t src_stride = in_stride;
-  uint32_t log2s = 0;
   for (uint32_t p = 0; p < npass; ++p) {
-    uint32_t rho = log2n / npass + (p < log2n % npass ? 1u : 0u);
-    uint32_t log2b = log2tile - rho;
-    if (log2b > log2n - rho) log2b = log2n - rho;
+    const NttPass plan = ntt_pass_plan(geom, log2n, p);
+    const uint32_t rho = plan.rho, log2b = plan.log2b, log2s = plan.log2s, ntiles = plan.ntiles;
     const bool last = p + 1 == npass;
-    const size_t shmem = pass_shmem(rho, log2b);
-    const uint32_t ntiles = 1u << (log2n - rho - log2b);
+    const size_t shmem = plan.shmem;
     if (last && fuse_abc) {
       if (small)
         KLAUNCH(ctx, "ntt_last_pass_abc", (ntt_last_pass_abc<NTT_BLOCK_SMALL, NTT_TILE_SMALL>), ntiles, NTT_BLOCK_SMALL,
@@ -111,15 +115,13 @@ static int32_t ntt_batched(g16_ctx* ctx, const u256* in, size_t in_stride, u256*
               dst_stride, last ? scale : (const u256*)nullptr, p == 0 ? c_from_ab : 0);
     src = dst;
     src_stride = dst_stride;
-    log2s += rho;
   }
   HIPCHK(ctx, hipGetLastError());
   return G16_OK;
 }
 
 int32_t g16_ntt_device(g16_ctx* ctx, const void* d_src, void* d_dst, uint32_t log2n, int inverse) {
-  const uint32_t one_pass = g16_env().ntt_tile == NTT_TILE_SMALL ? NTT_MAX_RHO_SMALL : NTT_MAX_RHO;
-  if (d_src == d_dst && log2n <= one_pass && log2n > 0) {   // single pass: never in place
+  if (d_src == d_dst && ntt_one_pass(ntt_geom(g16_env().ntt_tile), log2n) && log2n > 0) {   // single pass: never in place
     int32_t rc = ensure(ctx, ctx->ntt_tmp, (size_t(32) << log2n));
     if (rc) return rc;
     if ((rc = ntt_batched(ctx, (const u256*)d_src, 0, (u256*)ctx->ntt_tmp.p, 0, 1, log2n, inverse, nullptr))) return rc;
@@ -169,7 +171,7 @@ int32_t g16_quotient_device(g16_ctx* ctx, const void* d_a, const void* d_b, cons
     HIPCHK(ctx, hipMemcpyAsync(X + n, d_b, n * 32, hipMemcpyDeviceToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(X + 2 * n, d_c, n * 32, hipMemcpyDeviceToDevice, ctx->stream));
     in = X;
-    if (log2n <= (g16_env().ntt_tile == NTT_TILE_SMALL ? NTT_MAX_RHO_SMALL : NTT_MAX_RHO)) {   // a single pass cannot run in place: stage behind the work area
+    if (ntt_one_pass(ntt_geom(g16_env().ntt_tile), log2n)) {   // a single pass cannot run in place: stage behind the work area
       if ((rc = ensure(ctx, ctx->ntt_tmp, 3 * n * 32))) return rc;
       HIPCHK(ctx, hipMemcpyAsync(ctx->ntt_tmp.p, X, 3 * n * 32, hipMemcpyDeviceToDevice, ctx->stream));
       in = (const u256*)ctx->ntt_tmp.p;

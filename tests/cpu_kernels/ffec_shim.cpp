@@ -4,6 +4,7 @@
 #include "../../nim_groth16_amd/csrc/pairing.cuh"
 #include "../../nim_groth16_amd/csrc/msm_params.hpp"
 #include "../../nim_groth16_amd/csrc/spmv_params.hpp"
+#include "../../nim_groth16_amd/csrc/ntt_plan.hpp"
 #include <cstring>
 #include <vector>
 using namespace g16;
@@ -86,6 +87,27 @@ uint32_t shim_spmv_bins_check(uint32_t max_len) {
     if (b == 2 && (L < 3 || L > 4)) return 1 + L;
   }
   return 0;
+}
+
+// the NTT pass plan of geometry `tile` (ntt_plan.hpp) at 2^log2n: geometry {log2tile, max_rho, opt-in LDS, one-pass},
+// then per pass {rho, log2b, log2s, ntiles, shmem} into out[4 + 5 p ..].  -> npass
+uint32_t shim_ntt_plan(int tile, uint32_t log2n, uint64_t* out) {
+  const NttGeom g = ntt_geom(tile);
+  const uint32_t npass = ntt_npass(g, log2n);
+  out[0] = g.log2tile;
+  out[1] = g.max_rho;
+  out[2] = ntt_optin_shmem();
+  out[3] = ntt_one_pass(g, log2n) ? 1 : 0;
+  for (uint32_t p = 0; p < npass; ++p) {
+    const NttPass q = ntt_pass_plan(g, log2n, p);
+    uint64_t* o = out + 4 + 5 * p;
+    o[0] = q.rho;
+    o[1] = q.log2b;
+    o[2] = q.log2s;
+    o[3] = q.ntiles;
+    o[4] = q.shmem;
+  }
+  return npass;
 }
 
 // the class bucket set of registered point sets with two multiplier tables (msm_params.hpp): every digit magnitude

@@ -18,7 +18,8 @@ def shim():
     so = os.path.join(HERE, "libffec_shim.so")
     src = os.path.join(HERE, "ffec_shim.cpp")
     import glob
-    deps = [src] + glob.glob(os.path.join(HERE, "..", "..", "nim_groth16_amd", "csrc", "*.cuh"))
+    deps = [src] + glob.glob(os.path.join(HERE, "..", "..", "nim_groth16_amd", "csrc", "*.cuh")) + \
+        glob.glob(os.path.join(HERE, "..", "..", "nim_groth16_amd", "csrc", "*.hpp"))
     if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", src, "-o", so])
     return ctypes.CDLL(so)
@@ -233,3 +234,57 @@ def test_spmv_row_bins(shim):
     shim.shim_spmv_bins_check.restype = ctypes.c_uint32
     assert shim.shim_spmv_bins_check(100000) == 0
 
+
+
+# G16_NTT_TILE -> (log2tile, max_rho), as ntt.cuh documents the three geometries
+NTT_GEOMS = {1024: (10, 8), 2048: (11, 10), 4096: (12, 10)}
+
+
+def ntt_plan_rule(tile, log2n):
+    """the pass plan of ntt.cuh, restated: ceil(log2n / max_rho) passes (one at log2n = 0), the stages dealt as evenly
+    as possible with the first log2n % npass passes taking one more, tiles of 2^log2b bases filling 2^log2tile elements
+    but no more bases than the transform has; LDS = tile + R/2 twiddles.  -> [(rho, log2b, log2s, ntiles, shmem)]"""
+    log2tile, max_rho = NTT_GEOMS[tile]
+    npass = max(1, -(-log2n // max_rho))
+    out, log2s = [], 0
+    for p in range(npass):
+        rho = log2n // npass + (1 if p < log2n % npass else 0)
+        log2b = min(log2tile - rho, log2n - rho)
+        out.append((rho, log2b, log2s, 1 << (log2n - rho - log2b), (32 << (rho + log2b)) + (16 << rho)))
+        log2s += rho
+    return out
+
+
+def test_ntt_pass_plans_every_geometry_and_size(shim):
+    """ntt_plan.hpp: every geometry x log2n 0..28 -- the stages add up, no pass exceeds its geometry's tile or the LDS
+    the kernels are opted in to, the tiles cover the transform exactly, every pass starts where the previous ones
+    ended, the pass counts are the documented ones, and each plan equals the restated rule"""
+    shim.shim_ntt_plan.restype = ctypes.c_uint32
+    shim.shim_ntt_plan.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64)]
+    buf = (ctypes.c_uint64 * (4 + 5 * 8))()
+    for tile, (log2tile, max_rho) in NTT_GEOMS.items():
+        for log2n in range(29):
+            n = 1 << log2n
+            npass = shim.shim_ntt_plan(tile, log2n, buf)
+            assert 1 <= npass <= 4, (tile, log2n)
+            assert (buf[0], buf[1]) == (log2tile, max_rho), tile
+            optin = buf[2]
+            assert optin <= 160 * 1024
+            assert buf[3] == (1 if log2n <= max_rho else 0), (tile, log2n)            # the one-pass threshold
+            plan = [tuple(buf[4 + 5 * p: 9 + 5 * p]) for p in range(npass)]
+            where = f"G16_NTT_TILE={tile} log2n={log2n}: {plan}"
+            assert sum(p[0] for p in plan) == log2n, where
+            log2s = 0
+            for rho, log2b, s, ntiles, shmem in plan:
+                assert (1 <= rho <= max_rho) if log2n else rho == 0, where
+                assert rho + log2b <= log2tile and rho + log2b <= log2n, where
+                assert ntiles << (rho + log2b) == n, where
+                assert s == log2s, where
+                assert shmem == (32 << (rho + log2b)) + (16 << rho) and shmem <= optin, where
+                log2s += rho
+            if tile == 1024:
+                want = 1 if log2n <= 8 else 2 if log2n <= 16 else 3 if log2n <= 24 else 4
+            else:
+                want = 1 if log2n <= 10 else 2 if log2n <= 20 else 3
+            assert npass == want, where
+            assert plan == ntt_plan_rule(tile, log2n), where

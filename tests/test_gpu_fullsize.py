@@ -20,8 +20,10 @@ def _bytes(vals):
     return F.frSeqToMontBytes(vals)
 
 
-# sizes 2^15 .. 2^19 walk the merged-bucket fold through 2, 4, 8, 16, 32 reduction slices (64 at 2^20)
-@pytest.mark.parametrize("group,log2n", [(1, 20), (2, 18), (2, 20), (1, 15), (1, 16), (1, 17), (1, 19), (2, 15), (2, 16)])
+# sizes 2^15 .. 2^19 walk the merged-bucket fold through 2, 4, 8, 16, 32 reduction slices (64 at 2^20); 2^23 is the
+# smallest registered set with the window of every point set of a 2^24 key (c = 22: 2048 reduce2 chunks per slice)
+@pytest.mark.parametrize("group,log2n", [(1, 20), (2, 18), (2, 20), (1, 15), (1, 16), (1, 17), (1, 19), (2, 15), (2, 16),
+                                         (1, 23), (2, 23)])
 def test_msm_fullsize_known_discrete_logs(ctx, orc, group, log2n):
     """P_i = k_i * G, so that sum s_i P_i = (sum s_i k_i mod r) * G  (SURVEY 8d config 2 check).  The point set is
     produced by the product's fixed-base kernel (the oracle would take minutes at 2^20); the EXPECTED value is the
@@ -46,10 +48,17 @@ def test_msm_fullsize_known_discrete_logs(ctx, orc, group, log2n):
         assert ctx.msm(group, sb, pts, n) == exp                 # one-shot path (no tables)
     h = ctx.register_points(group, pts, n)
     try:
-        assert ctx.msm_points(h, sb) == exp
+        c, ntab = h.info()
+        layout = f"c = {c}, {ntab} tables: {'two tables' if ntab == 2 * (254 // c + 1) else 'one table'} per window"
+        if log2n >= 23:
+            assert c == 22, layout                               # the cost model's window (msm_host.cuh)
+            # two tables per window, or one when they do not fit the free HBM (points_register falls back silently;
+            # G16_MTAB=1 in test_gpu_knobs.py holds that layout at c = 20 and 22 too)
+            assert ntab in (24, 12), layout
+        assert ctx.msm_points(h, sb) == exp, layout
         # linearity in the scalars: MSM(2 s) == 2 MSM(s)
         two = ctx.msm_points(h, _bytes([2 * s % R for s in sc]))
-        assert two == orc.mul(group, _bytes([2 * e % R]), gen)
+        assert two == orc.mul(group, _bytes([2 * e % R]), gen), layout
     finally:
         h.release()
 

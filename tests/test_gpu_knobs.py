@@ -64,6 +64,9 @@ for group, n in ((1, 3000), (2, 700), (1, 64), (1, 1)):
     want = orc.msm(group, I.fr_mont_bytes(sc), pts)
     assert ctx.msm(group, I.fr_mont_bytes(sc), pts, n) == want
     h = ctx.register_points(group, pts, n)
+    c, ntab = h.info()                                          # the forced window and table layout are the ones run
+    assert c == int(os.environ.get("G16_TABLE_WINDOW", c)), (c, ntab)
+    assert ntab == (2 if os.environ.get("G16_MTAB") != "1" and c >= 15 else 1) * (254 // c + 1), (c, ntab)
     assert ctx.msm_points(h, I.fr_mont_bytes(sc)) == want
     assert ctx.msm_points(h, I.fr_std_bytes(sc), mont=False) == want
     h.release()
@@ -105,6 +108,15 @@ KNOBS = [
     {"G16_QUOTIENT_FIRST": "0", "G16_G2_FIRST": "1"},
     {"G16_CU_SPLIT": "8"},                                      # main stream on 8 CUs per XCD, lanes on the rest (H on the spare lane)
     {"G16_CU_SPLIT": "4", "G16_HEAVY_GRID": "64", "G16_QUOTIENT_FIRST": "0"},
+    # the table windows of large registered sets (the cost model picks 17 from 2^17 points, 20 from 2^20, 22 from 2^23)
+    {"G16_TABLE_WINDOW": "18"},
+    {"G16_TABLE_WINDOW": "19"},
+    {"G16_TABLE_WINDOW": "20"},
+    {"G16_TABLE_WINDOW": "21"},                                 # accepted though the cost model never picks it: 2-bit top window
+    {"G16_TABLE_WINDOW": "22"},                                 # 2^15 buckets in each of the 43 class slices
+    {"G16_TABLE_WINDOW": "20", "G16_MTAB": "1"},               # one table per window: the layout registration falls
+    {"G16_TABLE_WINDOW": "22", "G16_MTAB": "1"},               # back to when two do not fit the HBM or 31-bit indices
+    {"G16_MSM_WINDOW": "20"},                                   # a plain MSM above the cost model's cap of 16
 ]
 
 
