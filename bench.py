@@ -18,9 +18,16 @@ once per circuit, files/zkey.nim:241-245) and the witness arrives per proof -- h
 circuit, so `value` includes the PCIe transfer.  The HBM-resident figure is reported next to it
 (`value_witness_in_hbm`).  The in-flight proofs of one GPU share ONE resident key.
 
-Prints ONE JSON line (rank 0).  Every run is gated on correctness: for every distinct witness the GPU proof must
-equal the CPU oracle's proof bit for bit and satisfy the pairing equation (tests/parity.py).  The oracle is used only
-for that check and for the `cpu_baseline` leg."""
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: setup, warm-up, the timed steps,
+--dump-outputs, the line (`roofline` and `cpu_baseline` are null in it).  The proofs of one witness must agree with
+each other throughout.
+
+  python bench.py --full ...
+
+adds everything else, after the timed steps: the other witness placement, the single-proof latency, the Poseidon-shaped
+circuit, the stand-alone MSM roofline, and the correctness gate -- for every distinct witness the GPU proof must equal
+the CPU oracle's proof bit for bit and satisfy the pairing equation (tests/parity.py) -- with the `cpu_baseline` leg.
+The oracle is used only for that check and that leg."""
 import argparse
 import json
 import os
@@ -58,7 +65,11 @@ def parse_args(argv=None):
                          "dump_outputs)")
     ap.add_argument("--log2n", type=int, default=20, help="domain size 2^log2n (constraints m = 2^log2n - 2)")
     ap.add_argument("--mode", choices=["replica", "shard"], default="replica")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything besides the headline: the other "
+                         "witness placement, single-proof latency, the Poseidon-shaped circuit, the stand-alone MSM "
+                         "roofline, the CPU-oracle correctness gate and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline leg")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="collective backend; gloo only for rehearsing the multi-process path on a one-GPU box "
                          "(all ranks then share device 0)")
@@ -72,8 +83,8 @@ def parse_args(argv=None):
                     help="shard mode: the three coset pipelines of the quotient on three different ranks + three "
                          "scatters of the slices (tasks), or recomputed by every rank (replicated)")
     ap.add_argument("--no-poseidon-shape", action="store_true",
-                    help="skip the extra key value_poseidon_shape (N = 1, replica mode: a second key, a Poseidon-shaped "
-                         "Merkle circuit of the same domain, ~15 s of setup + one more oracle proof)")
+                    help="--full: skip the extra key value_poseidon_shape (N = 1, replica mode: a second key, a "
+                         "Poseidon-shaped Merkle circuit of the same domain, ~15 s of setup + one more oracle proof)")
     ap.add_argument("--inject-failure", default="", metavar="RANK[:AFTER]",
                     help="test hook: that rank raises after AFTER proofs (dry run: before its first collective)")
     ap.add_argument("--dry-run", action="store_true",
@@ -108,11 +119,22 @@ def lib_sha16():
     return device_code_sha16()
 
 
+def extra_witness(m, w0):
+    """one more satisfying witness of the benchmark circuit (a worker process of build_inputs)"""
+    import gc
+    from nim_groth16_amd.synthetic import squaringChain
+    gc.disable()                       # see build_inputs
+    return squaringChain(m, seed=4, w0=w0)[1]
+
+
 def build_inputs(args, ctx, rank, world, dist):
-    """The circuit, its key and NWITNESS satisfying witnesses.  Rank 0 alone runs the ~25 s of Python big-integer
-    setup (and the fixed-base multiplications on its GPU); the other ranks of a multi-GPU launch load what it wrote
-    (one pickle in /dev/shm) instead of repeating it."""
+    """The circuit, its key and NWITNESS satisfying witnesses.  Rank 0 alone runs the Python big-integer setup (and the
+    fixed-base multiplications on its GPU); the other ranks of a multi-GPU launch load what it wrote (one pickle in
+    /dev/shm) instead of repeating it."""
+    import gc
+    import multiprocessing
     import pickle
+    from concurrent.futures import ProcessPoolExecutor
     from nim_groth16_amd.fake_setup import ToxicWaste, fakeCircuitSetup
     from nim_groth16_amd.synthetic import SplitMix64, squaringChain
     n = 1 << args.log2n
@@ -121,13 +143,22 @@ def build_inputs(args, ctx, rank, world, dist):
     import tempfile
     path = None
     if rank == 0:
-        r1cs, wit0 = squaringChain(m, seed=4)
+        # The setup allocates some 10^7 tuples and lists (constraints, coefficient records) and no reference cycles:
+        # the cyclic collector would scan them over and over and free nothing (it more than doubled the time the
+        # squaring chain takes to build).
+        gc.disable()
         # more satisfying witnesses of the SAME circuit: the chain constants k_i (which are what the key depends on)
-        # stay, the free input w_0 changes, and with it every wire
-        wits = [wit0] + [squaringChain(m, seed=4, w0=w0)[1] for w0 in (5, 7, 11, 13)[:NWITNESS - 1]]
-        rng = SplitMix64(5)
-        tox = ToxicWaste(*[rng.fr() for _ in range(5)])
-        zkey = fakeCircuitSetup(r1cs, tox, 1, ctx)           # scalar side on the host, every `y ** gen` on the GPU
+        # stay, the free input w_0 changes, and with it every wire.  Each is its own process's work (spawned: this one
+        # has a GPU open), done while this process builds the circuit and its key.
+        with ProcessPoolExecutor(NWITNESS - 1, mp_context=multiprocessing.get_context("spawn")) as pool:
+            more = [pool.submit(extra_witness, m, w0) for w0 in (5, 7, 11, 13)[:NWITNESS - 1]]
+            r1cs, wit0 = squaringChain(m, seed=4)
+            rng = SplitMix64(5)
+            tox = ToxicWaste(*[rng.fr() for _ in range(5)])
+            zkey = fakeCircuitSetup(r1cs, tox, 1, ctx)       # scalar side on the host, every `y ** gen` on the GPU
+            wits = [wit0] + [f.result() for f in more]
+        gc.freeze()                    # what the setup built lives to the end: out of every later collection's way
+        gc.enable()
         if world > 1:
             # a directory only this user can enter (mkdtemp: mode 0700, unpredictable name), its path handed to the
             # other ranks through the process group -- not a fixed name in world-writable /dev/shm
@@ -190,8 +221,8 @@ def main(argv=None):
         fail_fast(e, rank, world)
     if dist is not None:
         dist.destroy_process_group()
-    # The oracle gate and the CPU baseline run AFTER the process group is gone: 3 x ~14 s of CPU work on rank 0
-    # during which no other rank idles inside a collective.
+    # The oracle gate and the CPU baseline (--full) run AFTER the process group is gone: 3 x ~14 s of CPU work on
+    # rank 0 during which no other rank idles inside a collective.
     if rank == 0:
         finish_rank0(args, world, state)
 
@@ -341,6 +372,7 @@ def measure(args, rank, world, local, dist, coll_dev, state):
     # HIP events around the bucket-accumulation kernels run INSIDE the timed region, on this rank's first context
     # (recorded on the stream each kernel is launched on): the CONTENDED duration of the dominant kernel, reported
     # next to the uncontended one below.  (Events around all ~110 launches of a proof would cost ~3 % of throughput.)
+    # They are recorded in a plain run too, so that the timed region is the same with and without --full.
     ctx.profile(2 if rank == 0 else 0)
     ctx.profile_reset()
     runs = []
@@ -358,6 +390,13 @@ def measure(args, rank, world, local, dist, coll_dev, state):
     dt = sorted(runs)[len(runs) // 2]          # the median run
     proofs_done = args.steps * (1 if shard or world == 1 else world)
     value = proofs_done / dt
+    state.update(zkey=zkey, wits=wits, mask=mask, proofs=proofs, ctx=ctx, value=value, dt=dt, inflight=inflight,
+                 shard=shard, value_runs=[round(proofs_done / t, 4) for t in runs])
+    if not args.full:
+        if shard:
+            sp.close()
+        return
+    # ---- --full: everything besides the headline ------------------------------------------------------------------
     # the other witness placement, same protocol (barrier, K' steps, barrier, max over ranks), reported as an extra key
     k2 = max(inflight * NWITNESS, min(args.steps, 48))
     barrier()
@@ -387,8 +426,7 @@ def measure(args, rank, world, local, dist, coll_dev, state):
             state["poseidon_error"] = repr(e)
             errors.clear()
 
-    state.update(zkey=zkey, wits=wits, mask=mask, proofs=proofs, ctx=ctx, value=value, dt=dt, value_other=value_other,
-                 lat_ms=lat_ms, inflight=inflight, shard=shard, value_runs=[round(proofs_done / t, 4) for t in runs])
+    state.update(value_other=value_other, lat_ms=lat_ms)
     if rank != 0:
         return
     # ---- roofline of the dominant kernel (rank 0; nothing else runs on this GPU from here on) -------------------------
@@ -580,18 +618,16 @@ def static_inputs(args, shard, dom):
     return out
 
 
-def finish_rank0(args, world, st):
-    """correctness gate + CPU baseline (oracle = checker / baseline only), then the ONE JSON line"""
+def oracle_gate(args, world, st):
+    """--full: every distinct witness's proof (and the Poseidon-shaped one) against the CPU oracle, and the CPU baseline
+    from those oracle proofs (oracle = checker / baseline only) -> (cpu_baseline, Poseidon-shape result or None)"""
     from nim_groth16_amd import bn128 as F
     from tests.oracle_c import load_oracle
     from tests.parity import check_gpu_proof
     zkey, wits, mask, proofs, ctx = st["zkey"], st["wits"], st["mask"], st["proofs"], st["ctx"]
-    shard, inflight = st["shard"], st["inflight"]
     orc = load_oracle()
     cpu_s = []
     for k in range(NWITNESS):
-        if proofs[k] is None:
-            raise SystemExit(f"FAIL: witness {k} was never proved")
         try:
             cpu_s.append(check_gpu_proof(orc, zkey, wits[k], F.frSeqToMontBytes(wits[k]), mask.r, mask.s, proofs[k], ctx))
         except AssertionError as e:
@@ -611,6 +647,17 @@ def finish_rank0(args, world, st):
         cpu = {"value": round(1.0 / mean_s, 5), "unit": "proofs/s", "cores": orc.cores(), "kind": "port",
                "sample": f"{len(cpu_s)} full proofs (buildABC + 6 NTT + 4 G1 MSM + 1 G2 MSM), domain "
                          f"2^{args.log2n}, {mean_s:.1f}s each; C restatement, NOT constantine"}
+    return cpu, pos
+
+
+def finish_rank0(args, world, st):
+    """--full: the correctness gate + CPU baseline first; then the ONE JSON line"""
+    zkey, proofs = st["zkey"], st["proofs"]
+    shard, inflight = st["shard"], st["inflight"]
+    for k in range(NWITNESS):
+        if proofs[k] is None:
+            raise SystemExit(f"FAIL: witness {k} was never proved")
+    cpu, pos = oracle_gate(args, world, st) if args.full else (None, None)
     where = "host (pinned, .wtns layout)" if args.witness == "host" else "HBM"
     out = {
         "metric": "proofs/sec (BN254 Groth16, 2^20-constraint circuit)" if args.log2n == 20 else
@@ -634,14 +681,17 @@ def finish_rank0(args, world, st):
         "roofline": st.get("roof"), "cpu_baseline": cpu,
     }
     extra = st.get("extra", {})
-    other = "value_witness_in_hbm" if args.witness == "host" else "value_witness_from_host"
-    extra[other] = round(st["value_other"], 4)
+    if args.full:
+        other = "value_witness_in_hbm" if args.witness == "host" else "value_witness_from_host"
+        extra[other] = round(st["value_other"], 4)
     extra["value_runs"] = st["value_runs"]
     extra["value_is"] = f"median of {len(st['value_runs'])} timed regions of {args.steps} proofs each"
-    extra["proof_latency_ms_single_in_flight"] = round(st["lat_ms"], 3)
+    if args.full:
+        extra["proof_latency_ms_single_in_flight"] = round(st["lat_ms"], 3)
     extra["proofs_in_flight_per_gpu"] = inflight
     extra["keys_resident_per_gpu"] = 1
     extra["kernels_sha16"] = lib_sha16()
+    extra["full"] = args.full
     if pos is not None:
         extra["value_poseidon_shape"] = pos["line"]["value"]
         extra["poseidon_shape"] = pos["line"]

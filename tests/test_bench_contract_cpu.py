@@ -140,3 +140,29 @@ def test_accumulate_hot_loops_keep_their_instruction_budget():
     assert 4300 <= g2["v_mad_u64_u32"] <= 4400 and sum(c for op, c in g2.items() if op.startswith("v_")) <= 6700
     assert g2.get("s_nop", 0) <= 300, g2.get("s_nop")        # 280: chain pairs as asm statements (956 with pinned C++ pairs)
     assert not any(op.startswith("scratch_store") for op in g2), "the G2 accumulate loop spills"
+
+
+class _HostOnlyContext:
+    """stands in for the GPU context in build_inputs: the column dot products and every `y ** gen` as zero bytes"""
+
+    def spmv(self, wires, rows, values, lag, nwires):
+        return bytes(32 * nwires)
+
+    def fixed_base(self, group, scalars):
+        return bytes((64 if group == 1 else 128) * (len(scalars) // 32))
+
+
+def test_plain_run_is_the_default_and_its_inputs_are_the_squaring_chains():
+    """a plain run (no --full) builds the same circuit and witnesses as ever: the extra witnesses come from worker
+    processes, w_0 = 3, 5, 7 in that order, each the squaring chain's own"""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    from nim_groth16_amd.synthetic import squaringChain
+    assert bench.parse_args([]).full is False and bench.parse_args(["--full"]).full is True
+    args = bench.parse_args(["--log2n", "10"])
+    zkey, wits = bench.build_inputs(args, _HostOnlyContext(), 0, 1, None)
+    m = (1 << 10) - 2
+    assert len(wits) == bench.NWITNESS == 3
+    assert wits == [squaringChain(m, seed=4, w0=w0)[1] for w0 in (3, 5, 7)]
+    assert zkey.header.domainSize == 1 << 10 and zkey.header.nvars == m + 2

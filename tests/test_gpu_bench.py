@@ -1,7 +1,8 @@
-"""bench.py end to end on the GPU box at a small domain: the plain single-GPU command, and the plain
-`--gpus 2 --mode shard --backend gloo` command from a bare shell (two self-launched ranks sharing the box's one GPU,
-the real g16_prove_partials / g16_prove_combine on both, the exchange over gloo).  Both must pass bench.py's own gate
-(every distinct witness's proof bit-exact against the CPU oracle) and print ONE contract line."""
+"""bench.py end to end on the GPU box at a small domain: the single-GPU command, and the `--gpus 2 --mode shard
+--backend gloo` command from a bare shell (two self-launched ranks sharing the box's one GPU, the real
+g16_prove_partials / g16_prove_combine on both, the exchange over gloo).  With --full both must pass bench.py's own
+gate (every distinct witness's proof bit-exact against the CPU oracle) and print ONE contract line; a plain run must
+print the headline line without the extra legs and prove what the gated run proves."""
 import json
 import os
 import subprocess
@@ -40,7 +41,7 @@ def _run(*flags):
 @pytest.mark.timeout(1000)
 def test_bench_single_gpu_small_domain_contract_line(tmp_path):
     dump = tmp_path / "dump"
-    d = _run("--log2n", "14", "--steps", "12", "--warmup", "3", "--repeats", "11", "--dump-outputs", str(dump))
+    d = _run("--full", "--log2n", "14", "--steps", "12", "--warmup", "3", "--repeats", "11", "--dump-outputs", str(dump))
     for k in KEYS:
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 12 and d["scaling"] == "weak" and d["value"] > 0
@@ -67,10 +68,36 @@ def test_bench_single_gpu_small_domain_contract_line(tmp_path):
 
 
 @pytest.mark.timeout(1000)
+def test_bench_plain_run_prints_the_headline_alone_and_proves_what_the_full_run_checks(tmp_path):
+    """without --full: setup, warm-up, timed steps, --dump-outputs and the line -- no oracle gate, no extra legs; its
+    last proof is the one a --full run (gated against the CPU oracle) dumps for the same seeds"""
+    import numpy as np
+    flags = ("--log2n", "14", "--steps", "12", "--warmup", "3")
+    r = _sub(*flags, "--dump-outputs", str(tmp_path / "plain"))
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-6000:])
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    for k in KEYS:
+        assert k in d, k
+    assert d["full"] is False and d["roofline"] is None and d["cpu_baseline"] is None
+    assert d["unit"] == "proofs/s" and d["higher_is_better"] is True and d["steps"] == 12 and d["warmup"] == 3
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) < 0.01 * d["value"] and "squaring chain" in d["config"]["workload"]
+    for k in ("value_witness_in_hbm", "proof_latency_ms_single_in_flight", "value_poseidon_shape", "roofline_valu",
+              "roofline_gather", "overlap_efficiency"):
+        assert k not in d, k
+    assert "correctness gate" not in r.stderr
+    full = _run("--full", "--no-cpu-baseline", "--no-poseidon-shape", *flags, "--dump-outputs", str(tmp_path / "full"))
+    assert full["full"] is True and full["roofline"] is not None
+    for name in ("pi_a", "pi_b", "pi_c"):
+        assert np.array_equal(np.load(tmp_path / "plain" / f"{name}.npy"), np.load(tmp_path / "full" / f"{name}.npy")), name
+
+
+@pytest.mark.timeout(1000)
 @pytest.mark.parametrize("quotient", ["tasks", "replicated"])
 def test_bench_two_ranks_shard_mode_from_a_bare_shell(quotient):
-    d = _run("--gpus", "2", "--mode", "shard", "--backend", "gloo", "--log2n", "14", "--steps", "6", "--warmup", "3",
-             "--quotient", quotient)
+    d = _run("--full", "--gpus", "2", "--mode", "shard", "--backend", "gloo", "--log2n", "14", "--steps", "6",
+             "--warmup", "3", "--quotient", quotient)
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["mode"] == "shard" and d["value"] > 0
     assert f"quotient {quotient}" in d["config"]["workload"]
     assert d["cpu_baseline"] is None                       # reported at N = 1 only
@@ -78,7 +105,8 @@ def test_bench_two_ranks_shard_mode_from_a_bare_shell(quotient):
 
 @pytest.mark.timeout(1000)
 def test_bench_two_ranks_replica_mode_from_a_bare_shell():
-    d = _run("--gpus", "2", "--backend", "gloo", "--log2n", "13", "--steps", "6", "--warmup", "3", "--inflight", "2")
+    d = _run("--full", "--gpus", "2", "--backend", "gloo", "--log2n", "13", "--steps", "6", "--warmup", "3",
+             "--inflight", "2")
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["config"]["mode"] == "replica"
     assert abs(d["value"] - 2 * 1e3 / d["ms_per_step"]) < 0.01 * d["value"]     # whole-job aggregate over both ranks
     assert len(d["value_runs"]) == 1                        # by default --steps is the number of timed proofs

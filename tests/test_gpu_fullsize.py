@@ -131,5 +131,5 @@ def test_full_proof_2p14_jensgroth_bit_exact_vs_c_oracle(ctx, orc):
 
 def test_full_proof_2p20_bit_exact_vs_c_oracle(ctx, orc):
     """BASELINE config 3 (2^20-constraint circuit, full prove) inside the suite: bit-exact against the C oracle's
-    proof and accepted by both verifiers -- the same check that gates every bench.py run (tests/parity.py)."""
+    proof and accepted by both verifiers -- the same check that gates every bench.py --full run (tests/parity.py)."""
     _prove_and_check(ctx, orc, 20, True)

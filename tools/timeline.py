@@ -1,6 +1,6 @@
 """Per-stream timeline of the single-in-flight proofs of a bench.py run traced with rocprofv3 --kernel-trace:
-  rocprofv3 --kernel-trace --output-format csv -d gpurun_out/tl -o tl -- python3 bench.py --steps 6 --warmup 3 --no-cpu-baseline
-  python3 tools/timeline.py gpurun_out/tl/tl_kernel_trace.csv
+  rocprofv3 --kernel-trace --output-format csv -d tl -o tl -- python3 bench.py --full --steps 6 --warmup 3 --no-cpu-baseline
+  python3 tools/timeline.py tl/tl_kernel_trace.csv
 Prints, for the three latency-measurement proofs, when each stream starts / ends and its long kernels (ms from the
 proof's first GPU activity).
   python3 tools/timeline.py <trace.csv> --gap [min_us]
