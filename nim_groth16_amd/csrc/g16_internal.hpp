@@ -11,6 +11,7 @@
 #include <vector>
 
 
+#include "hip_owners.hpp"
 #include "msm_params.hpp"
 
 // Experiment knobs (G16_* environment variables), read ONCE per process -- at the first g16_ctx_create -- and never
@@ -63,18 +64,21 @@ inline uint32_t msm_red_chunk(const g16::MsmParams& P) {
 
 struct ProfEntry {
   const char* name;
-  hipEvent_t e0, e1;
+  Event e0, e1;
 };
 
+// Members release themselves when g16_ctx_destroy deletes the context, in reverse order of declaration; the order
+// among them does not matter because g16_ctx_destroy has made the device current and drained every stream first.
 struct g16_ctx {
   int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
+  hipStream_t stream = nullptr;   // the main stream: own_stream's, or the caller's (g16_ctx_set_stream; never destroyed here)
+  Stream own_stream;              // empty while the caller's stream is in use
   std::string err;
-  // growable device buffers
+  // growable device buffers (ensure())
   struct Buf {
-    void* p = nullptr;
+    DevMem<> mem;
     size_t bytes = 0;
+    void* p() const { return mem.get(); }
   };
   // MSM workspaces.  A "sort" is the bucket arrangement of ONE scalar vector (shared by every MSM that
   // uses those scalars: the witness feeds A1, B1, B2 and C1, prover.nim:282-302); a "lane" is one
@@ -92,13 +96,14 @@ struct g16_ctx {
     uint2* xseg = nullptr;
   };
   struct MsmLane {
-    hipStream_t stream = nullptr;
-    hipEvent_t done = nullptr;
+    Stream stream;
+    Event done;
     Buf acc;
   };
   MsmSort sort[4];   // 0: witness (all pairs)  1: H scalars  2: witness, A1's live pairs  3: witness, B1/B2's live pairs
   MsmLane lane[5];
-  hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_q = nullptr, ev_b2 = nullptr, ev_c = nullptr, ev_g2 = nullptr;
+  enum { EV_A, EV_B, EV_Q, EV_B2, EV_C, EV_G2, EV_COUNT };
+  Event ev[EV_COUNT];   // the cross-stream edges of a proof (prover.hip)
   Buf stage_s;   // staged scalars (host-pointer API)
   Buf stage_p;   // staged points
   Buf stage_p29; // the same points as reduced-radix entries (one-shot MSMs; registered sets keep their own tables)
@@ -110,7 +115,7 @@ struct g16_ctx {
   Buf prove;     // per-proof scalars: witness, Az|Bz|Cz, qs
   Buf fb_table[2];  // fixed-base tables of gen1 / gen2
   bool fb_ready[2] = {false, false};
-  unsigned long long* clk_buf = nullptr;   // {sum d_memtime, sum d_memrealtime} of the accumulate kernels (g16_profile_clock)
+  DevMem<unsigned long long> clk_buf;   // {sum d_memtime, sum d_memrealtime} of the accumulate kernels (g16_profile_clock)
   const void* shard_begun = nullptr;   // key of a g16_prove_partials_begin that still awaits its _end
   uint32_t tw_log2n = 0xffffffffu;
   uint32_t coset_log2n[2] = {0xffffffffu, 0xffffffffu};
@@ -118,16 +123,22 @@ struct g16_ctx {
   bool profiling = false;
   bool prof_accum_only = false;   // g16_profile_enable(ctx, 2): only the bucket-accumulation kernels
   std::vector<ProfEntry> prof;
-  std::vector<hipEvent_t> free_events;
+  std::vector<Event> free_events;
 };
 
-#define HIPCHK(ctx, call)                                                                      \
-  do {                                                                                         \
-    hipError_t e__ = (call);                                                                   \
-    if (e__ != hipSuccess) {                                                                   \
-      (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e__);                         \
-      return e__ == hipErrorOutOfMemory ? G16_ENOMEM : G16_EHIP;                               \
-    }                                                                                          \
+// The one way a HIP call fails in the host layer: "<call>: <reason>" goes to the error slot the caller will ask
+// (g16_last_error, or through it g16_group_last_error / g16_prover_last_error), out-of-memory maps to G16_ENOMEM and
+// everything else to G16_EHIP, and HIP's sticky last error is cleared so that it does not surface in the caller's next,
+// unrelated call.
+inline int32_t g16_hip_check(std::string& err, const char* call, hipError_t e) {
+  if (e == hipSuccess) return G16_OK;
+  err = std::string(call) + ": " + hipGetErrorString(e);
+  (void)hipGetLastError();
+  return e == hipErrorOutOfMemory ? G16_ENOMEM : G16_EHIP;
+}
+#define HIPCHK(ctx, call)                                                          \
+  do {                                                                             \
+    if (int32_t hiprc__ = g16_hip_check((ctx)->err, #call, (call))) return hiprc__; \
   } while (0)
 
 // waits for everything this context has queued: the main stream AND the five MSM lane streams.  Called before a
@@ -136,8 +147,14 @@ struct g16_ctx {
 inline void ctx_quiesce(g16_ctx* ctx) {
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   for (auto& l : ctx->lane)
-    if (l.stream) (void)hipStreamSynchronize(l.stream);
+    if (l.stream) (void)hipStreamSynchronize(l.stream.get());
 }
+// for the temporaries of one call: declared AFTER the owners of the call's scratch buffers, it drains the stream that
+// uses them on every exit, before they are freed
+struct SyncOnExit {
+  hipStream_t stream;
+  ~SyncOnExit() { (void)hipStreamSynchronize(stream); }
+};
 
 // Entry protocol of every context-taking C-ABI function.
 //  * The calling thread's current HIP device becomes the context's: allocations, event creation and launches bind to
@@ -167,14 +184,13 @@ inline int32_t ctx_enter(g16_ctx* ctx, bool keep_shard = false) {
 inline int32_t ensure(g16_ctx* ctx, g16_ctx::Buf& b, size_t bytes) {
   if (b.bytes >= bytes) return G16_OK;
   HIPCHK(ctx, hipSetDevice(ctx->device));   // hipMalloc binds to the calling thread's current device
-  if (b.p) {
+  if (b.mem) {
     ctx_quiesce(ctx);
-    HIPCHK(ctx, hipFree(b.p));
-    b.p = nullptr;
+    b.mem.reset();
     b.bytes = 0;
   }
   size_t want = bytes + bytes / 8 + 4096;
-  HIPCHK(ctx, hipMalloc(&b.p, want));
+  HIPCHK(ctx, dev_alloc(b.mem, want));
   b.bytes = want;
   return G16_OK;
 }
@@ -190,22 +206,22 @@ struct ProfScope {
         st(stream ? stream : c->stream) {
     if (!on) return;
     e.name = name;
-    auto get = [&](hipEvent_t& ev) {
+    auto get = [&](Event& ev) {
       if (!ctx->free_events.empty()) {
-        ev = ctx->free_events.back();
+        ev = std::move(ctx->free_events.back());
         ctx->free_events.pop_back();
       } else {
-        (void)hipEventCreate(&ev);
+        (void)event_create(ev, hipEventDefault);
       }
     };
     get(e.e0);
     get(e.e1);
-    (void)hipEventRecord(e.e0, st);
+    (void)hipEventRecord(e.e0.get(), st);
   }
   ~ProfScope() {
     if (!on) return;
-    (void)hipEventRecord(e.e1, st);
-    ctx->prof.push_back(e);
+    (void)hipEventRecord(e.e1.get(), st);
+    ctx->prof.push_back(std::move(e));
   }
 };
 #define KLAUNCH_ON(ctx, stream_, name, kernel, grid, block, shmem, ...)                        \
@@ -246,7 +262,7 @@ struct g16_msm_run {
 };
 int32_t g16_msm_batch(g16_ctx* ctx, hipStream_t stream, int group, const g16_msm_run* runs, int n_accum, int n_tail,
                       hipEvent_t after_heavy);
-inline const void* g16_msm_partial_ptr(const g16_ctx::Buf& acc) { return acc.p; }
+inline const void* g16_msm_partial_ptr(const g16_ctx::Buf& acc) { return acc.p(); }
 int32_t g16_msm_reduce_g1(g16_ctx* ctx, hipStream_t stream, g16_ctx::Buf& acc, const g16_ctx::MsmSort& sort,
                           const void* d_points, void* d_out_aff, void* d_out_acc);
 int32_t g16_msm_reduce_g2(g16_ctx* ctx, hipStream_t stream, g16_ctx::Buf& acc, const g16_ctx::MsmSort& sort,
@@ -286,8 +302,8 @@ struct g16_points {
   uint32_t c = 0, nwin = 0;
   uint32_t mtab = 1;         // multiplier tables per window: 1, or 2 = {1, 2} with the class bucket set (msm.cuh)
   uint32_t cfg() const { return c | (mtab << 8); }   // the `table_cfg` of g16_msm_sort / g16_msm_device_*
-  void* d_tables = nullptr;  // mtab * nwin * n affine points: [m][w][i] = 2^(c w + m) P_i
-  uint32_t* d_live = nullptr;   // bitmap: bit i set <=> point i is not (0,0); ceil(n/32) words
+  DevMem<> d_tables;         // mtab * nwin * n affine points: [m][w][i] = 2^(c w + m) P_i
+  DevMem<uint32_t> d_live;      // bitmap: bit i set <=> point i is not (0,0); ceil(n/32) words
   size_t n_inf = 0;             // points at infinity in the set
 };
 // *d_n_inf (device u32, zeroed by the caller) += number of (0,0) points; bitmap: ceil(n/32) words

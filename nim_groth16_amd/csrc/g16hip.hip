@@ -51,15 +51,18 @@ const G16Env& g16_env() {
 // every XCD and the five MSM lanes over the remaining 32 - k: the front of a proof then owns CUs instead of waiting for
 // accumulate waves of other streams to drain.  CU-mask bit i is CU (i / 8) of XCD (i % 8) on this part (the mask is dealt
 // round robin over the XCCs).  Such streams have no priority.  Measured: profiles/r05_ab_cu_split.txt.
-static hipError_t stream_create(hipStream_t* st, int prio_index, bool front) {
+static hipError_t ctx_stream_create(Stream& out, int prio_index, bool front) {
   const int k = g16_env().cu_split;
-  if (k <= 0) return hipStreamCreateWithPriority(st, hipStreamNonBlocking, g16_stream_priority(prio_index));
   uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   for (int bit = 0; bit < 256; ++bit) {
     const bool in_front = bit / 8 < k;
     if (in_front == front) mask[bit / 32] |= 1u << (bit % 32);
   }
-  return hipExtStreamCreateWithCUMask(st, 8, mask);
+  hipStream_t st = nullptr;
+  const hipError_t e = k <= 0 ? hipStreamCreateWithPriority(&st, hipStreamNonBlocking, g16_stream_priority(prio_index))
+                              : hipExtStreamCreateWithCUMask(&st, 8, mask);
+  out.reset(st);
+  return e;
 }
 
 // ---- context ------------------------------------------------------------------------------------
@@ -71,19 +74,13 @@ extern "C" int32_t g16_ctx_create(int32_t device, g16_ctx** out) {
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ENODEV;
   if (device < 0 || device >= ndev) return G16_EINVAL;
   if (hipSetDevice(device) != hipSuccess) return G16_ENODEV;
-  g16_ctx* ctx = new (std::nothrow) g16_ctx();
+  Building<g16_ctx, g16_ctx_destroy> ctx(new (std::nothrow) g16_ctx());
   if (!ctx) return G16_ENOMEM;
   ctx->device = device;
-  if (stream_create(&ctx->stream, 5, true) != hipSuccess) {
-    delete ctx;
-    return G16_ENODEV;
-  }
-  ctx->own_stream = true;
-  if (g16_lanes_init(ctx) != G16_OK) {
-    g16_ctx_destroy(ctx);
-    return G16_ENODEV;
-  }
-  *out = ctx;
+  if (ctx_stream_create(ctx->own_stream, 5, true) != hipSuccess) return G16_ENODEV;
+  ctx->stream = ctx->own_stream.get();
+  if (g16_lanes_init(ctx.get()) != G16_OK) return G16_ENODEV;
+  *out = ctx.release();
   return G16_OK;
 }
 
@@ -106,46 +103,17 @@ int g16_stream_priority(int index) {
 int32_t g16_lanes_init(g16_ctx* ctx) {
   for (int i = 0; i < 5; ++i) {
     auto& l = ctx->lane[i];
-    if (stream_create(&l.stream, i, false) != hipSuccess) return G16_EHIP;
-    if (hipEventCreateWithFlags(&l.done, hipEventDisableTiming) != hipSuccess) return G16_EHIP;
+    HIPCHK(ctx, ctx_stream_create(l.stream, i, false));
+    HIPCHK(ctx, event_create(l.done));
   }
-  if (hipEventCreateWithFlags(&ctx->ev_a, hipEventDisableTiming) != hipSuccess) return G16_EHIP;
-  if (hipEventCreateWithFlags(&ctx->ev_b, hipEventDisableTiming) != hipSuccess) return G16_EHIP;
-  if (hipEventCreateWithFlags(&ctx->ev_q, hipEventDisableTiming) != hipSuccess) return G16_EHIP;
-  if (hipEventCreateWithFlags(&ctx->ev_b2, hipEventDisableTiming) != hipSuccess) return G16_EHIP;
-  if (hipEventCreateWithFlags(&ctx->ev_c, hipEventDisableTiming) != hipSuccess) return G16_EHIP;
-  if (hipEventCreateWithFlags(&ctx->ev_g2, hipEventDisableTiming) != hipSuccess) return G16_EHIP;
+  for (Event& e : ctx->ev) HIPCHK(ctx, event_create(e));
   return G16_OK;
 }
 
 extern "C" void g16_ctx_destroy(g16_ctx* ctx) {
   if (!ctx) return;
-  (void)hipSetDevice(ctx->device);
-  ctx_quiesce(ctx);
-  for (auto& l : ctx->lane) {
-    if (l.stream) (void)hipStreamDestroy(l.stream);
-    if (l.done) (void)hipEventDestroy(l.done);
-    if (l.acc.p) (void)hipFree(l.acc.p);
-  }
-  for (auto& srt : ctx->sort)
-    if (srt.buf.p) (void)hipFree(srt.buf.p);
-  if (ctx->ev_a) (void)hipEventDestroy(ctx->ev_a);
-  if (ctx->ev_b) (void)hipEventDestroy(ctx->ev_b);
-  if (ctx->ev_q) (void)hipEventDestroy(ctx->ev_q);
-  if (ctx->ev_b2) (void)hipEventDestroy(ctx->ev_b2);
-  if (ctx->ev_c) (void)hipEventDestroy(ctx->ev_c);
-  if (ctx->ev_g2) (void)hipEventDestroy(ctx->ev_g2);
-  for (g16_ctx::Buf* b : {&ctx->stage_s, &ctx->stage_p, &ctx->stage_p29, &ctx->stage_o, &ctx->ntt_tw, &ctx->ntt_tmp,
-                          &ctx->coset[0], &ctx->coset[1], &ctx->quot, &ctx->prove, &ctx->fb_table[0],
-                          &ctx->fb_table[1]})
-    if (b->p) (void)hipFree(b->p);
-  for (auto& e : ctx->prof) {
-    (void)hipEventDestroy(e.e0);
-    (void)hipEventDestroy(e.e1);
-  }
-  for (auto& e : ctx->free_events) (void)hipEventDestroy(e);
-  if (ctx->clk_buf) (void)hipFree(ctx->clk_buf);
-  if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
+  (void)hipSetDevice(ctx->device);   // the context's device is current while its members are released
+  ctx_quiesce(ctx);                  // no stream still reads a buffer that is about to go
   delete ctx;
 }
 
@@ -155,16 +123,9 @@ extern "C" int32_t g16_ctx_set_stream(g16_ctx* ctx, void* hip_stream) {
   if (!ctx) return G16_EINVAL;
   CTX_ENTER(ctx);
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->own_stream) {
-    (void)hipStreamDestroy(ctx->stream);
-    ctx->own_stream = false;
-  }
-  if (hip_stream) {
-    ctx->stream = (hipStream_t)hip_stream;
-  } else {
-    HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
-    ctx->own_stream = true;
-  }
+  ctx->own_stream.reset();   // (a caller's stream is not ours to destroy)
+  if (!hip_stream) HIPCHK(ctx, stream_create(ctx->own_stream));
+  ctx->stream = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream.get();
   return G16_OK;
 }
 
@@ -189,8 +150,8 @@ extern "C" int32_t g16_profile_enable(g16_ctx* ctx, int32_t on) {
   if (!ctx) return G16_EINVAL;
   CTX_ENTER_KEEP(ctx);
   if (on && !ctx->clk_buf) {
-    HIPCHK(ctx, hipMalloc((void**)&ctx->clk_buf, 16));
-    HIPCHK(ctx, hipMemset(ctx->clk_buf, 0, 16));
+    HIPCHK(ctx, dev_alloc(ctx->clk_buf, 16));
+    HIPCHK(ctx, hipMemset(ctx->clk_buf.get(), 0, 16));
   }
   ctx->profiling = on != 0;
   ctx->prof_accum_only = on == 2;
@@ -201,8 +162,8 @@ extern "C" int32_t g16_profile_reset(g16_ctx* ctx) {
   CTX_ENTER_KEEP(ctx);
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   for (auto& e : ctx->prof) {
-    ctx->free_events.push_back(e.e0);
-    ctx->free_events.push_back(e.e1);
+    ctx->free_events.push_back(std::move(e.e0));
+    ctx->free_events.push_back(std::move(e.e1));
   }
   ctx->prof.clear();
   return G16_OK;
@@ -214,7 +175,7 @@ extern "C" int32_t g16_profile_report(g16_ctx* ctx, char* buf, size_t buflen) {
   std::map<std::string, std::pair<int, double>> agg;
   for (auto& e : ctx->prof) {
     float ms = 0;
-    if (hipEventElapsedTime(&ms, e.e0, e.e1) == hipSuccess) {
+    if (hipEventElapsedTime(&ms, e.e0.get(), e.e1.get()) == hipSuccess) {
       auto& a = agg[e.name];
       a.first++;
       a.second += ms;
@@ -248,8 +209,8 @@ extern "C" int32_t g16_profile_clock(g16_ctx* ctx, double* ghz) {
   if (!ctx->clk_buf) return G16_OK;
   ctx_quiesce(ctx);
   unsigned long long h[2] = {0, 0};
-  HIPCHK(ctx, hipMemcpy(h, ctx->clk_buf, 16, hipMemcpyDeviceToHost));
-  HIPCHK(ctx, hipMemset(ctx->clk_buf, 0, 16));
+  HIPCHK(ctx, hipMemcpy(h, ctx->clk_buf.get(), 16, hipMemcpyDeviceToHost));
+  HIPCHK(ctx, hipMemset(ctx->clk_buf.get(), 0, 16));
   if (h[1]) *ghz = (double)h[0] / (double)h[1] * 0.1;
   return G16_OK;
 }
@@ -278,19 +239,19 @@ static int32_t msm_entry(g16_ctx* ctx, const void* scalars, uint32_t flags, cons
   if (!on_device) {
     if ((rc = ensure(ctx, ctx->stage_s, n * 32))) return rc;
     if ((rc = ensure(ctx, ctx->stage_p, n * sizeof(typename C::Aff)))) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->stage_s.p, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->stage_p.p, points, n * sizeof(typename C::Aff), hipMemcpyHostToDevice,
+    HIPCHK(ctx, hipMemcpyAsync(ctx->stage_s.p(), scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->stage_p.p(), points, n * sizeof(typename C::Aff), hipMemcpyHostToDevice,
                                ctx->stream));
-    d_s = ctx->stage_s.p;
-    d_p = ctx->stage_p.p;
+    d_s = ctx->stage_s.p();
+    d_p = ctx->stage_p.p();
   }
   if ((rc = ensure(ctx, ctx->stage_o, 512))) return rc;
-  auto* d_aff = partial ? nullptr : (typename C::Aff*)ctx->stage_o.p;
-  auto* d_acc = partial ? (typename C::Acc*)ctx->stage_o.p : nullptr;
+  auto* d_aff = partial ? nullptr : (typename C::Aff*)ctx->stage_o.p();
+  auto* d_acc = partial ? (typename C::Acc*)ctx->stage_o.p() : nullptr;
   rc = sizeof(typename C::Aff) == 64 ? g16_msm_device_g1(ctx, d_s, flags, d_p, n, d_aff, d_acc, 0)
                                      : g16_msm_device_g2(ctx, d_s, flags, d_p, n, d_aff, d_acc, 0);
   if (rc) return rc;
-  HIPCHK(ctx, hipMemcpyAsync(out, ctx->stage_o.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(out, ctx->stage_o.p(), out_bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return G16_OK;
 }
@@ -305,7 +266,7 @@ static int32_t points_register(g16_ctx* ctx, int group, const void* points, size
   }
   *out = nullptr;
   CTX_ENTER(ctx);
-  g16_points* h = new (std::nothrow) g16_points();
+  Building<g16_points, g16_points_release> h(new (std::nothrow) g16_points());
   if (!h) return G16_ENOMEM;
   h->device = ctx->device;
   h->group = group;
@@ -319,55 +280,40 @@ static int32_t points_register(g16_ctx* ctx, int group, const void* points, size
   // and the plain bucket set (the rounds 1-3 layout) instead of failing.
   if ((size_t)h->mtab * h->nwin * n >= (size_t(1) << 31)) h->mtab = 1;
   if ((size_t)h->mtab * h->nwin * n >= (size_t(1) << 31)) {
-    delete h;
     ctx->err = "point set too large for 31-bit table indices";
     return G16_EINVAL;
   }
   if (n) {
-    hipError_t e = hipMalloc(&h->d_tables, (size_t)h->mtab * h->nwin * n * psz);   // packed reduced-radix entries: 64 / 128 B
-    if (e != hipSuccess && h->mtab == 2) {
+    // packed reduced-radix entries: 64 / 128 B
+    if (h->mtab == 2 && dev_alloc(h->d_tables, 2 * (size_t)h->nwin * n * psz) != hipSuccess) {
       (void)hipGetLastError();
       h->mtab = 1;
-      e = hipMalloc(&h->d_tables, (size_t)h->nwin * n * psz);
     }
-    if (e != hipSuccess) {
-      delete h;
-      ctx->err = "hipMalloc(tables) failed";
-      return G16_ENOMEM;
-    }
+    if (!h->d_tables) HIPCHK(ctx, dev_alloc(h->d_tables, (size_t)h->nwin * n * psz));
     const void* d_src = points;
-    int32_t rc = G16_OK;
+    int32_t rc;
     if (!on_device) {
-      rc = ensure(ctx, ctx->stage_p, n * psz);
-      if (!rc && hipMemcpyAsync(ctx->stage_p.p, points, n * psz, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-        rc = G16_EHIP;
-      d_src = ctx->stage_p.p;
+      if ((rc = ensure(ctx, ctx->stage_p, n * psz))) return rc;
+      HIPCHK(ctx, hipMemcpyAsync(ctx->stage_p.p(), points, n * psz, hipMemcpyHostToDevice, ctx->stream));
+      d_src = ctx->stage_p.p();
     }
-    if (!rc)
-      rc = group == 1 ? g16_precompute_device_g1(ctx, d_src, n, h->c, h->mtab, h->d_tables)
-                      : g16_precompute_device_g2(ctx, d_src, n, h->c, h->mtab, h->d_tables);
+    rc = group == 1 ? g16_precompute_device_g1(ctx, d_src, n, h->c, h->mtab, h->d_tables.get())
+                    : g16_precompute_device_g2(ctx, d_src, n, h->c, h->mtab, h->d_tables.get());
+    if (rc) return rc;
     // which points are (0,0): snarkjs keys hold the point at infinity for every wire absent from a matrix
     uint32_t n_inf = 0;
-    if (!rc && hipMalloc((void**)&h->d_live, ((n + 31) / 32 + 1) * 4) != hipSuccess) rc = G16_ENOMEM;
-    if (!rc) rc = ensure(ctx, ctx->stage_o, 2048);
-    if (!rc) {
-      uint32_t* d_cnt = (uint32_t*)ctx->stage_o.p;
-      if (hipMemsetAsync(d_cnt, 0, 4, ctx->stream) != hipSuccess) rc = G16_EHIP;
-      if (!rc) rc = group == 1 ? g16_live_bitmap_device_g1(ctx, d_src, n, h->d_live, d_cnt)
-                               : g16_live_bitmap_device_g2(ctx, d_src, n, h->d_live, d_cnt);
-      if (!rc && hipMemcpyAsync(&n_inf, d_cnt, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = G16_EHIP;
-    }
-    if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = G16_EHIP;
+    HIPCHK(ctx, dev_alloc(h->d_live, ((n + 31) / 32 + 1) * 4));
+    if ((rc = ensure(ctx, ctx->stage_o, 2048))) return rc;
+    uint32_t* d_cnt = (uint32_t*)ctx->stage_o.p();
+    HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, 4, ctx->stream));
+    rc = group == 1 ? g16_live_bitmap_device_g1(ctx, d_src, n, h->d_live.get(), d_cnt)
+                    : g16_live_bitmap_device_g2(ctx, d_src, n, h->d_live.get(), d_cnt);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(&n_inf, d_cnt, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     h->n_inf = n_inf;
-    if (rc) {
-      if (h->d_live) (void)hipFree(h->d_live);
-      (void)hipFree(h->d_tables);
-      delete h;
-      if (ctx->err.empty()) ctx->err = "point registration failed";
-      return rc;
-    }
   }
-  *out = h;
+  *out = h.release();
   return G16_OK;
 }
 extern "C" int32_t g16_points_register_g1(g16_ctx* ctx, const void* points, size_t n, g16_points** out) {
@@ -389,14 +335,12 @@ extern "C" void g16_points_release(g16_points* h) {
     // registered them may already be gone: wait for the whole device, never for one context's stream
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
-    (void)hipFree(h->d_tables);
-    if (h->d_live) (void)hipFree(h->d_live);
   }
   delete h;
 }
 extern "C" size_t g16_points_inf_count(const g16_points* h) { return h ? h->n_inf : 0; }
 const uint32_t* g16_points_live_if_sparse(const g16_points* p) {
-  return p && p->d_live && p->n && p->n_inf * 100 >= (size_t)g16_env().inf_compact_pct * p->n && p->n_inf ? p->d_live
+  return p && p->d_live && p->n && p->n_inf * 100 >= (size_t)g16_env().inf_compact_pct * p->n && p->n_inf ? p->d_live.get()
                                                                                                         : nullptr;
 }
 extern "C" size_t g16_points_count(const g16_points* h) { return h ? h->n : 0; }
@@ -420,11 +364,11 @@ static int32_t points_check(g16_ctx* ctx, int group, const void* points, size_t 
   int32_t rc;
   if ((rc = ensure(ctx, ctx->stage_p, n * psz + psz))) return rc;
   if ((rc = ensure(ctx, ctx->stage_o, 2048))) return rc;
-  uint32_t* d_bad = (uint32_t*)ctx->stage_o.p;
+  uint32_t* d_bad = (uint32_t*)ctx->stage_o.p();
   HIPCHK(ctx, hipMemsetAsync(d_bad, 0xff, 4, ctx->stream));
-  if (n) HIPCHK(ctx, hipMemcpyAsync(ctx->stage_p.p, points, n * psz, hipMemcpyHostToDevice, ctx->stream));
-  rc = group == 1 ? g16_on_curve_device_g1(ctx, ctx->stage_p.p, n, d_bad)
-                  : g16_on_curve_device_g2(ctx, ctx->stage_p.p, n, d_bad);
+  if (n) HIPCHK(ctx, hipMemcpyAsync(ctx->stage_p.p(), points, n * psz, hipMemcpyHostToDevice, ctx->stream));
+  rc = group == 1 ? g16_on_curve_device_g1(ctx, ctx->stage_p.p(), n, d_bad)
+                  : g16_on_curve_device_g2(ctx, ctx->stage_p.p(), n, d_bad);
   if (rc) return rc;
   uint32_t bad = 0;
   HIPCHK(ctx, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -453,13 +397,13 @@ static int32_t fixed_base(g16_ctx* ctx, int group, const void* scalars, uint32_t
   if ((rc = ensure(ctx, tb, 32 * 255 * psz))) return rc;
   if ((rc = ensure(ctx, ctx->stage_s, n * 32 + 32))) return rc;
   if ((rc = ensure(ctx, ctx->stage_p, n * psz + psz))) return rc;
-  if (n) HIPCHK(ctx, hipMemcpyAsync(ctx->stage_s.p, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
+  if (n) HIPCHK(ctx, hipMemcpyAsync(ctx->stage_s.p(), scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
   const uint32_t mont = (flags & G16_SCALARS_MONT) ? 1u : 0u;
-  rc = group == 1 ? g16_fixed_base_device_g1(ctx, tb.p, ctx->fb_ready[0], ctx->stage_s.p, mont, n, ctx->stage_p.p)
-                  : g16_fixed_base_device_g2(ctx, tb.p, ctx->fb_ready[1], ctx->stage_s.p, mont, n, ctx->stage_p.p);
+  rc = group == 1 ? g16_fixed_base_device_g1(ctx, tb.p(), ctx->fb_ready[0], ctx->stage_s.p(), mont, n, ctx->stage_p.p())
+                  : g16_fixed_base_device_g2(ctx, tb.p(), ctx->fb_ready[1], ctx->stage_s.p(), mont, n, ctx->stage_p.p());
   if (rc) return rc;
   ctx->fb_ready[group - 1] = true;
-  if (n) HIPCHK(ctx, hipMemcpyAsync(out, ctx->stage_p.p, n * psz, hipMemcpyDeviceToHost, ctx->stream));
+  if (n) HIPCHK(ctx, hipMemcpyAsync(out, ctx->stage_p.p(), n * psz, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return G16_OK;
 }
@@ -491,17 +435,17 @@ extern "C" int32_t g16_msm_points(g16_ctx* ctx, const g16_points* pts, const voi
   const void* d_s = scalars;
   if (!(flags & G16_SCALARS_DEVICE)) {
     if ((rc = ensure(ctx, ctx->stage_s, n * 32))) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->stage_s.p, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
-    d_s = ctx->stage_s.p;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->stage_s.p(), scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
+    d_s = ctx->stage_s.p();
   }
   if ((rc = ensure(ctx, ctx->stage_o, 512))) return rc;
-  void* d_aff = partial ? nullptr : ctx->stage_o.p;
-  void* d_acc = partial ? ctx->stage_o.p : nullptr;
+  void* d_aff = partial ? nullptr : ctx->stage_o.p();
+  void* d_acc = partial ? ctx->stage_o.p() : nullptr;
   const uint32_t* live = g16_points_live_if_sparse(pts);
-  rc = pts->group == 1 ? g16_msm_device_g1(ctx, d_s, flags, pts->d_tables, n, d_aff, d_acc, pts->cfg(), live)
-                       : g16_msm_device_g2(ctx, d_s, flags, pts->d_tables, n, d_aff, d_acc, pts->cfg(), live);
+  rc = pts->group == 1 ? g16_msm_device_g1(ctx, d_s, flags, pts->d_tables.get(), n, d_aff, d_acc, pts->cfg(), live)
+                       : g16_msm_device_g2(ctx, d_s, flags, pts->d_tables.get(), n, d_aff, d_acc, pts->cfg(), live);
   if (rc) return rc;
-  HIPCHK(ctx, hipMemcpyAsync(out, ctx->stage_o.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(out, ctx->stage_o.p(), out_bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return G16_OK;
 }
@@ -539,11 +483,11 @@ static int32_t sum_partials(g16_ctx* ctx, const void* xyzz, size_t count, void* 
   size_t bytes = count * sizeof(typename C::Acc);
   if ((rc = ensure(ctx, ctx->stage_p, bytes + 256))) return rc;
   if ((rc = ensure(ctx, ctx->stage_o, 512))) return rc;
-  if (count) HIPCHK(ctx, hipMemcpyAsync(ctx->stage_p.p, xyzz, bytes, hipMemcpyHostToDevice, ctx->stream));
-  rc = sizeof(typename C::Aff) == 64 ? g16_sum_partials_device_g1(ctx, ctx->stage_p.p, (uint32_t)count, ctx->stage_o.p)
-                                     : g16_sum_partials_device_g2(ctx, ctx->stage_p.p, (uint32_t)count, ctx->stage_o.p);
+  if (count) HIPCHK(ctx, hipMemcpyAsync(ctx->stage_p.p(), xyzz, bytes, hipMemcpyHostToDevice, ctx->stream));
+  rc = sizeof(typename C::Aff) == 64 ? g16_sum_partials_device_g1(ctx, ctx->stage_p.p(), (uint32_t)count, ctx->stage_o.p())
+                                     : g16_sum_partials_device_g2(ctx, ctx->stage_p.p(), (uint32_t)count, ctx->stage_o.p());
   if (rc) return rc;
-  HIPCHK(ctx, hipMemcpyAsync(out, ctx->stage_o.p, sizeof(typename C::Aff), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(out, ctx->stage_o.p(), sizeof(typename C::Aff), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return G16_OK;
 }
@@ -576,9 +520,9 @@ extern "C" int32_t g16_ntt_fr(g16_ctx* ctx, const void* src, void* dst, uint32_t
   int32_t rc;
   if ((rc = ensure(ctx, ctx->stage_s, bytes))) return rc;
   if ((rc = ensure(ctx, ctx->stage_p, bytes))) return rc;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->stage_s.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-  if ((rc = g16_ntt_device(ctx, ctx->stage_s.p, ctx->stage_p.p, log2n, inverse ? 1 : 0))) return rc;
-  HIPCHK(ctx, hipMemcpyAsync(dst, ctx->stage_p.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->stage_s.p(), src, bytes, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = g16_ntt_device(ctx, ctx->stage_s.p(), ctx->stage_p.p(), log2n, inverse ? 1 : 0))) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(dst, ctx->stage_p.p(), bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return G16_OK;
 }
@@ -630,39 +574,37 @@ extern "C" int32_t g16_selftest(g16_ctx* ctx) {
   static_assert(sizeof(u256) == 32 && sizeof(g1_aff) == 64 && sizeof(g2_aff) == 128, "layout");
   CTX_ENTER(ctx);
   int32_t rc;
-  g16_ctx::Buf st;   // own scratch: the MSM / NTT below use the context's staging buffers
+  g16_ctx::Buf st;                // own scratch: the MSM / NTT below use the context's staging buffers
+  SyncOnExit sync{ctx->stream};   // ... freed on every exit, behind the stream that uses it
   if ((rc = ensure(ctx, st, 4096))) return rc;
-  uint32_t* d = (uint32_t*)st.p;
+  uint32_t* d = (uint32_t*)st.p();
   hipLaunchKernelGGL(selftest_kernel, dim3(1), dim3(64), 0, ctx->stream, d);
   uint32_t ok = 0;
   struct {
     g1_aff msm, want;
     u256 ntt[8], one;
   } h;
-  auto finish = [&](int32_t code, const char* msg) {
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(st.p);
-    if (code) ctx->err = msg;
-    return code;
-  };
   // known-answer MSM through the whole Pippenger pipeline (1*G + 2*(2G) + 3*G = 8G) and NTT (e_0 -> all ones)
   const g1_aff* d_pts = reinterpret_cast<const g1_aff*>(d + 16);
   const u256* d_sc = reinterpret_cast<const u256*>(d + 16 + 64);
   u256* d_nt = reinterpret_cast<u256*>(d + 16 + 64 + 24);
   g1_aff* d_res = reinterpret_cast<g1_aff*>(d + 16 + 64 + 24 + 72);
   u256* d_nout = reinterpret_cast<u256*>(d + 16 + 64 + 24 + 72 + 16);
-  if ((rc = g16_msm_device_g1(ctx, d_sc, G16_SCALARS_STD, d_pts, 3, d_res, nullptr, 0))) return finish(rc, "self-test MSM failed to launch");
-  if ((rc = g16_ntt_device(ctx, d_nt, d_nout, 3, 0))) return finish(rc, "self-test NTT failed to launch");
-  if (hipMemcpyAsync(&ok, d, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-      hipMemcpyAsync(&h.msm, d_res, 64, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-      hipMemcpyAsync(&h.want, d_pts + 3, 64, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-      hipMemcpyAsync(h.ntt, d_nout, 256, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-      hipMemcpyAsync(&h.one, d_nt + 8, 32, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-      hipStreamSynchronize(ctx->stream) != hipSuccess)
-    return finish(G16_EHIP, "self-test copy failed");
-  if (ok != 1) return finish(G16_ESELFTEST, "device arithmetic self-test failed");
-  if (memcmp(&h.msm, &h.want, 64) != 0) return finish(G16_ESELFTEST, "known-answer MSM self-test failed");
-  for (int i = 0; i < 8; ++i)
-    if (memcmp(&h.ntt[i], &h.one, 32) != 0) return finish(G16_ESELFTEST, "known-answer NTT self-test failed");
-  return finish(G16_OK, "");
+  if ((rc = g16_msm_device_g1(ctx, d_sc, G16_SCALARS_STD, d_pts, 3, d_res, nullptr, 0))) return rc;
+  if ((rc = g16_ntt_device(ctx, d_nt, d_nout, 3, 0))) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(&ok, d, 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(&h.msm, d_res, 64, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(&h.want, d_pts + 3, 64, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(h.ntt, d_nout, 256, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(&h.one, d_nt + 8, 32, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  bool ntt_ok = true;
+  for (int i = 0; i < 8; ++i) ntt_ok &= memcmp(&h.ntt[i], &h.one, 32) == 0;
+  const char* bad = ok != 1                             ? "device arithmetic self-test failed"
+                    : memcmp(&h.msm, &h.want, 64) != 0 ? "known-answer MSM self-test failed"
+                    : !ntt_ok                           ? "known-answer NTT self-test failed"
+                                                        : nullptr;
+  if (!bad) return G16_OK;
+  ctx->err = bad;
+  return G16_ESELFTEST;
 }

@@ -35,8 +35,8 @@ struct g16_group_pkey {
   std::vector<int> device;           // devices[g], for the key's own teardown
   uint32_t nvars = 0, log2n = 0, flavour = 1;
   std::vector<g16_pkey*> key;        // shard g on member g
-  std::vector<void*> task_out;       // member g: its owned coset vectors (owned x n Fr), HBM of devices[g]
-  std::vector<void*> slices;         // member g: 3 x (h_hi - h_lo) Fr, HBM of devices[g]
+  std::vector<DevMem<>> task_out;    // member g: its owned coset vectors (owned x n Fr), HBM of devices[g]
+  std::vector<DevMem<>> slices;      // member g: 3 x (h_hi - h_lo) Fr, HBM of devices[g]
   std::vector<size_t> h_lo, h_hi;
 };
 
@@ -79,13 +79,15 @@ extern "C" int32_t g16_group_create(const int32_t* devices, int32_t ndev, g16_gr
   return G16_OK;
 }
 
+// released explicitly, member by member: shard i first (that waits for device i), then, with device i current, the
+// buffers its proofs exchanged through
 extern "C" void g16_group_pkey_destroy(g16_group_pkey* k) {
   if (!k) return;
   for (size_t i = 0; i < k->key.size(); ++i) {
     g16_pkey_destroy(k->key[i]);
     if (i < k->device.size()) (void)hipSetDevice(k->device[i]);
-    if (i < k->task_out.size() && k->task_out[i]) (void)hipFree(k->task_out[i]);
-    if (i < k->slices.size() && k->slices[i]) (void)hipFree(k->slices[i]);
+    if (i < k->task_out.size()) k->task_out[i].reset();
+    if (i < k->slices.size()) k->slices[i].reset();
   }
   delete k;
 }
@@ -128,14 +130,14 @@ extern "C" int32_t g16_group_pkey_create(g16_group* g, const g16_pkey_desc* desc
     return G16_EINVAL;
   }
   const size_t G = g->m.size();
-  g16_group_pkey* k = new (std::nothrow) g16_group_pkey();
+  Building<g16_group_pkey, g16_group_pkey_destroy> k(new (std::nothrow) g16_group_pkey());
   if (!k) return G16_ENOMEM;
   k->grp = g;
   for (auto& mb : g->m) k->device.push_back(mb.device);
   k->nvars = desc->nvars, k->log2n = desc->log2_domain, k->flavour = desc->flavour;
   k->key.assign(G, nullptr);
-  k->task_out.assign(G, nullptr);
-  k->slices.assign(G, nullptr);
+  k->task_out.resize(G);
+  k->slices.resize(G);
   k->h_lo.assign(G, 0);
   k->h_hi.assign(G, 0);
   const size_t n = size_t(1) << desc->log2_domain;
@@ -144,24 +146,22 @@ extern "C" int32_t g16_group_pkey_create(g16_group* g, const g16_pkey_desc* desc
     g16_pkey_desc d = *desc;
     d.shard_index = (uint32_t)i;
     d.shard_count = (uint32_t)G;
-    int32_t r = g16_pkey_create(g->m[i].ctx, &d, &k->key[i]);
+    g16_ctx* ctx = g->m[i].ctx;   // for_members reports this member's error text
+    int32_t r = g16_pkey_create(ctx, &d, &k->key[i]);
     if (r != G16_OK) return r;
     k->h_lo[i] = (n * i) / G;               // msm.nim:107-115: b = (N * (k + 1)) div ntasks
     k->h_hi[i] = (n * (i + 1)) / G;
     if (desc->flavour != G16_FLAVOUR_SNARKJS) return G16_OK;
     size_t owned = 0;
     for (uint32_t v = 0; v < 3; ++v) owned += task_owner(v, (uint32_t)G) == i;
-    if (hipSetDevice(g->m[i].device) != hipSuccess) return G16_EHIP;
-    if (owned && hipMalloc(&k->task_out[i], owned * n * 32) != hipSuccess) return G16_ENOMEM;
+    HIPCHK(ctx, hipSetDevice(g->m[i].device));
+    if (owned) HIPCHK(ctx, dev_alloc(k->task_out[i], owned * n * 32));
     const size_t nh = k->h_hi[i] - k->h_lo[i];
-    if (nh && hipMalloc(&k->slices[i], 3 * nh * 32) != hipSuccess) return G16_ENOMEM;
+    if (nh) HIPCHK(ctx, dev_alloc(k->slices[i], 3 * nh * 32));
     return G16_OK;
   });
-  if (rc != G16_OK) {
-    g16_group_pkey_destroy(k);
-    return rc;
-  }
-  *out = k;
+  if (rc != G16_OK) return rc;
+  *out = k.release();
   return G16_OK;
 }
 
@@ -193,28 +193,25 @@ extern "C" int32_t g16_group_prove(g16_group* g, const g16_group_pkey* k, const 
       uint32_t mask = 0;
       for (uint32_t v = 0; v < 3; ++v)
         if (task_owner(v, (uint32_t)G) == i) mask |= 1u << v;
-      return g16_prove_partials_begin(g->m[i].ctx, k->key[i], witness, wflags, mask, k->task_out[i]);
+      return g16_prove_partials_begin(g->m[i].ctx, k->key[i], witness, wflags, mask, k->task_out[i].get());
     });
     // phase 2: every member fetches its slices from the owners' HBM and finishes
     if (rc == G16_OK)
       rc = for_members(g, [&](size_t i) -> int32_t {
         g16_ctx* ctx = g->m[i].ctx;
         const size_t nh = k->h_hi[i] - k->h_lo[i];
-        char* sl = (char*)k->slices[i];
-        if (hipSetDevice(g->m[i].device) != hipSuccess) return G16_EHIP;
+        char* sl = (char*)k->slices[i].get();
+        HIPCHK(ctx, hipSetDevice(g->m[i].device));
         for (uint32_t v = 0; v < 3 && nh; ++v) {
           const size_t o = task_owner(v, (uint32_t)G);
           size_t idx = 0;                               // position of v among the owner's pipelines
           for (uint32_t u = 0; u < v; ++u) idx += task_owner(u, (uint32_t)G) == o;
-          const char* src = (const char*)k->task_out[o] + (idx * n + k->h_lo[i]) * 32;
+          const char* src = (const char*)k->task_out[o].get() + (idx * n + k->h_lo[i]) * 32;
           const hipError_t e = g->m[o].device == g->m[i].device
                                    ? hipMemcpyAsync(sl + v * nh * 32, src, nh * 32, hipMemcpyDeviceToDevice, ctx->stream)
                                    : hipMemcpyPeerAsync(sl + v * nh * 32, g->m[i].device, src, g->m[o].device, nh * 32,
                                                         ctx->stream);
-          if (e != hipSuccess) {
-            ctx->err = std::string("coset slice copy: ") + hipGetErrorString(e);
-            return G16_EHIP;
-          }
+          if (int32_t r = g16_hip_check(ctx->err, "coset slice copy", e)) return r;
         }
         return g16_prove_partials_end(ctx, k->key[i], sl, sl + nh * 32, sl + 2 * nh * 32, 0,
                                       records.data() + i * G16_PARTIALS_BYTES);

@@ -96,7 +96,7 @@ static int32_t msm_sort_device(g16_ctx* ctx, hipStream_t st, const void* d_scala
                o_shist = take(use_part ? (size_t)nparts * BS_SPLIT * BS_LOW * 4 : 4);
   int32_t rc = ensure(ctx, S.buf, o);
   if (rc) return rc;
-  char* ws = (char*)S.buf.p;
+  char* ws = (char*)S.buf.p();
   S.count = (uint32_t*)(ws + o_count);
   S.cursor = (uint32_t*)(ws + o_cursor);
   S.offset = (uint32_t*)(ws + o_offset);

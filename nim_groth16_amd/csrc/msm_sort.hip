@@ -45,7 +45,7 @@ static int32_t msm_batch(g16_ctx* ctx, hipStream_t st, const g16_msm_run* runs, 
     }
     int32_t rc = ensure(ctx, *runs[j].acc, o);
     if (rc) return rc;
-    char* ws = (char*)runs[j].acc->p;
+    char* ws = (char*)runs[j].acc->p();
     MsmJob<C>& J = B.job[j];
     J.points = (const typename Ec29<C>::Tab*)runs[j].d_points;
     J.entries = S.entries;
@@ -97,10 +97,10 @@ static int32_t msm_device(g16_ctx* ctx, int group, const void* d_scalars, uint32
   if ((table_c & 0xffu) == 0 && n) {   // plain point array: the accumulate kernel reads reduced-radix entries
     const size_t esz = group == 1 ? 64 : 128;
     if ((rc = ensure(ctx, ctx->stage_p29, n * esz))) return rc;
-    rc = group == 1 ? g16_to29_device_g1(ctx, ctx->stream, d_points, n, ctx->stage_p29.p)
-                    : g16_to29_device_g2(ctx, ctx->stream, d_points, n, ctx->stage_p29.p);
+    rc = group == 1 ? g16_to29_device_g1(ctx, ctx->stream, d_points, n, ctx->stage_p29.p())
+                    : g16_to29_device_g2(ctx, ctx->stream, d_points, n, ctx->stage_p29.p());
     if (rc) return rc;
-    d_points = ctx->stage_p29.p;
+    d_points = ctx->stage_p29.p();
   }
   return group == 1 ? g16_msm_reduce_g1(ctx, ctx->stream, ctx->lane[0].acc, ctx->sort[0], d_points, d_out_aff, d_out_acc)
                     : g16_msm_reduce_g2(ctx, ctx->stream, ctx->lane[0].acc, ctx->sort[0], d_points, d_out_aff, d_out_acc);

@@ -13,7 +13,7 @@ static int32_t stage_accum(g16_ctx* ctx, hipStream_t st, const MsmParams& P, con
   const bool g2 = sizeof(typename C::Aff) == 128;
   const uint32_t ntask = P.nbuckets + P.max_extra;
   KLAUNCH_ON(ctx, st, g2 ? "msm_accum_g2" : "msm_accum_g1", msm_accum<C>, dim3((ntask + ACC_BLOCK - 1) / ACC_BLOCK, ny),
-             ACC_BLOCK, 0, *(const MsmBatch<C>*)batch, P, ctx->profiling ? ctx->clk_buf : (unsigned long long*)nullptr);
+             ACC_BLOCK, 0, *(const MsmBatch<C>*)batch, P, ctx->profiling ? ctx->clk_buf.get() : (unsigned long long*)nullptr);
   HIPCHK(ctx, hipGetLastError());
   return G16_OK;
 }

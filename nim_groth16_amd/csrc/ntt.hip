@@ -14,7 +14,7 @@ static int32_t ensure_twiddles(g16_ctx* ctx, uint32_t log2n) {
   const size_t n = size_t(1) << log2n;
   int32_t rc;
   if ((rc = ensure(ctx, ctx->ntt_tw, (n / 2 + 1) * 32))) return rc;
-  KLAUNCH(ctx, "ntt_twiddles", ntt_make_twiddles, (uint32_t)((n / 2 + 1 + 255) / 256), 256, 0, (u256*)ctx->ntt_tw.p,
+  KLAUNCH(ctx, "ntt_twiddles", ntt_make_twiddles, (uint32_t)((n / 2 + 1 + 255) / 256), 256, 0, (u256*)ctx->ntt_tw.p(),
           log2n);
   ctx->tw_log2n = log2n;
   return G16_OK;
@@ -77,7 +77,7 @@ static int32_t ntt_batched(g16_ctx* ctx, const u256* in, size_t in_stride, u256*
   u256 *tmpA = nullptr, *tmpB = nullptr;
   if (npass > 1) {
     if ((rc = ensure(ctx, ctx->ntt_tmp, (npass > 2 ? 2 : 1) * n * 32 * batch))) return rc;
-    tmpA = (u256*)ctx->ntt_tmp.p;
+    tmpA = (u256*)ctx->ntt_tmp.p();
     tmpB = tmpA + n * batch;
   }
   const u256* src = in;
@@ -90,28 +90,28 @@ static int32_t ntt_batched(g16_ctx* ctx, const u256* in, size_t in_stride, u256*
     if (last && fuse_abc) {
       if (small)
         KLAUNCH(ctx, "ntt_last_pass_abc", (ntt_last_pass_abc<NTT_BLOCK_SMALL, NTT_TILE_SMALL>), ntiles, NTT_BLOCK_SMALL,
-                shmem, src, out, (const u256*)ctx->ntt_tw.p, log2n, log2s, rho, log2b, src_stride, fuse_abc == 2 ? 1 : 0);
+                shmem, src, out, (const u256*)ctx->ntt_tw.p(), log2n, log2s, rho, log2b, src_stride, fuse_abc == 2 ? 1 : 0);
       else if (mid)
         KLAUNCH(ctx, "ntt_last_pass_abc", (ntt_last_pass_abc<NTT_BLOCK_MID, NTT_TILE_MID>), ntiles, NTT_BLOCK_MID,
-                shmem, src, out, (const u256*)ctx->ntt_tw.p, log2n, log2s, rho, log2b, src_stride, fuse_abc == 2 ? 1 : 0);
+                shmem, src, out, (const u256*)ctx->ntt_tw.p(), log2n, log2s, rho, log2b, src_stride, fuse_abc == 2 ? 1 : 0);
       else
         KLAUNCH(ctx, "ntt_last_pass_abc", (ntt_last_pass_abc<NTT_BLOCK, NTT_TILE>), ntiles, NTT_BLOCK, shmem, src, out,
-                (const u256*)ctx->ntt_tw.p, log2n, log2s, rho, log2b, src_stride, fuse_abc == 2 ? 1 : 0);
+                (const u256*)ctx->ntt_tw.p(), log2n, log2s, rho, log2b, src_stride, fuse_abc == 2 ? 1 : 0);
       break;
     }
     u256* dst = last ? out : ((p & 1) ? tmpB : tmpA);
     const size_t dst_stride = last ? out_stride : n;
     if (small)
       KLAUNCH(ctx, inverse ? "ntt_pass_inv" : "ntt_pass_fwd", ntt_pass<NTT_BLOCK_SMALL>, dim3(ntiles, batch),
-              NTT_BLOCK_SMALL, shmem, src, dst, (const u256*)ctx->ntt_tw.p, log2n, log2s, rho, log2b, inverse,
+              NTT_BLOCK_SMALL, shmem, src, dst, (const u256*)ctx->ntt_tw.p(), log2n, log2s, rho, log2b, inverse,
               last ? 1 : 0, src_stride, dst_stride, last ? scale : (const u256*)nullptr, p == 0 ? c_from_ab : 0);
     else if (mid)
       KLAUNCH(ctx, inverse ? "ntt_pass_inv" : "ntt_pass_fwd", ntt_pass<NTT_BLOCK_MID>, dim3(ntiles, batch),
-              NTT_BLOCK_MID, shmem, src, dst, (const u256*)ctx->ntt_tw.p, log2n, log2s, rho, log2b, inverse,
+              NTT_BLOCK_MID, shmem, src, dst, (const u256*)ctx->ntt_tw.p(), log2n, log2s, rho, log2b, inverse,
               last ? 1 : 0, src_stride, dst_stride, last ? scale : (const u256*)nullptr, p == 0 ? c_from_ab : 0);
     else
       KLAUNCH(ctx, inverse ? "ntt_pass_inv" : "ntt_pass_fwd", ntt_pass<NTT_BLOCK>, dim3(ntiles, batch), NTT_BLOCK, shmem,
-              src, dst, (const u256*)ctx->ntt_tw.p, log2n, log2s, rho, log2b, inverse, last ? 1 : 0, src_stride,
+              src, dst, (const u256*)ctx->ntt_tw.p(), log2n, log2s, rho, log2b, inverse, last ? 1 : 0, src_stride,
               dst_stride, last ? scale : (const u256*)nullptr, p == 0 ? c_from_ab : 0);
     src = dst;
     src_stride = dst_stride;
@@ -124,8 +124,8 @@ int32_t g16_ntt_device(g16_ctx* ctx, const void* d_src, void* d_dst, uint32_t lo
   if (d_src == d_dst && ntt_one_pass(ntt_geom(g16_env().ntt_tile), log2n) && log2n > 0) {   // single pass: never in place
     int32_t rc = ensure(ctx, ctx->ntt_tmp, (size_t(32) << log2n));
     if (rc) return rc;
-    if ((rc = ntt_batched(ctx, (const u256*)d_src, 0, (u256*)ctx->ntt_tmp.p, 0, 1, log2n, inverse, nullptr))) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(d_dst, ctx->ntt_tmp.p, size_t(32) << log2n, hipMemcpyDeviceToDevice, ctx->stream));
+    if ((rc = ntt_batched(ctx, (const u256*)d_src, 0, (u256*)ctx->ntt_tmp.p(), 0, 1, log2n, inverse, nullptr))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(d_dst, ctx->ntt_tmp.p(), size_t(32) << log2n, hipMemcpyDeviceToDevice, ctx->stream));
     return G16_OK;
   }
   return ntt_batched(ctx, (const u256*)d_src, 0, (u256*)d_dst, 0, 1, log2n, inverse, nullptr);
@@ -137,7 +137,7 @@ static int32_t ensure_coset(g16_ctx* ctx, uint32_t log2n, int mode) {
   int32_t rc;
   if ((rc = ensure(ctx, ctx->coset[mode], n * 32))) return rc;
   KLAUNCH(ctx, "ntt_coset_table", ntt_make_coset_table, (uint32_t)((n + 255) / 256), 256, 0,
-          (u256*)ctx->coset[mode].p, log2n, mode);
+          (u256*)ctx->coset[mode].p(), log2n, mode);
   ctx->coset_log2n[mode] = log2n;
   return G16_OK;
 }
@@ -159,7 +159,7 @@ int32_t g16_quotient_device(g16_ctx* ctx, const void* d_a, const void* d_b, cons
   int32_t rc;
   if ((rc = ensure(ctx, ctx->quot, 4 * n * 32))) return rc;
   if ((rc = ensure_coset(ctx, log2n, 0))) return rc;
-  u256* X = (u256*)ctx->quot.p;   // 3n: coset coefficients  |  n: JensGroth intermediate
+  u256* X = (u256*)ctx->quot.p();   // 3n: coset coefficients  |  n: JensGroth intermediate
   u256* Y = X + 3 * n;
   const u256* in = (const u256*)d_a;
   if (c_from_ab && ((const u256*)d_b != in + n || (const u256*)d_c != in + 2 * n || log2n == 0)) {
@@ -173,19 +173,19 @@ int32_t g16_quotient_device(g16_ctx* ctx, const void* d_a, const void* d_b, cons
     in = X;
     if (ntt_one_pass(ntt_geom(g16_env().ntt_tile), log2n)) {   // a single pass cannot run in place: stage behind the work area
       if ((rc = ensure(ctx, ctx->ntt_tmp, 3 * n * 32))) return rc;
-      HIPCHK(ctx, hipMemcpyAsync(ctx->ntt_tmp.p, X, 3 * n * 32, hipMemcpyDeviceToDevice, ctx->stream));
-      in = (const u256*)ctx->ntt_tmp.p;
+      HIPCHK(ctx, hipMemcpyAsync(ctx->ntt_tmp.p(), X, 3 * n * 32, hipMemcpyDeviceToDevice, ctx->stream));
+      in = (const u256*)ctx->ntt_tmp.p();
     }
   }
   // shiftEvalDomain x3 (prover.nim:109-113, 167-169): iNTT with eta^i/n folded in, then forward NTT whose last pass
   // forms A1*B1 - C1 (prover.nim:175-176) [* invZ1, prover.nim:141]
-  if ((rc = ntt_batched(ctx, in, n, X, n, 3, log2n, 1, (const u256*)ctx->coset[0].p, 0, c_from_ab))) return rc;
+  if ((rc = ntt_batched(ctx, in, n, X, n, 3, log2n, 1, (const u256*)ctx->coset[0].p(), 0, c_from_ab))) return rc;
   if (flavour == 1) {  // Snarkjs
     if ((rc = ntt_batched(ctx, X, n, (u256*)d_out, 0, 3, log2n, 0, nullptr, 1))) return rc;
   } else {  // JensGroth: ... * invZ1, iNTT, * eta^-i   (prover.nim:141-143)
     if ((rc = ensure_coset(ctx, log2n, 1))) return rc;
     if ((rc = ntt_batched(ctx, X, n, Y, 0, 3, log2n, 0, nullptr, 2))) return rc;
-    if ((rc = ntt_batched(ctx, Y, n, (u256*)d_out, n, 1, log2n, 1, (const u256*)ctx->coset[1].p))) return rc;
+    if ((rc = ntt_batched(ctx, Y, n, (u256*)d_out, n, 1, log2n, 1, (const u256*)ctx->coset[1].p()))) return rc;
   }
   HIPCHK(ctx, hipGetLastError());
   return G16_OK;
@@ -203,8 +203,8 @@ int32_t g16_coset_pipeline_device(g16_ctx* ctx, const void* d_in, uint32_t log2n
   int32_t rc;
   if ((rc = ensure(ctx, ctx->quot, 4 * n * 32))) return rc;
   if ((rc = ensure_coset(ctx, log2n, 0))) return rc;
-  u256* X = (u256*)ctx->quot.p;
-  if ((rc = ntt_batched(ctx, (const u256*)d_in, n, X, n, 1, log2n, 1, (const u256*)ctx->coset[0].p))) return rc;
+  u256* X = (u256*)ctx->quot.p();
+  if ((rc = ntt_batched(ctx, (const u256*)d_in, n, X, n, 1, log2n, 1, (const u256*)ctx->coset[0].p()))) return rc;
   return ntt_batched(ctx, X, n, (u256*)d_out, n, 1, log2n, 0, nullptr);
 }
 

@@ -10,8 +10,8 @@ struct g16_vkey {
   int device = 0;
   uint32_t npubs = 0;
   g2_aff gamma2, delta2;
-  void* d_ic = nullptr;   // (npubs + 1) G1 points
-  void* d_ab = nullptr;   // Miller value of (alpha1, beta2): 384 B
+  DevMem<> d_ic;   // (npubs + 1) G1 points
+  DevMem<> d_ab;   // Miller value of (alpha1, beta2): 384 B
 };
 
 namespace {
@@ -154,7 +154,7 @@ extern "C" int32_t g16_pairing(g16_ctx* ctx, const void* g1_points, const void* 
   int32_t rc;
   const size_t o_q = n * 64, o_out = o_q + n * 128;
   if ((rc = ensure(ctx, ctx->stage_p, o_out + n * sizeof(fp12_t)))) return rc;
-  char* ws = (char*)ctx->stage_p.p;
+  char* ws = (char*)ctx->stage_p.p();
   HIPCHK(ctx, hipMemcpyAsync(ws, g1_points, n * 64, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(ws + o_q, g2_points, n * 128, hipMemcpyHostToDevice, ctx->stream));
   KLAUNCH(ctx, "pairing", pairing_kernel, (uint32_t)((n + PBLOCK - 1) / PBLOCK), PBLOCK, 0, (const g1_aff*)ws,
@@ -172,36 +172,25 @@ extern "C" int32_t g16_vkey_create(g16_ctx* ctx, const g16_vkey_desc* d, g16_vke
     return G16_EINVAL;
   }
   CTX_ENTER(ctx);
-  g16_vkey* k = new (std::nothrow) g16_vkey();
+  Building<g16_vkey, g16_vkey_destroy> k(new (std::nothrow) g16_vkey());
   if (!k) return G16_ENOMEM;
   k->device = ctx->device;
   k->npubs = d->npubs;
   memcpy(&k->gamma2, d->gamma2, 128);
   memcpy(&k->delta2, d->delta2, 128);
   const size_t nio = (size_t)d->npubs + 1;
-  auto fail = [&](int32_t rc) {
-    g16_vkey_destroy(k);
-    return rc;
-  };
-  if (hipMalloc(&k->d_ic, nio * 64) != hipSuccess || hipMalloc(&k->d_ab, sizeof(fp12_t) + 64 + 128) != hipSuccess) {
-    ctx->err = "g16_vkey_create: hipMalloc failed";
-    return fail(G16_ENOMEM);
-  }
-  char* ab = (char*)k->d_ab;
-  if (hipMemcpyAsync(k->d_ic, d->pointsIC, nio * 64, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-      hipMemcpyAsync(ab + sizeof(fp12_t), d->alpha1, 64, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-      hipMemcpyAsync(ab + sizeof(fp12_t) + 64, d->beta2, 128, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-    ctx->err = "g16_vkey_create: upload failed";
-    return fail(G16_EHIP);
-  }
+  HIPCHK(ctx, dev_alloc(k->d_ic, nio * 64));
+  HIPCHK(ctx, dev_alloc(k->d_ab, sizeof(fp12_t) + 64 + 128));
+  char* ab = (char*)k->d_ab.get();
+  HIPCHK(ctx, hipMemcpyAsync(k->d_ic.get(), d->pointsIC, nio * 64, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ab + sizeof(fp12_t), d->alpha1, 64, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ab + sizeof(fp12_t) + 64, d->beta2, 128, hipMemcpyHostToDevice, ctx->stream));
   // vkey.spec.alphaBeta (zkey_types.nim:62-73) is kept as its Miller value; the final exponentiation is shared
   hipLaunchKernelGGL(pairing_kernel, dim3(1), dim3(PBLOCK), 0, ctx->stream, (const g1_aff*)(ab + sizeof(fp12_t)),
                      (const g2_aff*)(ab + sizeof(fp12_t) + 64), 1u, 0, (fp12_t*)ab);
-  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
-    ctx->err = "g16_vkey_create: kernel failed";
-    return fail(G16_EHIP);
-  }
-  *out = k;
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  *out = k.release();
   return G16_OK;
 }
 
@@ -209,8 +198,6 @@ extern "C" void g16_vkey_destroy(g16_vkey* k) {
   if (!k) return;
   (void)hipSetDevice(k->device);   // device-bound like g16_pkey: valid before and after any context
   (void)hipDeviceSynchronize();
-  if (k->d_ic) (void)hipFree(k->d_ic);
-  if (k->d_ab) (void)hipFree(k->d_ab);
   delete k;
 }
 
@@ -234,19 +221,19 @@ extern "C" int32_t g16_verify(g16_ctx* ctx, const g16_vkey* key, const g16_proof
                o_mil = take(3 * count * sizeof(fp12_t)), o_st = take(count * 4);
   int32_t rc;
   if ((rc = ensure(ctx, ctx->stage_p, o))) return rc;
-  char* ws = (char*)ctx->stage_p.p;
+  char* ws = (char*)ctx->stage_p.p();
   HIPCHK(ctx, hipMemcpyAsync(ws + o_pr, proofs, count * sizeof(g16_proof), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(ws + o_pub, public_io, total * 32, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(ws + o_st, 0, count * 4, ctx->stream));
   KLAUNCH(ctx, "verify_pub_terms", verify_pub_terms, (uint32_t)((total + PBLOCK - 1) / PBLOCK), PBLOCK, 0,
-          (const u256*)(ws + o_pub), (flags & G16_SCALARS_MONT) ? 1u : 0u, (const g1_aff*)key->d_ic, (uint32_t)nio,
+          (const u256*)(ws + o_pub), (flags & G16_SCALARS_MONT) ? 1u : 0u, (const g1_aff*)key->d_ic.get(), (uint32_t)nio,
           (uint32_t)total, (g1_acc*)(ws + o_part), (int32_t*)(ws + o_st));
   KLAUNCH(ctx, "verify_miller", verify_miller, (uint32_t)((3 * count + PBLOCK - 1) / PBLOCK), PBLOCK, 0,
           (const g16_proof*)(ws + o_pr), (uint32_t)count, (const g1_acc*)(ws + o_part), (uint32_t)nio, key->gamma2,
           key->delta2, twist_b(), (flags & G16_VERIFY_SUBGROUP) ? 1u : 0u, (fp12_t*)(ws + o_mil),
           (int32_t*)(ws + o_st));
   KLAUNCH(ctx, "verify_final", verify_final, (uint32_t)((count + PBLOCK - 1) / PBLOCK), PBLOCK, 0,
-          (const fp12_t*)(ws + o_mil), (const fp12_t*)key->d_ab, (uint32_t)count, (int32_t*)(ws + o_st));
+          (const fp12_t*)(ws + o_mil), (const fp12_t*)key->d_ab.get(), (uint32_t)count, (int32_t*)(ws + o_st));
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipMemcpyAsync(status, ws + o_st, count * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));

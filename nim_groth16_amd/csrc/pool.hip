@@ -31,12 +31,14 @@ struct PoolRec {
   uint32_t flags = 0;
   unsigned char r[32], s[32];   // mask, Montgomery (zero when the caller passed NULL)
   g16_combine_pre pre;          // written by the enqueue half at launch
-  void* d_w = nullptr;          // device witness buffer (nvars * 32 bytes)
-  hipEvent_t up = nullptr;      // the upload into d_w has completed
-  hipEvent_t done = nullptr;    // the result copy into the pinned slot has completed
+  DevMem<> d_w;                 // device witness buffer (nvars * 32 bytes)
+  Event up;                     // the upload into d_w has completed
+  Event done;                   // the result copy into the pinned slot has completed
 };
 }  // namespace
 
+// The contexts are destroyed by g16_prover_destroy, which also drains the copy stream; the other members release
+// themselves when it deletes the pool (no work is left on the device by then, so their order does not matter).
 struct g16_prover {
   int device = 0;
   const g16_pkey* key = nullptr;
@@ -45,9 +47,9 @@ struct g16_prover {
   std::vector<g16_ctx*> ctx;           // one per slot
   std::vector<int> slot_rec;           // record running on each slot, -1 = free
   std::vector<PoolRec> rec;            // depth + 1 records: one per outstanding proof
-  hipStream_t copy = nullptr;          // witness uploads (non-blocking; not a lane of any context)
-  unsigned char* d_part = nullptr;     // depth x G16_PARTIALS_BYTES: the partial record of each slot (HBM)
-  unsigned char* h_res = nullptr;      // (depth + 1) x G16_COMBINE_RES_BYTES, pinned: the MSM sums of each record
+  Stream copy;                         // witness uploads (non-blocking; not a lane of any context)
+  DevMem<unsigned char> d_part;        // depth x G16_PARTIALS_BYTES: the partial record of each slot (HBM)
+  PinnedMem<unsigned char> h_res;      // (depth + 1) x G16_COMBINE_RES_BYTES, pinned: the MSM sums of each record
   uint64_t next_ticket = 1;
   int32_t failed = G16_OK;
   std::string err;
@@ -64,25 +66,28 @@ static int32_t pool_einval(g16_prover* p, const char* msg) {
   if (p->failed == G16_OK) p->err = msg;
   return G16_EINVAL;
 }
-#define POOLCHK(p, call)                                                                                    \
-  do {                                                                                                      \
-    hipError_t e__ = (call);                                                                                \
-    if (e__ != hipSuccess)                                                                                  \
-      return pool_fail(p, e__ == hipErrorOutOfMemory ? G16_ENOMEM : G16_EHIP,                               \
-                       std::string(#call) + ": " + hipGetErrorString(e__));                                 \
+// a failed HIP call of the pool itself: g16_hip_check's message and code, through pool_fail
+static int32_t pool_hip(g16_prover* p, const char* call, hipError_t e) {
+  std::string msg;
+  const int32_t rc = g16_hip_check(msg, call, e);
+  return rc ? pool_fail(p, rc, msg) : G16_OK;
+}
+#define POOLCHK(p, call)                                          \
+  do {                                                            \
+    if (int32_t rc__ = pool_hip(p, #call, (call))) return rc__;   \
   } while (0)
 
 // enqueue record i on free slot `slot` (never waits for the GPU)
 static int32_t pool_launch(g16_prover* p, int i, int slot) {
   PoolRec& r = p->rec[i];
   g16_ctx* c = p->ctx[slot];
-  unsigned char* part = p->d_part + (size_t)slot * G16_PARTIALS_BYTES;
-  POOLCHK(p, hipStreamWaitEvent(c->stream, r.up, 0));
+  unsigned char* part = p->d_part.get() + (size_t)slot * G16_PARTIALS_BYTES;
+  POOLCHK(p, hipStreamWaitEvent(c->stream, r.up.get(), 0));
   const uint32_t flags = (r.flags & G16_SCALARS_MONT) | G16_SCALARS_DEVICE | G16_OUT_DEVICE | G16_NO_HOST_SYNC;
-  int32_t rc = g16_prove_partials(c, p->key, r.d_w, flags, part);
+  int32_t rc = g16_prove_partials(c, p->key, r.d_w.get(), flags, part);
   if (rc) return pool_fail(p, rc, c->err);
-  rc = g16_combine_enqueue(c, p->key, part, 1, G16_SCALARS_DEVICE, r.r, r.s, p->h_res + (size_t)i * G16_COMBINE_RES_BYTES,
-                           r.done, &r.pre);
+  rc = g16_combine_enqueue(c, p->key, part, 1, G16_SCALARS_DEVICE, r.r, r.s,
+                           p->h_res.get() + (size_t)i * G16_COMBINE_RES_BYTES, r.done.get(), &r.pre);
   if (rc) return pool_fail(p, rc, c->err);
   r.state = REC_RUNNING;
   r.slot = slot;
@@ -96,7 +101,7 @@ static int32_t pool_advance(g16_prover* p) {
   for (size_t i = 0; i < p->rec.size(); ++i) {
     PoolRec& r = p->rec[i];
     if (r.state != REC_RUNNING) continue;
-    const hipError_t q = hipEventQuery(r.done);
+    const hipError_t q = hipEventQuery(r.done.get());
     if (q == hipErrorNotReady) continue;
     if (q != hipSuccess) return pool_fail(p, G16_EHIP, std::string("proof failed on the GPU: ") + hipGetErrorString(q));
     r.state = REC_DONE;
@@ -129,17 +134,7 @@ extern "C" void g16_prover_destroy(g16_prover* p) {
   if (!p) return;
   (void)hipSetDevice(p->device);
   for (g16_ctx* c : p->ctx) g16_ctx_destroy(c);   // waits for its streams: every launched proof
-  if (p->copy) {
-    (void)hipStreamSynchronize(p->copy);          // a prefetched upload
-    (void)hipStreamDestroy(p->copy);
-  }
-  for (PoolRec& r : p->rec) {
-    if (r.done) (void)hipEventDestroy(r.done);
-    if (r.up) (void)hipEventDestroy(r.up);
-    if (r.d_w) (void)hipFree(r.d_w);
-  }
-  if (p->d_part) (void)hipFree(p->d_part);
-  if (p->h_res) (void)hipHostFree(p->h_res);
+  if (p->copy) (void)hipStreamSynchronize(p->copy.get());   // a prefetched upload
   delete p;
 }
 
@@ -155,9 +150,8 @@ extern "C" int32_t g16_prover_create(int32_t device, const g16_pkey* key, uint32
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ENODEV;
   if (device < 0 || device >= ndev) return G16_EINVAL;
   if (hipSetDevice(device) != hipSuccess) return G16_ENODEV;
-  g16_prover* p = new (std::nothrow) g16_prover();
+  Building<g16_prover, g16_prover_destroy> p(new (std::nothrow) g16_prover());
   if (!p) return G16_ENOMEM;
-  int32_t rc = G16_OK;
   try {
     p->device = device;
     p->key = key;
@@ -167,25 +161,19 @@ extern "C" int32_t g16_prover_create(int32_t device, const g16_pkey* key, uint32
     p->slot_rec.assign(depth, -1);
     p->rec.resize(depth + 1);
   } catch (const std::bad_alloc&) {
-    rc = G16_ENOMEM;
+    return G16_ENOMEM;
   }
-  for (uint32_t s = 0; s < depth && !rc; ++s) rc = g16_ctx_create(device, &p->ctx[s]);
-  auto hip = [&](hipError_t e) {
-    if (!rc && e != hipSuccess) rc = e == hipErrorOutOfMemory ? G16_ENOMEM : G16_EHIP;
-  };
-  if (!rc) hip(hipStreamCreateWithFlags(&p->copy, hipStreamNonBlocking));
+  for (uint32_t s = 0; s < depth; ++s)
+    if (int32_t rc = g16_ctx_create(device, &p->ctx[s])) return rc;
+  POOLCHK(p.get(), stream_create(p->copy));
   for (PoolRec& r : p->rec) {
-    if (!rc) hip(hipEventCreateWithFlags(&r.done, hipEventDisableTiming));
-    if (!rc) hip(hipEventCreateWithFlags(&r.up, hipEventDisableTiming));
-    if (!rc) hip(hipMalloc(&r.d_w, p->wbytes));
+    POOLCHK(p.get(), event_create(r.done));
+    POOLCHK(p.get(), event_create(r.up));
+    POOLCHK(p.get(), dev_alloc(r.d_w, p->wbytes));
   }
-  if (!rc) hip(hipMalloc((void**)&p->d_part, (size_t)depth * G16_PARTIALS_BYTES));
-  if (!rc) hip(hipHostMalloc((void**)&p->h_res, (size_t)(depth + 1) * G16_COMBINE_RES_BYTES, hipHostMallocDefault));
-  if (rc) {
-    g16_prover_destroy(p);
-    return rc;
-  }
-  *out = p;
+  POOLCHK(p.get(), dev_alloc(p->d_part, (size_t)depth * G16_PARTIALS_BYTES));
+  POOLCHK(p.get(), pinned_alloc(p->h_res, (size_t)(depth + 1) * G16_COMBINE_RES_BYTES));
+  *out = p.release();
   return G16_OK;
 }
 
@@ -207,9 +195,10 @@ extern "C" int32_t g16_prover_submit(g16_prover* p, const void* witness, uint32_
   if (i < 0) return G16_EBUSY;   // depth + 1 outstanding
   PoolRec& r = p->rec[i];
   // (a free record's d_w is no longer read: its last proof was collected, after its `done` event)
-  POOLCHK(p, hipMemcpyAsync(r.d_w, witness, p->wbytes,
-                            (flags & G16_SCALARS_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, p->copy));
-  POOLCHK(p, hipEventRecord(r.up, p->copy));
+  POOLCHK(p, hipMemcpyAsync(r.d_w.get(), witness, p->wbytes,
+                            (flags & G16_SCALARS_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                            p->copy.get()));
+  POOLCHK(p, hipEventRecord(r.up.get(), p->copy.get()));
   r.flags = flags;
   memset(r.r, 0, 32);
   memset(r.s, 0, 32);
@@ -241,11 +230,11 @@ extern "C" int32_t g16_prover_collect(g16_prover* p, uint64_t ticket, g16_proof*
     // proof.  Otherwise block on this one.
     bool pending = false;
     for (const PoolRec& q : p->rec) pending |= q.state == REC_PENDING;
-    if (r.state == REC_RUNNING && !pending) POOLCHK(p, hipEventSynchronize(r.done));
+    if (r.state == REC_RUNNING && !pending) POOLCHK(p, hipEventSynchronize(r.done.get()));
     else std::this_thread::yield();
     if (int32_t rc = pool_advance(p)) return rc;
   }
-  g16_combine_finish(&r.pre, p->h_res + (size_t)i * G16_COMBINE_RES_BYTES, out);
+  g16_combine_finish(&r.pre, p->h_res.get() + (size_t)i * G16_COMBINE_RES_BYTES, out);
   r.state = REC_FREE;
   r.ticket = 0;
   return G16_OK;
@@ -258,13 +247,12 @@ extern "C" int32_t g16_host_alloc(int32_t device, size_t bytes, void** out) {
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ENODEV;
   if (device < 0 || device >= ndev || bytes == 0) return G16_EINVAL;
   if (hipSetDevice(device) != hipSuccess) return G16_ENODEV;
-  if (hipHostMalloc(out, bytes, hipHostMallocDefault) != hipSuccess) {
-    *out = nullptr;
-    return G16_ENOMEM;
-  }
+  PinnedMem<> mem;   // handed to the caller, who returns it to g16_host_free
+  if (pinned_alloc(mem, bytes) != hipSuccess) return G16_ENOMEM;
+  *out = mem.release();
   return G16_OK;
 }
 
 extern "C" void g16_host_free(void* p) {
-  if (p) (void)hipHostFree(p);
+  if (p) HostFree{}(p);
 }

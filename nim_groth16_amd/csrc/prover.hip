@@ -37,8 +37,8 @@ struct g16_pkey {
   // witness sort such an entry still occupies a loop trip of a wave whose other lanes run a full addition, so a set
   // with >= G16_INF_COMPACT % of them gets entry lists of its own that leave them out: liveA = A1's bitmap, liveB =
   // the union of B1's and B2's (one sort serves both).  nullptr = dense: the set rides on the shared sort.
-  const uint32_t* liveA = nullptr;
-  uint32_t* liveB = nullptr;      // owned (the union), or nullptr
+  const uint32_t* liveA = nullptr;   // not owned: A1's own bitmap
+  DevMem<uint32_t> liveB;            // owned (the union), or empty
   size_t deadB = 0;               // wires whose B1 AND B2 points are both (0,0)
 };
 
@@ -121,8 +121,7 @@ extern "C" void g16_pkey_destroy(g16_pkey* k) {
   (void)hipSetDevice(k->device);
   (void)hipDeviceSynchronize();
   g16_spmat_destroy(k->abc);
-  if (k->liveB) (void)hipFree(k->liveB);
-  delete k;
+  delete k;   // (liveB goes with it)
 }
 
 // what the prover pool (pool.hip) needs to know about a key
@@ -174,7 +173,7 @@ static int32_t pkey_create(g16_ctx* ctx, const g16_pkey_desc* d, const CoeffSour
     return G16_EINVAL;
   }
   CTX_ENTER(ctx);
-  g16_pkey* k = new (std::nothrow) g16_pkey();
+  Building<g16_pkey, g16_pkey_destroy> k(new (std::nothrow) g16_pkey());
   if (!k) return G16_ENOMEM;
   k->device = ctx->device;
   k->nvars = d->nvars;
@@ -187,17 +186,11 @@ static int32_t pkey_create(g16_ctx* ctx, const g16_pkey_desc* d, const CoeffSour
   memcpy(&k->beta2, d->beta2, 128);
   memcpy(&k->delta2, d->delta2, 128);
   int32_t rc;
-#define TRY(x)               \
-  if ((rc = (x)) != G16_OK) { \
-    g16_pkey_destroy(k);     \
-    return rc;               \
-  }
   // contiguous index ranges per rank: b = (N*(k+1)) div ntasks   (msm.nim:107-115)
   k->shard_count = d->shard_count ? d->shard_count : 1;
   k->shard_index = d->shard_index;
   if (k->shard_index >= k->shard_count) {
     ctx->err = "shard_index >= shard_count";
-    g16_pkey_destroy(k);
     return G16_EINVAL;
   }
   auto range = [&](size_t N, size_t& lo, size_t& hi) {
@@ -212,30 +205,25 @@ static int32_t pkey_create(g16_ctx* ctx, const g16_pkey_desc* d, const CoeffSour
   std::vector<unsigned char> c1pad((k->w_hi - k->w_lo) * 64, 0);
   for (size_t wI = k->w_lo; wI < k->w_hi; ++wI)
     if (wI > d->npubs) memcpy(&c1pad[(wI - k->w_lo) * 64], (const char*)d->pointsC1 + 64 * (wI - d->npubs - 1), 64);
-  TRY(g16_points_register_g1(ctx, (const char*)d->pointsA1 + 64 * k->w_lo, k->w_hi - k->w_lo, &k->A1));
-  TRY(g16_points_register_g1(ctx, (const char*)d->pointsB1 + 64 * k->w_lo, k->w_hi - k->w_lo, &k->B1));
-  TRY(g16_points_register_g2(ctx, (const char*)d->pointsB2 + 128 * k->w_lo, k->w_hi - k->w_lo, &k->B2));
-  TRY(g16_points_register_g1(ctx, c1pad.data(), k->w_hi - k->w_lo, &k->C1));
-  TRY(g16_points_register_g1(ctx, (const char*)d->pointsH1 + 64 * k->h_lo, k->h_hi - k->h_lo, &k->H1));
+  if ((rc = g16_points_register_g1(ctx, (const char*)d->pointsA1 + 64 * k->w_lo, k->w_hi - k->w_lo, &k->A1))) return rc;
+  if ((rc = g16_points_register_g1(ctx, (const char*)d->pointsB1 + 64 * k->w_lo, k->w_hi - k->w_lo, &k->B1))) return rc;
+  if ((rc = g16_points_register_g2(ctx, (const char*)d->pointsB2 + 128 * k->w_lo, k->w_hi - k->w_lo, &k->B2))) return rc;
+  if ((rc = g16_points_register_g1(ctx, c1pad.data(), k->w_hi - k->w_lo, &k->C1))) return rc;
+  if ((rc = g16_points_register_g1(ctx, (const char*)d->pointsH1 + 64 * k->h_lo, k->h_hi - k->h_lo, &k->H1))) return rc;
   {   // sparse sets get their own entry lists (see g16_pkey)
     const size_t nw = k->w_hi - k->w_lo;
     k->liveA = g16_points_live_if_sparse(k->A1);
     if (nw && k->B1->d_live && k->B2->d_live) {
-      uint32_t* d_cnt = nullptr;
       uint32_t dead = 0;
-      TRY(ensure(ctx, ctx->stage_o, 2048));
-      d_cnt = (uint32_t*)ctx->stage_o.p;
-      if (hipMalloc((void**)&k->liveB, ((nw + 31) / 32 + 1) * 4) != hipSuccess) TRY(G16_ENOMEM);
-      if (hipMemsetAsync(d_cnt, 0, 4, ctx->stream) != hipSuccess) TRY(G16_EHIP);
-      TRY(g16_bitmap_or_device(ctx, k->liveB, k->B1->d_live, k->B2->d_live, nw, d_cnt));
-      if (hipMemcpyAsync(&dead, d_cnt, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-          hipStreamSynchronize(ctx->stream) != hipSuccess)
-        TRY(G16_EHIP);
+      if ((rc = ensure(ctx, ctx->stage_o, 2048))) return rc;
+      uint32_t* d_cnt = (uint32_t*)ctx->stage_o.p();
+      HIPCHK(ctx, dev_alloc(k->liveB, ((nw + 31) / 32 + 1) * 4));
+      HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, 4, ctx->stream));
+      if ((rc = g16_bitmap_or_device(ctx, k->liveB.get(), k->B1->d_live.get(), k->B2->d_live.get(), nw, d_cnt))) return rc;
+      HIPCHK(ctx, hipMemcpyAsync(&dead, d_cnt, 4, hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
       k->deadB = dead;
-      if (!dead || (size_t)dead * 100 < (size_t)g16_env().inf_compact_pct * nw) {   // dense: share the witness sort
-        (void)hipFree(k->liveB);
-        k->liveB = nullptr;
-      }
+      if (!dead || (size_t)dead * 100 < (size_t)g16_env().inf_compact_pct * nw) k->liveB.reset();   // dense: share the witness sort
     }
   }
   // the A and B entries in row order, rows binned by length (sum order is irrelevant mod r)
@@ -244,7 +232,6 @@ static int32_t pkey_create(g16_ctx* ctx, const g16_pkey_desc* d, const CoeffSour
     vrow.resize(cs.count ? cs.count : 1);
   } catch (const std::bad_alloc&) {
     ctx->err = "out of host memory";
-    g16_pkey_destroy(k);
     return G16_ENOMEM;
   }
   for (size_t e = 0; e < cs.count; ++e) {
@@ -253,16 +240,15 @@ static int32_t pkey_create(g16_ctx* ctx, const g16_pkey_desc* d, const CoeffSour
     if (matrix > 1 || row >= n || col >= d->nvars) {
       // MatrixC entries make the reference's buildABC raise (prover.nim:67)
       ctx->err = "coefficient entry out of range (matrix must be 0=A or 1=B)";
-      g16_pkey_destroy(k);
       return G16_EINVAL;
     }
     vrow[e] = 2 * row + matrix;
   }
   k->ncoeffs = cs.count;
-  TRY(g16_spmat_create(ctx, 2, (uint32_t)n, cs.count, vrow.data(), 4, (const uint32_t*)(cs.count ? cs.base + 8 : nullptr),
-                       cs.stride, cs.count ? cs.base + cs.value_off : nullptr, cs.stride, &k->abc, cs.values_r2));
-#undef TRY
-  *out = k;
+  if ((rc = g16_spmat_create(ctx, 2, (uint32_t)n, cs.count, vrow.data(), 4, (const uint32_t*)(cs.count ? cs.base + 8 : nullptr),
+                             cs.stride, cs.count ? cs.base + cs.value_off : nullptr, cs.stride, &k->abc, cs.values_r2)))
+    return rc;
+  *out = k.release();
   return G16_OK;
 }
 
@@ -318,7 +304,7 @@ extern "C" int32_t g16_build_abc(g16_ctx* ctx, const g16_pkey* k, const void* wi
   const size_t n = size_t(1) << k->log2n;
   int32_t rc;
   if ((rc = ensure(ctx, ctx->prove, ((size_t)k->nvars + 4 * n) * 32))) return rc;
-  u256* d_w = (u256*)ctx->prove.p;
+  u256* d_w = (u256*)ctx->prove.p();
   u256* d_abc = d_w + k->nvars;
   HIPCHK(ctx, hipMemcpyAsync(d_w, witness, (size_t)k->nvars * 32, hipMemcpyHostToDevice, ctx->stream));
   if ((rc = build_abc_device(ctx, k, d_w, (flags & G16_SCALARS_MONT) ? 1u : 0u, d_abc))) return rc;
@@ -360,10 +346,10 @@ static int32_t prove_bufs(g16_ctx* ctx, const g16_pkey* k, ProveBufs& b) {
   int32_t rc;
   if ((rc = ensure(ctx, ctx->prove, ((size_t)k->nvars + 4 * n) * 32))) return rc;
   if ((rc = ensure(ctx, ctx->stage_o, 2048))) return rc;
-  b.d_w = (u256*)ctx->prove.p;
+  b.d_w = (u256*)ctx->prove.p();
   b.d_abc = b.d_w + k->nvars;
   b.d_qs = b.d_abc + 3 * n;
-  b.slots = (char*)ctx->stage_o.p;
+  b.slots = (char*)ctx->stage_o.p();
   return G16_OK;
 }
 
@@ -373,7 +359,7 @@ static int32_t upload_witness(g16_ctx* ctx, const g16_pkey* k, const void* witne
                              (flags & G16_SCALARS_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
                              ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(b.slots, 0, PART_BYTES, ctx->stream));   // empty range -> XYZZ infinity (all zero)
-  HIPCHK(ctx, hipEventRecord(ctx->ev_a, ctx->stream));                // witness resident
+  HIPCHK(ctx, hipEventRecord(ctx->ev[g16_ctx::EV_A].get(), ctx->stream));                // witness resident
   return G16_OK;
 }
 
@@ -410,18 +396,18 @@ static int32_t launch_witness_sorts(g16_ctx* ctx, const g16_pkey* k, uint32_t fl
   ProveBufs b;
   if ((rc = prove_bufs(ctx, k, b))) return rc;
   const u256* d_wr = b.d_w + k->w_lo;
-  HIPCHK(ctx, hipStreamWaitEvent(L[0].stream, ctx->ev_a, 0));
+  HIPCHK(ctx, hipStreamWaitEvent(L[0].stream.get(), ctx->ev[g16_ctx::EV_A].get(), 0));
   for (auto& srt : ctx->sort) srt.narrow_tail = true;   // proofs overlap their MSM tails with other work (msm_stage.cuh)
-  if ((rc = g16_msm_sort(ctx, L[0].stream, d_wr, wflags, nw, k->A1->cfg(), ctx->sort[0]))) return rc;
+  if ((rc = g16_msm_sort(ctx, L[0].stream.get(), d_wr, wflags, nw, k->A1->cfg(), ctx->sort[0]))) return rc;
   if (k->liveA)   // A1 with many (0,0) points: its own arrangement, behind the shared one
-    if ((rc = g16_msm_sort(ctx, L[0].stream, d_wr, wflags, nw, k->A1->cfg(), ctx->sort[2], k->liveA))) return rc;
-  HIPCHK(ctx, hipEventRecord(ctx->ev_b, L[0].stream));
+    if ((rc = g16_msm_sort(ctx, L[0].stream.get(), d_wr, wflags, nw, k->A1->cfg(), ctx->sort[2], k->liveA))) return rc;
+  HIPCHK(ctx, hipEventRecord(ctx->ev[g16_ctx::EV_B].get(), L[0].stream.get()));
   // B1 / B2 with many (0,0) points: their own arrangement of the witness (live pairs only), built on B2's lane
   // while lane 0 arranges the full witness
   if (k->liveB) {
-    HIPCHK(ctx, hipStreamWaitEvent(L[1].stream, ctx->ev_a, 0));
-    if ((rc = g16_msm_sort(ctx, L[1].stream, d_wr, wflags, nw, k->B2->cfg(), ctx->sort[3], k->liveB))) return rc;
-    HIPCHK(ctx, hipEventRecord(ctx->ev_b2, L[1].stream));
+    HIPCHK(ctx, hipStreamWaitEvent(L[1].stream.get(), ctx->ev[g16_ctx::EV_A].get(), 0));
+    if ((rc = g16_msm_sort(ctx, L[1].stream.get(), d_wr, wflags, nw, k->B2->cfg(), ctx->sort[3], k->liveB.get()))) return rc;
+    HIPCHK(ctx, hipEventRecord(ctx->ev[g16_ctx::EV_B2].get(), L[1].stream.get()));
   }
   return G16_OK;
 }
@@ -441,35 +427,35 @@ static int32_t launch_witness_msms(g16_ctx* ctx, const g16_pkey* k, const ProveB
   const g16_ctx::MsmSort* sortA = k->liveA ? &ctx->sort[2] : &ctx->sort[0];
   const g16_ctx::MsmSort* sortB = k->liveB ? &ctx->sort[3] : &ctx->sort[0];
   // workspaces: the accumulate buffers of lanes 1, 0, 2, 3 serve B2, A1, B1, C1 in every mode
-  const g16_msm_run runB2{sortB, &L[1].acc, k->B2->d_tables, nullptr, b.slots + PART_B2, nullptr};
-  g16_msm_run runs[3] = {{sortA, &L[0].acc, k->A1->d_tables, nullptr, b.slots + PART_A, nullptr},
-                         {sortB, &L[2].acc, k->B1->d_tables, nullptr, b.slots + PART_B1, nullptr},
-                         {&ctx->sort[0], &L[3].acc, k->C1->d_tables, nullptr, b.slots + PART_C, nullptr}};
+  const g16_msm_run runB2{sortB, &L[1].acc, k->B2->d_tables.get(), nullptr, b.slots + PART_B2, nullptr};
+  g16_msm_run runs[3] = {{sortA, &L[0].acc, k->A1->d_tables.get(), nullptr, b.slots + PART_A, nullptr},
+                         {sortB, &L[2].acc, k->B1->d_tables.get(), nullptr, b.slots + PART_B1, nullptr},
+                         {&ctx->sort[0], &L[3].acc, k->C1->d_tables.get(), nullptr, b.slots + PART_C, nullptr}};
   for (int i = 1; i < nlanes; ++i)   // (lane 1 sorted for itself when B is sparse)
-    HIPCHK(ctx, hipStreamWaitEvent(L[i].stream, i == 1 && k->liveB ? ctx->ev_b2 : ctx->ev_b, 0));
-  if (k->liveB) HIPCHK(ctx, hipStreamWaitEvent(L[lb].stream, ctx->ev_b2, 0));
-  if (k->liveA && la != 0) HIPCHK(ctx, hipStreamWaitEvent(L[la].stream, ctx->ev_b, 0));
+    HIPCHK(ctx, hipStreamWaitEvent(L[i].stream.get(), i == 1 && k->liveB ? ctx->ev[g16_ctx::EV_B2].get() : ctx->ev[g16_ctx::EV_B].get(), 0));
+  if (k->liveB) HIPCHK(ctx, hipStreamWaitEvent(L[lb].stream.get(), ctx->ev[g16_ctx::EV_B2].get(), 0));
+  if (k->liveA && la != 0) HIPCHK(ctx, hipStreamWaitEvent(L[la].stream.get(), ctx->ev[g16_ctx::EV_B].get(), 0));
   if (after)
-    for (int i = 0; i < nlanes; ++i) HIPCHK(ctx, hipStreamWaitEvent(L[i].stream, after, 0));
+    for (int i = 0; i < nlanes; ++i) HIPCHK(ctx, hipStreamWaitEvent(L[i].stream.get(), after, 0));
   // Small witness ranges (the shards of a proof spread over GPUs): the four accumulations together do not fill the
   // GPU, every kernel is a latency chain and B2's -- G2 additions, ~4 x the wave time of G1's -- is the longest: its
   // accumulation goes first, next to C1's only (the H accumulation continues C1's bucket sums: the second longest
   // chain); A1 and B1 then run under B2's reduce / fold tail.
   const bool g2_first = g16_env().g2_first >= 0 ? g16_env().g2_first != 0 : nw <= G2_FIRST_MAX;
-  if ((rc = g16_msm_batch(ctx, L[1].stream, 2, &runB2, 1, 1, g2_first ? ctx->ev_g2 : nullptr))) return rc;
+  if ((rc = g16_msm_batch(ctx, L[1].stream.get(), 2, &runB2, 1, 1, g2_first ? ctx->ev[g16_ctx::EV_G2].get() : nullptr))) return rc;
   if (g2_first) {
-    HIPCHK(ctx, hipStreamWaitEvent(L[la].stream, ctx->ev_g2, 0));
-    HIPCHK(ctx, hipStreamWaitEvent(L[lb].stream, ctx->ev_g2, 0));
-    if (!chain || g16_env().g2_first == 2) HIPCHK(ctx, hipStreamWaitEvent(L[lc].stream, ctx->ev_g2, 0));
+    HIPCHK(ctx, hipStreamWaitEvent(L[la].stream.get(), ctx->ev[g16_ctx::EV_G2].get(), 0));
+    HIPCHK(ctx, hipStreamWaitEvent(L[lb].stream.get(), ctx->ev[g16_ctx::EV_G2].get(), 0));
+    if (!chain || g16_env().g2_first == 2) HIPCHK(ctx, hipStreamWaitEvent(L[lc].stream.get(), ctx->ev[g16_ctx::EV_G2].get(), 0));
   }
   if (batch) {
-    if ((rc = g16_msm_batch(ctx, L[0].stream, 1, runs, 3, chain ? 2 : 3, chain ? ctx->ev_c : nullptr))) return rc;
+    if ((rc = g16_msm_batch(ctx, L[0].stream.get(), 1, runs, 3, chain ? 2 : 3, chain ? ctx->ev[g16_ctx::EV_C].get() : nullptr))) return rc;
   } else {
-    if ((rc = g16_msm_batch(ctx, L[la].stream, 1, &runs[0], 1, 1, nullptr))) return rc;
-    if ((rc = g16_msm_batch(ctx, L[lb].stream, 1, &runs[1], 1, 1, nullptr))) return rc;
-    if ((rc = g16_msm_batch(ctx, L[lc].stream, 1, &runs[2], 1, chain ? 0 : 1, chain ? ctx->ev_c : nullptr))) return rc;
+    if ((rc = g16_msm_batch(ctx, L[la].stream.get(), 1, &runs[0], 1, 1, nullptr))) return rc;
+    if ((rc = g16_msm_batch(ctx, L[lb].stream.get(), 1, &runs[1], 1, 1, nullptr))) return rc;
+    if ((rc = g16_msm_batch(ctx, L[lc].stream.get(), 1, &runs[2], 1, chain ? 0 : 1, chain ? ctx->ev[g16_ctx::EV_C].get() : nullptr))) return rc;
   }
-  for (int i = 0; i < nlanes; ++i) HIPCHK(ctx, hipEventRecord(L[i].done, L[i].stream));
+  for (int i = 0; i < nlanes; ++i) HIPCHK(ctx, hipEventRecord(L[i].done.get(), L[i].stream.get()));
   return G16_OK;
 }
 
@@ -489,24 +475,24 @@ static int32_t launch_h_and_collect(g16_ctx* ctx, const g16_pkey* k, const u256*
   if (nh) {
     if (!sorted && (rc = launch_h_sort(ctx, k, d_qs_slice))) return rc;
     const bool chain = chain_c_into_h(k);
-    const g16_msm_run run{&ctx->sort[1], &ctx->lane[4].acc, k->H1->d_tables, nullptr, b.slots + PART_H,
+    const g16_msm_run run{&ctx->sort[1], &ctx->lane[4].acc, k->H1->d_tables.get(), nullptr, b.slots + PART_H,
                           chain ? g16_msm_partial_ptr(ctx->lane[3].acc) : nullptr};
     // G16_CU_SPLIT: the main stream owns a few CUs per XCD only; the H accumulation then runs on the spare lane (the
     // large partition), ordered behind the H sort and joined again below
-    hipStream_t HS = g16_env().cu_split ? ctx->lane[4].stream : M;
+    hipStream_t HS = g16_env().cu_split ? ctx->lane[4].stream.get() : M;
     if (HS != M) {
-      HIPCHK(ctx, hipEventRecord(ctx->ev_q, M));
-      HIPCHK(ctx, hipStreamWaitEvent(HS, ctx->ev_q, 0));
+      HIPCHK(ctx, hipEventRecord(ctx->ev[g16_ctx::EV_Q].get(), M));
+      HIPCHK(ctx, hipStreamWaitEvent(HS, ctx->ev[g16_ctx::EV_Q].get(), 0));
     }
-    if (chain) HIPCHK(ctx, hipStreamWaitEvent(HS, ctx->ev_c, 0));   // C1's bucket sums are final
+    if (chain) HIPCHK(ctx, hipStreamWaitEvent(HS, ctx->ev[g16_ctx::EV_C].get(), 0));   // C1's bucket sums are final
     if ((rc = g16_msm_batch(ctx, HS, 1, &run, 1, 1, nullptr))) return rc;
     if (HS != M) {
-      HIPCHK(ctx, hipEventRecord(ctx->lane[4].done, HS));
-      HIPCHK(ctx, hipStreamWaitEvent(M, ctx->lane[4].done, 0));
+      HIPCHK(ctx, hipEventRecord(ctx->lane[4].done.get(), HS));
+      HIPCHK(ctx, hipStreamWaitEvent(M, ctx->lane[4].done.get(), 0));
     }
   }
   if (nw)
-    for (int i = 0; i < nlanes; ++i) HIPCHK(ctx, hipStreamWaitEvent(M, ctx->lane[i].done, 0));
+    for (int i = 0; i < nlanes; ++i) HIPCHK(ctx, hipStreamWaitEvent(M, ctx->lane[i].done.get(), 0));
   HIPCHK(ctx, hipMemcpyAsync(out_partials, b.slots, PART_BYTES,
                              (flags & G16_OUT_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
   // G16_NO_HOST_SYNC (device output only): the record is complete in stream order; the caller's next operation on
@@ -547,8 +533,8 @@ static int32_t prove_partials_impl(g16_ctx* ctx, const g16_pkey* k, const void* 
   if ((rc = launch_h_sort(ctx, k, b.d_qs + k->h_lo))) return rc;
   hipEvent_t after = nullptr;
   if (g16_env().lanes_after_quotient) {
-    HIPCHK(ctx, hipEventRecord(ctx->ev_q, ctx->stream));
-    after = ctx->ev_q;
+    HIPCHK(ctx, hipEventRecord(ctx->ev[g16_ctx::EV_Q].get(), ctx->stream));
+    after = ctx->ev[g16_ctx::EV_Q].get();
   }
   if ((rc = launch_witness_sorts(ctx, k, flags))) return rc;
   if ((rc = launch_witness_msms(ctx, k, b, after))) return rc;
@@ -590,15 +576,13 @@ extern "C" int32_t g16_prove_partials_begin(g16_ctx* ctx, const g16_pkey* k, con
   }
   hipEvent_t after = nullptr;
   if (!rc && task_mask && g16_env().quotient_first && g16_env().lanes_after_quotient) {
-    if (hipEventRecord(ctx->ev_q, ctx->stream) != hipSuccess) rc = G16_EHIP;
-    after = ctx->ev_q;
+    rc = g16_hip_check(ctx->err, "hipEventRecord(ev_q)", hipEventRecord(ctx->ev[g16_ctx::EV_Q].get(), ctx->stream));
+    after = ctx->ev[g16_ctx::EV_Q].get();
   }
   if (!rc) rc = launch_witness_sorts(ctx, k, flags);
   if (!rc) rc = launch_witness_msms(ctx, k, b, after);
-  if (!rc && !(flags & G16_NO_HOST_SYNC) && hipStreamSynchronize(ctx->stream) != hipSuccess) {   // the task outputs are complete; the lanes run on
-    ctx->err = "hipStreamSynchronize failed";
-    rc = G16_EHIP;
-  }
+  if (!rc && !(flags & G16_NO_HOST_SYNC))   // the task outputs are complete; the lanes run on
+    rc = g16_hip_check(ctx->err, "hipStreamSynchronize", hipStreamSynchronize(ctx->stream));
   if (rc != G16_OK) {
     ctx_quiesce(ctx);
     return rc;
@@ -672,11 +656,11 @@ int32_t g16_combine_enqueue(g16_ctx* ctx, const g16_pkey* k, const void* partial
   int32_t rc;
   if ((rc = ensure(ctx, ctx->stage_p, count * PART_BYTES))) return rc;
   if ((rc = ensure(ctx, ctx->stage_o, 2048))) return rc;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->stage_p.p, partials, count * PART_BYTES,
+  HIPCHK(ctx, hipMemcpyAsync(ctx->stage_p.p(), partials, count * PART_BYTES,
                              (flags & G16_SCALARS_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
                              ctx->stream));
-  unsigned char* d_res = (unsigned char*)ctx->stage_o.p + 1024;
-  KLAUNCH(ctx, "prove_combine", prove_combine_kernel, 5, 64, 0, (const unsigned char*)ctx->stage_p.p, (uint32_t)count,
+  unsigned char* d_res = (unsigned char*)ctx->stage_o.p() + 1024;
+  KLAUNCH(ctx, "prove_combine", prove_combine_kernel, 5, 64, 0, (const unsigned char*)ctx->stage_p.p(), (uint32_t)count,
           d_res);
 
   // Everything that depends on the mask and the key alone is computed while the GPU works -- in g16_prove that is the
@@ -751,7 +735,7 @@ extern "C" int32_t g16_prove(g16_ctx* ctx, const g16_pkey* k, const void* witnes
   if ((rc = ensure(ctx, ctx->stage_o, 2048))) return rc;
   if ((rc = ensure(ctx, ctx->stage_s, PART_BYTES))) return rc;
   // partials stay in HBM (stage_s is free again once the witness has been copied into the prove buffer)
-  unsigned char* d_part = (unsigned char*)ctx->stage_s.p;
+  unsigned char* d_part = (unsigned char*)ctx->stage_s.p();
   // no host wait here: the combine's copy and kernel are ordered behind the record on the main stream, and its
   // mask-only host arithmetic (~0.3 ms) then overlaps the whole proof instead of following it
   if ((rc = g16_prove_partials(ctx, k, witness, flags | G16_OUT_DEVICE | G16_NO_HOST_SYNC, d_part))) return rc;
@@ -772,7 +756,7 @@ extern "C" int32_t g16_quotient(g16_ctx* ctx, const void* Az, const void* Bz, co
   const size_t n = size_t(1) << log2n;
   int32_t rc;
   if ((rc = ensure(ctx, ctx->prove, 4 * n * 32))) return rc;
-  u256* d = (u256*)ctx->prove.p;
+  u256* d = (u256*)ctx->prove.p();
   HIPCHK(ctx, hipMemcpyAsync(d, Az, n * 32, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(d + n, Bz, n * 32, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(d + 2 * n, Cz, n * 32, hipMemcpyHostToDevice, ctx->stream));

@@ -154,17 +154,15 @@ struct g16_spmat {
   int device = 0;
   uint32_t nmat = 1, nrows = 0;
   size_t nnz = 0, ndict = 0;   // ndict > 0: d_val holds the dictionary, d_vidx the per-entry indices
-  uint32_t *d_ptr = nullptr, *d_col = nullptr, *d_vidx = nullptr, *d_rows = nullptr;
-  u256* d_val = nullptr;
-  u256* d_val2 = nullptr;      // dictionary only: the values times R (for standard-form x: the sum is Montgomery)
+  DevMem<uint32_t> d_ptr, d_col, d_vidx, d_rows;
+  DevMem<u256> d_val;
+  DevMem<u256> d_val2;         // dictionary only: the values times R (for standard-form x: the sum is Montgomery)
   SpmvBins bins;
 };
 
 void g16_spmat_destroy(g16_spmat* m) {
   if (!m) return;
   (void)hipSetDevice(m->device);
-  for (void* p : {(void*)m->d_ptr, (void*)m->d_col, (void*)m->d_vidx, (void*)m->d_rows, (void*)m->d_val, (void*)m->d_val2})
-    if (p) (void)hipFree(p);
   delete m;
 }
 
@@ -178,6 +176,13 @@ void g16_spmat_info(const g16_spmat* m, size_t out[1 + 9]) {
 static int32_t spmat_create(g16_ctx* ctx, uint32_t nmat, uint32_t nrows, size_t nnz, const uint32_t* vrow,
                             size_t vrow_stride, const uint32_t* col, size_t col_stride, const void* val_base,
                             size_t val_stride, g16_spmat** out, bool values_r2);
+// a device array of the matrix with its contents (an empty one still gets an address)
+template <class T>
+static int32_t upload(g16_ctx* ctx, DevMem<T>& dst, const void* src, size_t bytes) {
+  HIPCHK(ctx, dev_alloc(dst, bytes ? bytes : 4));
+  if (bytes) HIPCHK(ctx, hipMemcpy(dst.get(), src, bytes, hipMemcpyHostToDevice));
+  return G16_OK;
+}
 // values_r2: the 32-byte values are c R^2 (the double-Montgomery form of a .zkey's section 4) instead of c R
 int32_t g16_spmat_create(g16_ctx* ctx, uint32_t nmat, uint32_t nrows, size_t nnz, const uint32_t* vrow,
                          size_t vrow_stride, const uint32_t* col, size_t col_stride, const void* val_base,
@@ -248,7 +253,7 @@ static int32_t spmat_create(g16_ctx* ctx, uint32_t nmat, uint32_t nrows, size_t 
   // bins by the length of a virtual row
   std::vector<uint8_t> bin(nv ? nv : 1);
   std::vector<uint32_t> rows(nv ? nv : 1);
-  g16_spmat* m = new (std::nothrow) g16_spmat();   // (no allocation that can throw follows)
+  Building<g16_spmat, g16_spmat_destroy> m(new (std::nothrow) g16_spmat());   // (no allocation that can throw follows)
   if (!m) return G16_ENOMEM;
   m->device = ctx->device;
   m->nmat = nmat, m->nrows = nrows, m->nnz = nnz, m->ndict = dict ? vals.size() : 0;
@@ -269,55 +274,37 @@ static int32_t spmat_create(g16_ctx* ctx, uint32_t nmat, uint32_t nrows, size_t 
     for (int b = 0; b < NBINS; ++b) cur[b] = m->bins.row_off[b];
     for (size_t v = 0; v < nv; ++v) rows[cur[bin[v]]++] = (uint32_t)v;
   }
-  auto up = [&](void** dst, const void* src, size_t bytes) -> int32_t {
-    if (hipMalloc(dst, bytes ? bytes : 4) != hipSuccess) {
-      ctx->err = "hipMalloc(sparse matrix) failed";
-      return G16_ENOMEM;
-    }
-    if (bytes && hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) != hipSuccess) {
-      ctx->err = "hipMemcpy(sparse matrix) failed";
-      return G16_EHIP;
-    }
-    return G16_OK;
-  };
-  int32_t rc = up((void**)&m->d_ptr, ptr.data(), ptr.size() * 4);
-  if (!rc) rc = up((void**)&m->d_col, cols.data(), nnz * 4);
-  if (!rc) rc = up((void**)&m->d_val, vals.data(), (dict ? vals.size() : nnz) * 32);
-  if (!rc && dict) rc = up((void**)&m->d_vidx, vidx.data(), nnz * 4);
+  int32_t rc;
+  if ((rc = upload(ctx, m->d_ptr, ptr.data(), ptr.size() * 4))) return rc;
+  if ((rc = upload(ctx, m->d_col, cols.data(), nnz * 4))) return rc;
+  if ((rc = upload(ctx, m->d_val, vals.data(), (dict ? vals.size() : nnz) * 32))) return rc;
+  if (dict && (rc = upload(ctx, m->d_vidx, vidx.data(), nnz * 4))) return rc;
   // d_val holds what the host handed over: c R, or (values_r2) c R^2.  The kernel wants c R in d_val and, with a
   // dictionary, c R^2 in d_val2: one small launch rescales in the direction that is missing.
   const size_t nvals = dict ? vals.size() : nnz;
-  auto rescale = [&](const u256* in, u256* o, uint32_t divide) {
-    if (!nvals) return;
+  auto rescale = [&](const u256* in, u256* o, uint32_t divide) -> int32_t {
+    if (!nvals) return G16_OK;
     hipLaunchKernelGGL(values_rescale, dim3((uint32_t)((nvals + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, ctx->stream, in, o,
                        nvals, divide);
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) {
-      ctx->err = "coefficient rescaling failed";
-      rc = G16_EHIP;
-    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return G16_OK;
   };
-  if (!rc && dict) {
-    if (hipMalloc((void**)&m->d_val2, vals.size() * 32) != hipSuccess) {
-      ctx->err = "hipMalloc(sparse matrix) failed";
-      rc = G16_ENOMEM;
-    } else if (values_r2) {   // the file's bytes ARE the second table
+  if (dict) {
+    HIPCHK(ctx, dev_alloc(m->d_val2, vals.size() * 32));
+    if (values_r2) {   // the file's bytes ARE the second table
       // on the stream of the rescaling kernel that reads it: a device-to-device hipMemcpy may return before the copy
       // is done, and the null stream does not order work on the (non-blocking) context stream
-      if (hipMemcpyAsync(m->d_val2, m->d_val, vals.size() * 32, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
-        rc = G16_EHIP;
-      if (!rc) rescale(m->d_val2, m->d_val, 1);
+      HIPCHK(ctx, hipMemcpyAsync(m->d_val2.get(), m->d_val.get(), vals.size() * 32, hipMemcpyDeviceToDevice, ctx->stream));
+      rc = rescale(m->d_val2.get(), m->d_val.get(), 1);
     } else {
-      rescale(m->d_val, m->d_val2, 0);
+      rc = rescale(m->d_val.get(), m->d_val2.get(), 0);
     }
-  } else if (!rc && values_r2) {
-    rescale(m->d_val, m->d_val, 1);   // plain values: c R^2 -> c R in place
+  } else if (values_r2) {
+    rc = rescale(m->d_val.get(), m->d_val.get(), 1);   // plain values: c R^2 -> c R in place
   }
-  if (!rc) rc = up((void**)&m->d_rows, rows.data(), nv * 4);
-  if (rc) {
-    g16_spmat_destroy(m);
-    return rc;
-  }
-  *out = m;
+  if (rc) return rc;
+  if ((rc = upload(ctx, m->d_rows, rows.data(), nv * 4))) return rc;
+  *out = m.release();
   return G16_OK;
 }
 
@@ -327,11 +314,11 @@ int32_t g16_spmat_apply(g16_ctx* ctx, const g16_spmat* m, const void* d_x, uint3
   const uint32_t nblk = m->bins.blk_off[NBINS];
   if (!nblk) return G16_OK;
   // standard-form x: the dictionary's second table (v R) makes the sums Montgomery; plain values leave them standard
-  const u256* val = (m->ndict && !x_mont) ? m->d_val2 : m->d_val;
+  const u256* val = (m->ndict && !x_mont) ? m->d_val2.get() : m->d_val.get();
   const bool sums_mont = x_mont || m->ndict;
 #define SPMV_LAUNCH(NM, DI)                                                                                          \
-  KLAUNCH(ctx, NM == 2 ? "abc_spmv" : "spmv", (spmv_binned<NM, DI>), nblk, BLOCK, 0, m->bins, m->d_ptr, m->d_col,     \
-          val, m->d_vidx, (const u256*)d_x, m->d_rows, m->nrows, (u256*)d_out)
+  KLAUNCH(ctx, NM == 2 ? "abc_spmv" : "spmv", (spmv_binned<NM, DI>), nblk, BLOCK, 0, m->bins, m->d_ptr.get(),         \
+          m->d_col.get(), val, m->d_vidx.get(), (const u256*)d_x, m->d_rows.get(), m->nrows, (u256*)d_out)
   if (m->nmat == 2) {
     if (m->ndict) SPMV_LAUNCH(2, true);
     else SPMV_LAUNCH(2, false);
@@ -363,30 +350,19 @@ extern "C" int32_t g16_spmv_fr(g16_ctx* ctx, const uint32_t* row, const uint32_t
     }
   if (!nrows) return G16_OK;
   CTX_ENTER(ctx);
-  g16_spmat* m = nullptr;
-  int32_t rc = g16_spmat_create(ctx, 1, (uint32_t)nrows, nnz, row, 4, col, 4, val, 32, &m);
+  // released in reverse order: the stream is drained first, then d_y, d_x and the matrix go
+  Building<g16_spmat, g16_spmat_destroy> m;
+  DevMem<> d_x, d_y;
+  SyncOnExit sync{ctx->stream};
+  g16_spmat* built = nullptr;
+  int32_t rc = g16_spmat_create(ctx, 1, (uint32_t)nrows, nnz, row, 4, col, 4, val, 32, &built);
   if (rc) return rc;
-  void *d_x = nullptr, *d_y = nullptr;
-  auto done = [&](int32_t code) {
-    (void)hipStreamSynchronize(ctx->stream);
-    if (d_x) (void)hipFree(d_x);
-    if (d_y) (void)hipFree(d_y);
-    g16_spmat_destroy(m);
-    return code;
-  };
-  if (hipMalloc(&d_x, (ncols ? ncols : 1) * 32) != hipSuccess || hipMalloc(&d_y, nrows * 32) != hipSuccess) {
-    ctx->err = "hipMalloc(spmv vectors) failed";
-    return done(G16_ENOMEM);
-  }
-  if (ncols && hipMemcpyAsync(d_x, x, ncols * 32, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-    ctx->err = "hipMemcpy(x) failed";
-    return done(G16_EHIP);
-  }
-  if ((rc = g16_spmat_apply(ctx, m, d_x, 1, d_y))) return done(rc);
-  if (hipMemcpyAsync(y, d_y, nrows * 32, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-      hipStreamSynchronize(ctx->stream) != hipSuccess) {
-    ctx->err = "spmv: copy back failed";
-    return done(G16_EHIP);
-  }
-  return done(G16_OK);
+  m.reset(built);
+  HIPCHK(ctx, dev_alloc(d_x, (ncols ? ncols : 1) * 32));
+  HIPCHK(ctx, dev_alloc(d_y, nrows * 32));
+  if (ncols) HIPCHK(ctx, hipMemcpyAsync(d_x.get(), x, ncols * 32, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = g16_spmat_apply(ctx, m.get(), d_x.get(), 1, d_y.get()))) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(y, d_y.get(), nrows * 32, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return G16_OK;
 }
