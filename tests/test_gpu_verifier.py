@@ -27,6 +27,9 @@ def test_pairing_vs_oracle_and_bilinear(ctx):
     raw = ctx.pairing(b"".join(o.g1_to_bytes(p) for p in Ps), b"".join(o.g2_to_bytes(q) for q in Qs))
     gts = [_gt(raw[384 * i:384 * i + 384]) for i in range(len(Ps))]
     assert gts[0] == o.pairing(Ps[0], Qs[0])                 # bit-exact incl. the final exponentiation
+    for i, (p, q) in enumerate(zip(Ps, Qs)):                  # ... and every other finite pairing of the batch
+        if p != o.INF_G1 and q != o.INF_G2:
+            assert gts[i] == o.pairing(p, q), i
     assert gts[3] == o._f12_one() and gts[4] == o._f12_one()  # infinity on either side
     assert gts[5] == gts[0]                                   # e(aP, bQ) == e(abP, Q)
     assert gts[1] != gts[2] and gts[1] != o._f12_one()
@@ -94,6 +97,44 @@ def test_verify_rejects_malformed_points(ctx):
     assert dev.verify([(rogue.pi_a, rogue.pi_b, rogue.pi_c)], rogue.publicIO) == [0]
     assert dev.verify([(rogue.pi_a, rogue.pi_b, rogue.pi_c)], rogue.publicIO, subgroup=True) == [-4]
     assert dev.verify([], b"") == []
+
+
+def test_verify_batch_of_mixed_outcomes_across_block_boundaries(ctx):
+    """131 proofs in one g16_verify call: three Miller values per proof, so the kernels' t / 3 indexing crosses two
+    64-lane block boundaries; every status code in one batch, each at its own index; of two defects the smallest
+    code wins"""
+    import dataclasses
+    from nim_groth16_amd import extractVKey, loadVerifyingKey
+    zk, (good, other) = _toy(ctx)
+    dev = loadVerifyingKey(extractVKey(zk), ctx)
+    off_g1 = o.fp_to_mont_bytes(5) + o.fp_to_mont_bytes(7)             # not on y^2 = x^3 + 3
+    off_g2 = bytes(good.pi_b[:64]) + bytes(64)
+    x = (3, 1)
+    while True:                                                        # on the twist, outside the order-r subgroup
+        y = _fp2_sqrt(o.fp2_add(o.fp2_mul(o.fp2_sqr(x), x), o.TWIST_B))
+        if y is not None and not o.G2.is_inf(o.G2.mul(o.R, (x, y))):
+            break
+        x = (x[0] + 1, x[1])
+    ax = int.from_bytes(good.pi_a[:32], "little")
+    noncanon_a = (ax + o.P).to_bytes(32, "little") + bytes(good.pi_a[32:])      # the same residue, limbs >= p
+    pub = bytes(good.publicIO)
+    noncanon_pub = pub[:32] + (int.from_bytes(pub[32:64], "little") + o.R).to_bytes(32, "little") + pub[64:]
+    rep = dataclasses.replace
+    kinds = [(good, 1), (other, 1), (rep(good, pi_c=other.pi_c), 0), (rep(good, pi_a=off_g1), -1),
+             (rep(good, pi_b=off_g2), -2), (rep(good, pi_c=off_g1), -3), (rep(good, pi_b=o.g2_to_bytes((x, y))), -4),
+             (rep(good, pi_a=noncanon_a), -5), (rep(good, publicIO=noncanon_pub), -6),
+             (rep(good, pi_a=off_g1, pi_c=off_g1), -3),                                  # two defects: -1 and -3
+             (rep(good, pi_a=off_g1, publicIO=noncanon_pub), -6),                        # -1 and -6
+             (rep(good, pi_b=off_g2, pi_a=noncanon_a), -5)]                              # -2 and -5
+    n = 131
+    batch = [kinds[(5 * i + i // len(kinds)) % len(kinds)] for i in range(n)]
+    assert {e for _, e in batch} == {1, 0, -1, -2, -3, -4, -5, -6}
+    st = dev.verify([(p.pi_a, p.pi_b, p.pi_c) for p, _ in batch], b"".join(bytes(p.publicIO) for p, _ in batch),
+                    mont=True, subgroup=True)
+    assert st == [e for _, e in batch], [(i, s, e) for i, (s, (_, e)) in enumerate(zip(st, batch)) if s != e]
+    # alone, each kind gives the same answer as in the batch
+    for p, e in kinds:
+        assert dev.verify([(p.pi_a, p.pi_b, p.pi_c)], bytes(p.publicIO), mont=True, subgroup=True) == [e]
 
 
 def _fp2_sqrt(a):
