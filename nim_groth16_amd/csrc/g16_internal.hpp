@@ -86,7 +86,7 @@ struct g16_ctx {
   struct MsmSort {
     Buf buf;
     g16::MsmParams P;
-    bool narrow_tail = false;   // reduce2 geometry: see stage_reduce2_fold (set by the prover's lanes: throughput)
+    bool narrow_tail = false;   // reduce2 geometry: see stage_reduce2_fold, msm_stage.cuh (set by the prover's lanes: throughput)
     uint32_t *count = nullptr, *cursor = nullptr, *offset = nullptr, *xoff = nullptr, *heavy = nullptr,
              *info = nullptr, *entries = nullptr, *perm = nullptr, *ghist = nullptr, *blk_base = nullptr, *tile_hist = nullptr;
     uint2* tmp = nullptr;
@@ -233,17 +233,30 @@ struct ProfScope {
   KLAUNCH_ON(ctx, (ctx)->stream, name, kernel, grid, block, shmem, __VA_ARGS__)
 
 
-// implemented in msm_g1.hip / msm_g2.hip / ntt.hip
-// table_c == 0: d_points = n affine points; else g16_points::cfg() and d_points = the tables of that registered set
-int32_t g16_msm_device_g1(g16_ctx* ctx, const void* d_scalars, uint32_t flags, const void* d_points, size_t n,
-                          void* d_out_aff, void* d_out_acc, uint32_t table_c, const uint32_t* d_live = nullptr);
-int32_t g16_msm_device_g2(g16_ctx* ctx, const void* d_scalars, uint32_t flags, const void* d_points, size_t n,
-                          void* d_out_aff, void* d_out_acc, uint32_t table_c, const uint32_t* d_live = nullptr);
-// the live bitmap of a registered set if it holds enough (0,0) points for its own entry lists to pay (G16_INF_COMPACT)
-struct g16_points;
+// ---- MSM: the group-agnostic surface (msm_sort.hip unless noted) -------------------------------------
+// device-resident point set with precomputed window tables.  Immutable after registration and tied to a DEVICE,
+// not to the context that created it: every context of that device may run MSMs against it concurrently (the
+// in-flight proofs of one GPU share one key), and it may be released before or after any context.
+struct g16_points {
+  int device = 0;
+  int group = 1;          // 1: G1 (64-byte points), 2: G2 (128-byte points)
+  size_t n = 0;
+  uint32_t c = 0, nwin = 0;
+  uint32_t mtab = 1;         // multiplier tables per window: 1, or 2 = {1, 2} with the class bucket set (msm.cuh)
+  uint32_t cfg() const { return c | (mtab << 8); }   // the `table_cfg` of g16_msm_sort / msm_device
+  DevMem<> d_tables;         // mtab * nwin * n affine points: [m][w][i] = 2^(c w + m) P_i
+  DevMem<uint32_t> d_live;      // bitmap: bit i set <=> point i is not (0,0); ceil(n/32) words
+  size_t n_inf = 0;             // points at infinity in the set
+};
+// the live bitmap of a registered set if it holds enough (0,0) points for its own entry lists to pay (G16_INF_COMPACT;
+// g16hip.hip)
 const uint32_t* g16_points_live_if_sparse(const g16_points* p);
+// window bits / multiplier tables of a registered set of n points (the cost model of msm_sort.hip)
+uint32_t g16_pick_table_window(size_t n);
+uint32_t g16_pick_mtab(uint32_t c);
 // the two halves of an MSM: (1) arrange one scalar vector into buckets, (2) accumulate + reduce a point set
 // against that arrangement.  Several point sets may share one sort (same scalars, same n, same c).
+// table_c == 0: plain point arrays; else g16_points::cfg() of the registered sets that will run against the sort
 // d_live (optional): bitmap over the n pairs; pairs with a cleared bit get no entries (point sets with (0,0) points)
 int32_t g16_msm_sort(g16_ctx* ctx, hipStream_t stream, const void* d_scalars, uint32_t flags, size_t n,
                      uint32_t table_c, g16_ctx::MsmSort& sort, const uint32_t* d_live = nullptr);
@@ -255,64 +268,64 @@ int32_t g16_msm_sort(g16_ctx* ctx, hipStream_t stream, const void* d_scalars, ui
 struct g16_msm_run {
   const g16_ctx::MsmSort* sort;
   g16_ctx::Buf* acc;            // workspace of this job (bucket sums first: see g16_msm_partial_ptr)
-  const void* d_points;
+  const void* d_points;         // the tables of a registered set, or reduced-radix entries (to29_device)
   void* d_out_aff;              // either may be null
   void* d_out_acc;
   const void* init_partial;
 };
+// `group` (1 / 2) is data to the prover, which walks its MSMs in a table: the one run-time choice of the curve below the C ABI
 int32_t g16_msm_batch(g16_ctx* ctx, hipStream_t stream, int group, const g16_msm_run* runs, int n_accum, int n_tail,
                       hipEvent_t after_heavy);
 inline const void* g16_msm_partial_ptr(const g16_ctx::Buf& acc) { return acc.p(); }
-int32_t g16_msm_reduce_g1(g16_ctx* ctx, hipStream_t stream, g16_ctx::Buf& acc, const g16_ctx::MsmSort& sort,
-                          const void* d_points, void* d_out_aff, void* d_out_acc);
-int32_t g16_msm_reduce_g2(g16_ctx* ctx, hipStream_t stream, g16_ctx::Buf& acc, const g16_ctx::MsmSort& sort,
-                          const void* d_points, void* d_out_aff, void* d_out_acc);
-int32_t g16_lanes_init(g16_ctx* ctx);
+int32_t g16_lanes_init(g16_ctx* ctx);   // g16hip.hip
 int g16_stream_priority(int index);
-// per-curve stages of phase 2, each compiled in its own translation unit (msm_g{1,2}_{accum,reduce1,reduce2}.hip).
-// `batch`: a g16::MsmBatch<G1 / G2> (msm.cuh) of `ny` jobs that share the launch parameters P.
-#define G16_DECL_STAGES(g)                                                                                            \
-  int32_t g16_st_accum_##g(g16_ctx*, hipStream_t, const g16::MsmParams& P, const void* batch, uint32_t ny);           \
-  int32_t g16_st_heavy_##g(g16_ctx*, hipStream_t, const g16::MsmParams& P, const void* batch, uint32_t ny);           \
-  int32_t g16_st_reduce1_##g(g16_ctx*, hipStream_t, const g16::MsmParams& P, const void* batch, uint32_t ny);         \
-  int32_t g16_st_reduce2_##g(g16_ctx*, hipStream_t, const g16::MsmParams& P, bool narrow_tail, const void* batch,     \
-                             uint32_t ny);
-G16_DECL_STAGES(g1)
-G16_DECL_STAGES(g2)
-int32_t g16_to29_device_g1(g16_ctx* ctx, hipStream_t st, const void* d_points, size_t n, void* d_out);
-int32_t g16_to29_device_g2(g16_ctx* ctx, hipStream_t st, const void* d_points, size_t n, void* d_out);
-int32_t g16_precompute_device_g1(g16_ctx* ctx, const void* d_points, size_t n, uint32_t c, uint32_t mtab, void* d_tables);
-int32_t g16_precompute_device_g2(g16_ctx* ctx, const void* d_points, size_t n, uint32_t c, uint32_t mtab, void* d_tables);
-uint32_t g16_pick_window_g1(size_t n);
-uint32_t g16_pick_mtab(uint32_t c);
-int32_t g16_on_curve_device_g1(g16_ctx* ctx, const void* d_points, size_t n, uint32_t* d_first_bad);
-int32_t g16_on_curve_device_g2(g16_ctx* ctx, const void* d_points, size_t n, uint32_t* d_first_bad);
-int32_t g16_fixed_base_device_g1(g16_ctx* ctx, void* d_table, bool ready, const void* d_s, uint32_t mont, size_t n,
-                                 void* d_out);
-int32_t g16_fixed_base_device_g2(g16_ctx* ctx, void* d_table, bool ready, const void* d_s, uint32_t mont, size_t n,
-                                 void* d_out);
-
-// device-resident point set with precomputed window tables.  Immutable after registration and tied to a DEVICE,
-// not to the context that created it: every context of that device may run MSMs against it concurrently (the
-// in-flight proofs of one GPU share one key), and it may be released before or after any context.
-struct g16_points {
-  int device = 0;
-  int group = 1;          // 1: G1 (64-byte points), 2: G2 (128-byte points)
-  size_t n = 0;
-  uint32_t c = 0, nwin = 0;
-  uint32_t mtab = 1;         // multiplier tables per window: 1, or 2 = {1, 2} with the class bucket set (msm.cuh)
-  uint32_t cfg() const { return c | (mtab << 8); }   // the `table_cfg` of g16_msm_sort / g16_msm_device_*
-  DevMem<> d_tables;         // mtab * nwin * n affine points: [m][w][i] = 2^(c w + m) P_i
-  DevMem<uint32_t> d_live;      // bitmap: bit i set <=> point i is not (0,0); ceil(n/32) words
-  size_t n_inf = 0;             // points at infinity in the set
-};
-// *d_n_inf (device u32, zeroed by the caller) += number of (0,0) points; bitmap: ceil(n/32) words
-int32_t g16_live_bitmap_device_g1(g16_ctx* ctx, const void* d_points, size_t n, uint32_t* d_bitmap, uint32_t* d_n_inf);
-int32_t g16_live_bitmap_device_g2(g16_ctx* ctx, const void* d_points, size_t n, uint32_t* d_bitmap, uint32_t* d_n_inf);
+// d_out = d_a | d_b over bitmaps of n bits; *d_n_dead (device u32, zeroed by the caller) += bits clear in
+// the union (msm_g1_misc.hip)
 int32_t g16_bitmap_or_device(g16_ctx* ctx, uint32_t* d_out, const uint32_t* d_a, const uint32_t* d_b, size_t n,
                              uint32_t* d_n_dead);
-int32_t g16_sum_partials_device_g1(g16_ctx* ctx, const void* d_parts, uint32_t count, void* d_out_aff);
-int32_t g16_sum_partials_device_g2(g16_ctx* ctx, const void* d_parts, uint32_t count, void* d_out_aff);
+
+// ---- MSM: per curve, C = g16::G1 / g16::G2 (ec.cuh) ---------------------------------------------------
+// Declarations only.  msm_device is defined in msm_sort.hip; the bodies of the others are in msm_stage.cuh and are
+// explicitly instantiated, with their kernels, in msm_g{1,2}_{accum,reduce1,reduce2,misc}.hip.  A translation unit
+// that includes only this header can call them and instantiates no kernel of its own.
+namespace g16 {
+template <class C>
+struct MsmBatch;   // msm.cuh: up to MSM_BATCH_MAX jobs that share the launch parameters P
+}
+// one complete MSM on the context's main stream
+// table_c == 0: d_points = n affine points; else g16_points::cfg() and d_points = the tables of that registered set
+template <class C>
+int32_t msm_device(g16_ctx* ctx, const void* d_scalars, uint32_t flags, const void* d_points, size_t n, void* d_out_aff,
+                   void* d_out_acc, uint32_t table_c, const uint32_t* d_live = nullptr);
+// the stages of phase 2 over the first `ny` jobs of a batch
+template <class C>
+int32_t stage_accum(g16_ctx* ctx, hipStream_t st, const g16::MsmParams& P, const g16::MsmBatch<C>& B, uint32_t ny);
+template <class C>
+int32_t stage_heavy(g16_ctx* ctx, hipStream_t st, const g16::MsmParams& P, const g16::MsmBatch<C>& B, uint32_t ny);
+template <class C>
+int32_t stage_reduce1(g16_ctx* ctx, hipStream_t st, const g16::MsmParams& P, const g16::MsmBatch<C>& B, uint32_t ny);
+template <class C>
+int32_t stage_reduce2_fold(g16_ctx* ctx, hipStream_t st, const g16::MsmParams& P, bool narrow_tail,
+                           const g16::MsmBatch<C>& B, uint32_t ny);
+// reference-layout points -> reduced-radix entries (one-shot MSMs) / window tables (registered sets)
+template <class C>
+int32_t to29_device(g16_ctx* ctx, hipStream_t st, const void* d_points, size_t n, void* d_out);
+template <class C>
+int32_t precompute_device(g16_ctx* ctx, const void* d_points, size_t n, uint32_t c, uint32_t mtab, void* d_tables);
+// d_out[i] = d_scalars[i] * generator; d_table: 32*255 points, built first unless table_ready
+template <class C>
+int32_t fixed_base_device(g16_ctx* ctx, void* d_table, bool table_ready, const void* d_scalars, uint32_t mont, size_t n,
+                          void* d_out);
+// *d_first_bad (device u32, 0xffffffff on entry) = index of the first point off the curve
+template <class C>
+int32_t on_curve_device(g16_ctx* ctx, const void* d_points, size_t n, uint32_t* d_first_bad);
+// *d_n_inf (device u32, zeroed by the caller) += number of (0,0) points; bitmap: ceil(n/32) words
+template <class C>
+int32_t live_bitmap_device(g16_ctx* ctx, const void* d_points, size_t n, uint32_t* d_bitmap, uint32_t* d_n_inf);
+// sum of `count` XYZZ partials -> affine
+template <class C>
+int32_t sum_partials_device(g16_ctx* ctx, const void* d_parts, uint32_t count, void* d_out_aff);
+
 // row-binned sparse matrices over Fr (spmv.hip): nmat = 2 -> the A and B matrices of a key, apply = buildABC
 struct g16_spmat;
 int32_t g16_spmat_create(g16_ctx* ctx, uint32_t nmat, uint32_t nrows, size_t nnz, const uint32_t* vrow,

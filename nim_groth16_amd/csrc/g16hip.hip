@@ -215,9 +215,14 @@ extern "C" int32_t g16_profile_clock(g16_ctx* ctx, double* ghz) {
   return G16_OK;
 }
 
+// Every entry point below knows its curve C = G1 / G2 from its name and hands it on as a type; where the C ABI or a
+// context array wants the group as a number:
+template <class C>
+constexpr int group_of = sizeof(typename C::Aff) == sizeof(g1_aff) ? 1 : 2;
+
 template <class C>
 static int32_t msm_entry(g16_ctx* ctx, const void* scalars, uint32_t flags, const void* points, size_t n, void* out,
-                         bool on_device, bool partial, const char* tag) {
+                         bool on_device, bool partial) {
   if (!ctx) return G16_EINVAL;
   if (!out || (n > 0 && (!scalars || !points))) {
     ctx->err = "null pointer argument";
@@ -248,17 +253,15 @@ static int32_t msm_entry(g16_ctx* ctx, const void* scalars, uint32_t flags, cons
   if ((rc = ensure(ctx, ctx->stage_o, 512))) return rc;
   auto* d_aff = partial ? nullptr : (typename C::Aff*)ctx->stage_o.p();
   auto* d_acc = partial ? (typename C::Acc*)ctx->stage_o.p() : nullptr;
-  rc = sizeof(typename C::Aff) == 64 ? g16_msm_device_g1(ctx, d_s, flags, d_p, n, d_aff, d_acc, 0)
-                                     : g16_msm_device_g2(ctx, d_s, flags, d_p, n, d_aff, d_acc, 0);
-  if (rc) return rc;
+  if ((rc = msm_device<C>(ctx, d_s, flags, d_p, n, d_aff, d_acc, 0))) return rc;
   HIPCHK(ctx, hipMemcpyAsync(out, ctx->stage_o.p(), out_bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return G16_OK;
 }
 
 // ---- registered point sets (ProverPoints are constant per circuit: zkey_types.nim:36-41) ----------------
-static int32_t points_register(g16_ctx* ctx, int group, const void* points, size_t n, bool on_device,
-                               g16_points** out) {
+template <class C>
+static int32_t points_register(g16_ctx* ctx, const void* points, size_t n, bool on_device, g16_points** out) {
   if (!ctx) return G16_EINVAL;
   if (!out || (n && !points) || n >= (size_t(1) << 26)) {
     ctx->err = "bad argument";
@@ -269,12 +272,12 @@ static int32_t points_register(g16_ctx* ctx, int group, const void* points, size
   Building<g16_points, g16_points_release> h(new (std::nothrow) g16_points());
   if (!h) return G16_ENOMEM;
   h->device = ctx->device;
-  h->group = group;
+  h->group = group_of<C>;
   h->n = n;
-  h->c = g16_pick_window_g1(n);
+  h->c = g16_pick_table_window(n);
   h->nwin = 254 / h->c + 1;
   h->mtab = g16_pick_mtab(h->c);
-  const size_t psz = group == 1 ? 64 : 128;
+  constexpr size_t psz = sizeof(typename C::Aff);
   // Two multiplier tables per window double the set's HBM footprint (~10 GB for a 2^20 key, ~40 GB at 2^22): a set
   // that does not fit that way -- table indices beyond 31 bits, or no room in HBM -- falls back to one table per window
   // and the plain bucket set (the rounds 1-3 layout) instead of failing.
@@ -297,18 +300,14 @@ static int32_t points_register(g16_ctx* ctx, int group, const void* points, size
       HIPCHK(ctx, hipMemcpyAsync(ctx->stage_p.p(), points, n * psz, hipMemcpyHostToDevice, ctx->stream));
       d_src = ctx->stage_p.p();
     }
-    rc = group == 1 ? g16_precompute_device_g1(ctx, d_src, n, h->c, h->mtab, h->d_tables.get())
-                    : g16_precompute_device_g2(ctx, d_src, n, h->c, h->mtab, h->d_tables.get());
-    if (rc) return rc;
+    if ((rc = precompute_device<C>(ctx, d_src, n, h->c, h->mtab, h->d_tables.get()))) return rc;
     // which points are (0,0): snarkjs keys hold the point at infinity for every wire absent from a matrix
     uint32_t n_inf = 0;
     HIPCHK(ctx, dev_alloc(h->d_live, ((n + 31) / 32 + 1) * 4));
     if ((rc = ensure(ctx, ctx->stage_o, 2048))) return rc;
     uint32_t* d_cnt = (uint32_t*)ctx->stage_o.p();
     HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, 4, ctx->stream));
-    rc = group == 1 ? g16_live_bitmap_device_g1(ctx, d_src, n, h->d_live.get(), d_cnt)
-                    : g16_live_bitmap_device_g2(ctx, d_src, n, h->d_live.get(), d_cnt);
-    if (rc) return rc;
+    if ((rc = live_bitmap_device<C>(ctx, d_src, n, h->d_live.get(), d_cnt))) return rc;
     HIPCHK(ctx, hipMemcpyAsync(&n_inf, d_cnt, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     h->n_inf = n_inf;
@@ -317,16 +316,16 @@ static int32_t points_register(g16_ctx* ctx, int group, const void* points, size
   return G16_OK;
 }
 extern "C" int32_t g16_points_register_g1(g16_ctx* ctx, const void* points, size_t n, g16_points** out) {
-  return points_register(ctx, 1, points, n, false, out);
+  return points_register<G1>(ctx, points, n, false, out);
 }
 extern "C" int32_t g16_points_register_g2(g16_ctx* ctx, const void* points, size_t n, g16_points** out) {
-  return points_register(ctx, 2, points, n, false, out);
+  return points_register<G2>(ctx, points, n, false, out);
 }
 extern "C" int32_t g16_points_register_g1_dev(g16_ctx* ctx, const void* d_points, size_t n, g16_points** out) {
-  return points_register(ctx, 1, d_points, n, true, out);
+  return points_register<G1>(ctx, d_points, n, true, out);
 }
 extern "C" int32_t g16_points_register_g2_dev(g16_ctx* ctx, const void* d_points, size_t n, g16_points** out) {
-  return points_register(ctx, 2, d_points, n, true, out);
+  return points_register<G2>(ctx, d_points, n, true, out);
 }
 extern "C" void g16_points_release(g16_points* h) {
   if (!h) return;
@@ -353,23 +352,22 @@ extern "C" int32_t g16_points_info(const g16_points* h, uint32_t* window_bits, u
 
 // on-curve check of a host point array (mkG1 / mkG2 asserts of the reference's loaders, curves.nim:95-107):
 // *first_bad = index of the first point off the curve, or SIZE_MAX if every point is on it ((0,0) = infinity ok)
-static int32_t points_check(g16_ctx* ctx, int group, const void* points, size_t n, size_t* first_bad) {
+template <class C>
+static int32_t points_check(g16_ctx* ctx, const void* points, size_t n, size_t* first_bad) {
   if (!ctx) return G16_EINVAL;
   if (!first_bad || (n && !points) || n >= (size_t(1) << 31)) {
     ctx->err = "bad argument";
     return G16_EINVAL;
   }
   CTX_ENTER(ctx);
-  const size_t psz = group == 1 ? 64 : 128;
+  constexpr size_t psz = sizeof(typename C::Aff);
   int32_t rc;
   if ((rc = ensure(ctx, ctx->stage_p, n * psz + psz))) return rc;
   if ((rc = ensure(ctx, ctx->stage_o, 2048))) return rc;
   uint32_t* d_bad = (uint32_t*)ctx->stage_o.p();
   HIPCHK(ctx, hipMemsetAsync(d_bad, 0xff, 4, ctx->stream));
   if (n) HIPCHK(ctx, hipMemcpyAsync(ctx->stage_p.p(), points, n * psz, hipMemcpyHostToDevice, ctx->stream));
-  rc = group == 1 ? g16_on_curve_device_g1(ctx, ctx->stage_p.p(), n, d_bad)
-                  : g16_on_curve_device_g2(ctx, ctx->stage_p.p(), n, d_bad);
-  if (rc) return rc;
+  if ((rc = on_curve_device<C>(ctx, ctx->stage_p.p(), n, d_bad))) return rc;
   uint32_t bad = 0;
   HIPCHK(ctx, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -377,55 +375,49 @@ static int32_t points_check(g16_ctx* ctx, int group, const void* points, size_t 
   return G16_OK;
 }
 extern "C" int32_t g16_points_check_g1(g16_ctx* ctx, const void* points, size_t n, size_t* first_bad) {
-  return points_check(ctx, 1, points, n, first_bad);
+  return points_check<G1>(ctx, points, n, first_bad);
 }
 extern "C" int32_t g16_points_check_g2(g16_ctx* ctx, const void* points, size_t n, size_t* first_bad) {
-  return points_check(ctx, 2, points, n, first_bad);
+  return points_check<G2>(ctx, points, n, first_bad);
 }
 
 // out[i] = scalars[i] * generator  (`y ** gen1` / `y ** gen2`, fake_setup.nim:258-261); host pointers
-static int32_t fixed_base(g16_ctx* ctx, int group, const void* scalars, uint32_t flags, size_t n, void* out) {
+template <class C>
+static int32_t fixed_base(g16_ctx* ctx, const void* scalars, uint32_t flags, size_t n, void* out) {
   if (!ctx) return G16_EINVAL;
   if (n && (!scalars || !out)) {
     ctx->err = "null pointer argument";
     return G16_EINVAL;
   }
   CTX_ENTER(ctx);
-  const size_t psz = group == 1 ? 64 : 128;
+  constexpr size_t psz = sizeof(typename C::Aff);
   int32_t rc;
-  g16_ctx::Buf& tb = ctx->fb_table[group - 1];
+  g16_ctx::Buf& tb = ctx->fb_table[group_of<C> - 1];
+  bool& ready = ctx->fb_ready[group_of<C> - 1];
   if ((rc = ensure(ctx, tb, 32 * 255 * psz))) return rc;
   if ((rc = ensure(ctx, ctx->stage_s, n * 32 + 32))) return rc;
   if ((rc = ensure(ctx, ctx->stage_p, n * psz + psz))) return rc;
   if (n) HIPCHK(ctx, hipMemcpyAsync(ctx->stage_s.p(), scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
   const uint32_t mont = (flags & G16_SCALARS_MONT) ? 1u : 0u;
-  rc = group == 1 ? g16_fixed_base_device_g1(ctx, tb.p(), ctx->fb_ready[0], ctx->stage_s.p(), mont, n, ctx->stage_p.p())
-                  : g16_fixed_base_device_g2(ctx, tb.p(), ctx->fb_ready[1], ctx->stage_s.p(), mont, n, ctx->stage_p.p());
-  if (rc) return rc;
-  ctx->fb_ready[group - 1] = true;
+  if ((rc = fixed_base_device<C>(ctx, tb.p(), ready, ctx->stage_s.p(), mont, n, ctx->stage_p.p()))) return rc;
+  ready = true;
   if (n) HIPCHK(ctx, hipMemcpyAsync(out, ctx->stage_p.p(), n * psz, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return G16_OK;
 }
 extern "C" int32_t g16_fixed_base_g1(g16_ctx* ctx, const void* scalars, uint32_t flags, size_t n, void* out) {
-  return fixed_base(ctx, 1, scalars, flags, n, out);
+  return fixed_base<G1>(ctx, scalars, flags, n, out);
 }
 extern "C" int32_t g16_fixed_base_g2(g16_ctx* ctx, const void* scalars, uint32_t flags, size_t n, void* out) {
-  return fixed_base(ctx, 2, scalars, flags, n, out);
+  return fixed_base<G2>(ctx, scalars, flags, n, out);
 }
 
 // MSM against a registered set; flags: G16_SCALARS_MONT | G16_SCALARS_DEVICE | G16_OUT_PARTIAL
-extern "C" int32_t g16_msm_points(g16_ctx* ctx, const g16_points* pts, const void* scalars, uint32_t flags,
-                                  void* out) {
-  if (!ctx) return G16_EINVAL;
-  if (!pts || !out || pts->device != ctx->device || (pts->n && !scalars)) {
-    ctx->err = "bad argument (null pointer or point set of another device)";
-    return G16_EINVAL;
-  }
+template <class C>
+static int32_t msm_points(g16_ctx* ctx, const g16_points* pts, const void* scalars, uint32_t flags, void* out) {
   CTX_ENTER(ctx);
   const bool partial = (flags & G16_OUT_PARTIAL) != 0;
-  const size_t psz = pts->group == 1 ? 64 : 128;
-  const size_t out_bytes = partial ? 2 * psz : psz;
+  const size_t out_bytes = partial ? sizeof(typename C::Acc) : sizeof(typename C::Aff);
   const size_t n = pts->n;
   if (n == 0) {
     memset(out, 0, out_bytes);
@@ -442,33 +434,41 @@ extern "C" int32_t g16_msm_points(g16_ctx* ctx, const g16_points* pts, const voi
   void* d_aff = partial ? nullptr : ctx->stage_o.p();
   void* d_acc = partial ? ctx->stage_o.p() : nullptr;
   const uint32_t* live = g16_points_live_if_sparse(pts);
-  rc = pts->group == 1 ? g16_msm_device_g1(ctx, d_s, flags, pts->d_tables.get(), n, d_aff, d_acc, pts->cfg(), live)
-                       : g16_msm_device_g2(ctx, d_s, flags, pts->d_tables.get(), n, d_aff, d_acc, pts->cfg(), live);
-  if (rc) return rc;
+  if ((rc = msm_device<C>(ctx, d_s, flags, pts->d_tables.get(), n, d_aff, d_acc, pts->cfg(), live))) return rc;
   HIPCHK(ctx, hipMemcpyAsync(out, ctx->stage_o.p(), out_bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return G16_OK;
 }
+extern "C" int32_t g16_msm_points(g16_ctx* ctx, const g16_points* pts, const void* scalars, uint32_t flags,
+                                  void* out) {
+  if (!ctx) return G16_EINVAL;
+  if (!pts || !out || pts->device != ctx->device || (pts->n && !scalars)) {
+    ctx->err = "bad argument (null pointer or point set of another device)";
+    return G16_EINVAL;
+  }
+  // the set's group is data: here, and only here, it selects the curve
+  return pts->group == 1 ? msm_points<G1>(ctx, pts, scalars, flags, out) : msm_points<G2>(ctx, pts, scalars, flags, out);
+}
 
 extern "C" int32_t g16_msm_g1(g16_ctx* ctx, const void* s, uint32_t f, const void* p, size_t n, void* out) {
-  return msm_entry<G1>(ctx, s, f, p, n, out, false, false, "g1");
+  return msm_entry<G1>(ctx, s, f, p, n, out, false, false);
 }
 extern "C" int32_t g16_msm_g2(g16_ctx* ctx, const void* s, uint32_t f, const void* p, size_t n, void* out) {
-  return msm_entry<G2>(ctx, s, f, p, n, out, false, false, "g2");
+  return msm_entry<G2>(ctx, s, f, p, n, out, false, false);
 }
 extern "C" int32_t g16_msm_g1_dev(g16_ctx* ctx, const void* s, uint32_t f, const void* p, size_t n, void* out) {
-  return msm_entry<G1>(ctx, s, f, p, n, out, true, false, "g1");
+  return msm_entry<G1>(ctx, s, f, p, n, out, true, false);
 }
 extern "C" int32_t g16_msm_g2_dev(g16_ctx* ctx, const void* s, uint32_t f, const void* p, size_t n, void* out) {
-  return msm_entry<G2>(ctx, s, f, p, n, out, true, false, "g2");
+  return msm_entry<G2>(ctx, s, f, p, n, out, true, false);
 }
 extern "C" int32_t g16_msm_g1_partial_dev(g16_ctx* ctx, const void* s, uint32_t f, const void* p, size_t n,
                                           void* out) {
-  return msm_entry<G1>(ctx, s, f, p, n, out, true, true, "g1");
+  return msm_entry<G1>(ctx, s, f, p, n, out, true, true);
 }
 extern "C" int32_t g16_msm_g2_partial_dev(g16_ctx* ctx, const void* s, uint32_t f, const void* p, size_t n,
                                           void* out) {
-  return msm_entry<G2>(ctx, s, f, p, n, out, true, true, "g2");
+  return msm_entry<G2>(ctx, s, f, p, n, out, true, true);
 }
 
 template <class C>
@@ -484,9 +484,7 @@ static int32_t sum_partials(g16_ctx* ctx, const void* xyzz, size_t count, void* 
   if ((rc = ensure(ctx, ctx->stage_p, bytes + 256))) return rc;
   if ((rc = ensure(ctx, ctx->stage_o, 512))) return rc;
   if (count) HIPCHK(ctx, hipMemcpyAsync(ctx->stage_p.p(), xyzz, bytes, hipMemcpyHostToDevice, ctx->stream));
-  rc = sizeof(typename C::Aff) == 64 ? g16_sum_partials_device_g1(ctx, ctx->stage_p.p(), (uint32_t)count, ctx->stage_o.p())
-                                     : g16_sum_partials_device_g2(ctx, ctx->stage_p.p(), (uint32_t)count, ctx->stage_o.p());
-  if (rc) return rc;
+  if ((rc = sum_partials_device<C>(ctx, ctx->stage_p.p(), (uint32_t)count, ctx->stage_o.p()))) return rc;
   HIPCHK(ctx, hipMemcpyAsync(out, ctx->stage_o.p(), sizeof(typename C::Aff), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return G16_OK;
@@ -590,7 +588,7 @@ extern "C" int32_t g16_selftest(g16_ctx* ctx) {
   u256* d_nt = reinterpret_cast<u256*>(d + 16 + 64 + 24);
   g1_aff* d_res = reinterpret_cast<g1_aff*>(d + 16 + 64 + 24 + 72);
   u256* d_nout = reinterpret_cast<u256*>(d + 16 + 64 + 24 + 72 + 16);
-  if ((rc = g16_msm_device_g1(ctx, d_sc, G16_SCALARS_STD, d_pts, 3, d_res, nullptr, 0))) return rc;
+  if ((rc = msm_device<G1>(ctx, d_sc, G16_SCALARS_STD, d_pts, 3, d_res, nullptr, 0))) return rc;
   if ((rc = g16_ntt_device(ctx, d_nt, d_nout, 3, 0))) return rc;
   HIPCHK(ctx, hipMemcpyAsync(&ok, d, 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(&h.msm, d_res, 64, hipMemcpyDeviceToHost, ctx->stream));

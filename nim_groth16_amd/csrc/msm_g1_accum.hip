@@ -1,5 +1,3 @@
 // G1 bucket-segment accumulation (the dominant kernel of the MSM)
 #include "msm_stage.cuh"
-int32_t g16_st_accum_g1(g16_ctx* ctx, hipStream_t st, const MsmParams& P, const void* batch, uint32_t ny) {
-  return stage_accum<G1>(ctx, st, P, batch, ny);
-}
+template int32_t stage_accum<G1>(g16_ctx*, hipStream_t, const MsmParams&, const MsmBatch<G1>&, uint32_t);

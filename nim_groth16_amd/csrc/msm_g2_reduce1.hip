@@ -1,8 +1,4 @@
 // G2 split-bucket combine and first bucket-reduction stage
 #include "msm_stage.cuh"
-int32_t g16_st_heavy_g2(g16_ctx* ctx, hipStream_t st, const MsmParams& P, const void* batch, uint32_t ny) {
-  return stage_heavy<G2>(ctx, st, P, batch, ny);
-}
-int32_t g16_st_reduce1_g2(g16_ctx* ctx, hipStream_t st, const MsmParams& P, const void* batch, uint32_t ny) {
-  return stage_reduce1<G2>(ctx, st, P, batch, ny);
-}
+template int32_t stage_heavy<G2>(g16_ctx*, hipStream_t, const MsmParams&, const MsmBatch<G2>&, uint32_t);
+template int32_t stage_reduce1<G2>(g16_ctx*, hipStream_t, const MsmParams&, const MsmBatch<G2>&, uint32_t);

@@ -1,25 +1,26 @@
-// Per-curve launch templates of the accumulate / reduce stages and of the auxiliary point kernels.  Each stage is
-// instantiated in its own translation unit (msm_g1_*.hip, msm_g2_*.hip): the fully inlined G2 kernels take
-// minutes to compile, and `make -j` builds the stages in parallel.
+// Bodies of the per-curve launch templates that g16_internal.hpp declares: the accumulate / reduce stages and the
+// auxiliary point kernels.  Included only by msm_g1_*.hip and msm_g2_*.hip, each of which explicitly instantiates its
+// share for one curve: the fully inlined G2 kernels take minutes to compile, and `make -j` builds the stages in
+// parallel.  Every other translation unit calls the templates through their declarations and instantiates no kernel.
 #pragma once
 #include "g16_internal.hpp"
 #include "msm.cuh"
 
 using namespace g16;
 
-// `batch`: MsmBatch<C> with `ny` jobs that share the launch parameters P (same n, same window: the G1 MSMs of a proof)
+// B: `ny` jobs that share the launch parameters P (same n, same window: the G1 MSMs of a proof)
 template <class C>
-static int32_t stage_accum(g16_ctx* ctx, hipStream_t st, const MsmParams& P, const void* batch, uint32_t ny) {
+int32_t stage_accum(g16_ctx* ctx, hipStream_t st, const MsmParams& P, const MsmBatch<C>& B, uint32_t ny) {
   const bool g2 = sizeof(typename C::Aff) == 128;
   const uint32_t ntask = P.nbuckets + P.max_extra;
   KLAUNCH_ON(ctx, st, g2 ? "msm_accum_g2" : "msm_accum_g1", msm_accum<C>, dim3((ntask + ACC_BLOCK - 1) / ACC_BLOCK, ny),
-             ACC_BLOCK, 0, *(const MsmBatch<C>*)batch, P, ctx->profiling ? ctx->clk_buf.get() : (unsigned long long*)nullptr);
+             ACC_BLOCK, 0, B, P, ctx->profiling ? ctx->clk_buf.get() : (unsigned long long*)nullptr);
   HIPCHK(ctx, hipGetLastError());
   return G16_OK;
 }
 
 template <class C>
-static int32_t stage_heavy(g16_ctx* ctx, hipStream_t st, const MsmParams& P, const void* batch, uint32_t ny) {
+int32_t stage_heavy(g16_ctx* ctx, hipStream_t st, const MsmParams& P, const MsmBatch<C>& B, uint32_t ny) {
   const bool g2 = sizeof(typename C::Aff) == 128;
   // Grid size: the kernel loops grid-stride over the list of split buckets (all but empty for uniform or circom-like
   // scalars).  In the timeline of a proof this launch looks expensive (milliseconds, against 0.05 ms alone) because
@@ -29,19 +30,18 @@ static int32_t stage_heavy(g16_ctx* ctx, hipStream_t st, const MsmParams& P, con
   // (tools/perf_skew.py "256 values": 3.92 -> 5.11 ms).
   const uint32_t hgrid = g16_env().heavy_grid ? (uint32_t)g16_env().heavy_grid : (ny > 1 ? 512u : 1024u);
   KLAUNCH_ON(ctx, st, g2 ? "msm_heavy_g2" : "msm_heavy_g1", msm_heavy<C>, dim3(hgrid, ny), heavy_block<C>(),
-             heavy_block<C>() * sizeof(typename Ec29<C>::Acc), *(const MsmBatch<C>*)batch, P);
+             heavy_block<C>() * sizeof(typename Ec29<C>::Acc), B, P);
   HIPCHK(ctx, hipGetLastError());
   return G16_OK;
 }
 
 template <class C>
-static int32_t stage_reduce1(g16_ctx* ctx, hipStream_t st, const MsmParams& P, const void* batch, uint32_t ny) {
+int32_t stage_reduce1(g16_ctx* ctx, hipStream_t st, const MsmParams& P, const MsmBatch<C>& B, uint32_t ny) {
   const bool g2 = sizeof(typename C::Aff) == 128;
   const uint32_t rc = msm_red_chunk(P);
   const size_t nchunks = P.nbuckets / rc;
   KLAUNCH_ON(ctx, st, g2 ? "msm_reduce1_g2" : "msm_reduce1_g1", msm_reduce1<C>,
-             dim3((uint32_t)((nchunks + MSM_BLOCK - 1) / MSM_BLOCK), ny), MSM_BLOCK, 0, *(const MsmBatch<C>*)batch,
-             P.nbuckets, rc);
+             dim3((uint32_t)((nchunks + MSM_BLOCK - 1) / MSM_BLOCK), ny), MSM_BLOCK, 0, B, P.nbuckets, rc);
   HIPCHK(ctx, hipGetLastError());
   return G16_OK;
 }
@@ -49,12 +49,11 @@ static int32_t stage_reduce1(g16_ctx* ctx, hipStream_t st, const MsmParams& P, c
 // MsmJob::wsum: room for 2 * 64 + 2 accumulators
 // narrow_tail: the caller overlaps this tail with other work (only read by the one-lane kernels, below)
 template <class C>
-static int32_t stage_reduce2_fold(g16_ctx* ctx, hipStream_t st, const MsmParams& P, bool narrow_tail, const void* batch,
-                                  uint32_t ny) {
+int32_t stage_reduce2_fold(g16_ctx* ctx, hipStream_t st, const MsmParams& P, bool narrow_tail, const MsmBatch<C>& B,
+                           uint32_t ny) {
   const bool g2 = sizeof(typename C::Aff) == 128;
   const uint32_t rc = msm_red_chunk(P);
   const size_t nchunks = P.nbuckets / rc;
-  const MsmBatch<C>& B = *(const MsmBatch<C>*)batch;
   // reduction sets: the windows themselves, or <= 64 slices of the merged bucket set.  reduce2 is a latency chain
   // whose length grows with the chunks per thread, so the slices are as small as the 64 lanes of msm_fold_merged
   // allow: 512 chunks (2^13 buckets) per slice at c = 20 -> 64 workgroups, one chunk per thread (G1) / two (G2).
@@ -131,7 +130,7 @@ __global__ void sum_partials_kernel(const typename C::Acc* __restrict__ parts, u
 }
 
 template <class C>
-static int32_t sum_partials_device(g16_ctx* ctx, const void* d_parts, uint32_t count, void* d_out_aff) {
+int32_t sum_partials_device(g16_ctx* ctx, const void* d_parts, uint32_t count, void* d_out_aff) {
   KLAUNCH(ctx, "sum_partials", sum_partials_kernel<C>, 1, 64, 0, (const typename C::Acc*)d_parts, count,
           (typename C::Aff*)d_out_aff);
   HIPCHK(ctx, hipGetLastError());
@@ -139,7 +138,7 @@ static int32_t sum_partials_device(g16_ctx* ctx, const void* d_parts, uint32_t c
 }
 
 template <class C>
-static int32_t precompute_device(g16_ctx* ctx, const void* d_points, size_t n, uint32_t c, uint32_t mtab,
+int32_t precompute_device(g16_ctx* ctx, const void* d_points, size_t n, uint32_t c, uint32_t mtab,
                                  void* d_tables) {
   const uint32_t nwin = FR_BITS / c + 1;
   KLAUNCH(ctx, "msm_precompute", msm_precompute<C>, (uint32_t)((n + MSM_BLOCK - 1) / MSM_BLOCK), MSM_BLOCK, 0,
@@ -150,7 +149,7 @@ static int32_t precompute_device(g16_ctx* ctx, const void* d_points, size_t n, u
 
 // reference-layout points -> reduced-radix entries (the one-shot MSM entry points, which have no tables)
 template <class C>
-static int32_t to29_device(g16_ctx* ctx, hipStream_t st, const void* d_points, size_t n, void* d_out) {
+int32_t to29_device(g16_ctx* ctx, hipStream_t st, const void* d_points, size_t n, void* d_out) {
   if (n)
     KLAUNCH_ON(ctx, st, "points_to29", points_to29<C>, (uint32_t)((n + MSM_BLOCK - 1) / MSM_BLOCK), MSM_BLOCK, 0,
                (const typename C::Aff*)d_points, (uint32_t)n, (typename Ec29<C>::Tab*)d_out);
@@ -158,12 +157,18 @@ static int32_t to29_device(g16_ctx* ctx, hipStream_t st, const void* d_points, s
   return G16_OK;
 }
 
-// gen: group generator in Montgomery affine form; d_table: 32*255 points (built here when !table_ready)
+// Curve constants in Montgomery form, specialised beside the instantiations that use them (msm_g{1,2}_misc.hip):
+//   static typename C::Aff gen();   the group generator
+//   static typename C::E b();       the constant of y^2 = x^3 + b
 template <class C>
-static int32_t fixed_base_device(g16_ctx* ctx, const typename C::Aff& gen, void* d_table, bool table_ready,
-                                 const void* d_scalars, uint32_t mont, size_t n, void* d_out) {
+struct CurveConsts;
+
+// d_table: 32*255 multiples of the generator (built here when !table_ready)
+template <class C>
+int32_t fixed_base_device(g16_ctx* ctx, void* d_table, bool table_ready, const void* d_scalars, uint32_t mont, size_t n,
+                          void* d_out) {
   if (!table_ready)
-    KLAUNCH(ctx, "fixed_base_table", fixed_base_table<C>, (32 * 255 + 255) / 256, 256, 0, gen,
+    KLAUNCH(ctx, "fixed_base_table", fixed_base_table<C>, (32 * 255 + 255) / 256, 256, 0, CurveConsts<C>::gen(),
             (typename C::Aff*)d_table);
   if (n)
     KLAUNCH(ctx, "fixed_base_mul", fixed_base_mul<C>, (uint32_t)((n + 255) / 256), 256, 0, (const u256*)d_scalars,
@@ -174,11 +179,19 @@ static int32_t fixed_base_device(g16_ctx* ctx, const typename C::Aff& gen, void*
 
 // first_bad (device u32) must hold 0xffffffff on entry
 template <class C>
-static int32_t on_curve_device(g16_ctx* ctx, const void* d_points, size_t n, const typename C::E& b,
-                               uint32_t* d_first_bad) {
+int32_t on_curve_device(g16_ctx* ctx, const void* d_points, size_t n, uint32_t* d_first_bad) {
   if (n)
     KLAUNCH(ctx, "points_on_curve", points_on_curve<C>, (uint32_t)((n + 255) / 256), 256, 0,
-            (const typename C::Aff*)d_points, (uint32_t)n, b, d_first_bad);
+            (const typename C::Aff*)d_points, (uint32_t)n, CurveConsts<C>::b(), d_first_bad);
+  HIPCHK(ctx, hipGetLastError());
+  return G16_OK;
+}
+
+template <class C>
+int32_t live_bitmap_device(g16_ctx* ctx, const void* d_points, size_t n, uint32_t* d_bitmap, uint32_t* d_n_inf) {
+  if (n)
+    KLAUNCH(ctx, "points_live_bitmap", points_live_bitmap<C>, (uint32_t)((n + 255) / 256), 256, 0,
+            (const typename C::Aff*)d_points, (uint32_t)n, d_bitmap, d_n_inf);
   HIPCHK(ctx, hipGetLastError());
   return G16_OK;
 }

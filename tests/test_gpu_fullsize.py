@@ -51,7 +51,7 @@ def test_msm_fullsize_known_discrete_logs(ctx, orc, group, log2n):
         c, ntab = h.info()
         layout = f"c = {c}, {ntab} tables: {'two tables' if ntab == 2 * (254 // c + 1) else 'one table'} per window"
         if log2n >= 23:
-            assert c == 22, layout                               # the cost model's window (msm_host.cuh)
+            assert c == 22, layout                               # the cost model's window (msm_sort.hip)
             # two tables per window, or one when they do not fit the free HBM (points_register falls back silently;
             # G16_MTAB=1 in test_gpu_knobs.py holds that layout at c = 20 and 22 too)
             assert ntab in (24, 12), layout
