@@ -4,6 +4,7 @@
 #include <stddef.h>
 
 #include "../../nim_groth16_amd/csrc/ec29.cuh"
+#include "../../nim_groth16_amd/csrc/pairing.cuh"
 #include "../kernels/devops.inc"
 
 template <int OP = 0>

@@ -67,10 +67,12 @@ def edge_set(m):
     return tuple(out)
 
 
-def pair_tuples(name, edges, arity, rand, extra=()):
+def pair_tuples(name, edges, arity, rand, extra=(), nrandom=None):
     """all ordered pairs of `edges` in the first two slots (the other slots walk the set with coprime strides), then
-    `extra`, then NRANDOM random tuples; one more random tuple if the count would fill the last 64-lane block"""
+    `extra`, then NRANDOM (or `nrandom`) random tuples; one more random tuple if the count would fill the last 64-lane
+    block"""
     rng = _rng(name)
+    nrandom = NRANDOM if nrandom is None else nrandom
     n = len(edges)
     out = []
     for i, a in enumerate(edges):
@@ -79,7 +81,7 @@ def pair_tuples(name, edges, arity, rand, extra=()):
     if arity == 1:
         out = [[a] for a in edges]
     out += [list(t) for t in extra]
-    out += [[rand(rng) for _ in range(arity)] for _ in range(NRANDOM)]
+    out += [[rand(rng) for _ in range(arity)] for _ in range(nrandom)]
     if len(out) % 64 == 0:
         out.append([rand(rng) for _ in range(arity)])
     return out
@@ -599,6 +601,329 @@ def case_tab29(group):
     return Case("g%d_tab29" % group, inp, exp, [("tab_from_std", 0, pw), ("pack(unpack)", pw, pw)])
 
 
+# ---- the Fp12 tower, the Miller loop and the final exponentiation (pairing.cuh) --------------------------------------
+# An element is a tuple of six Fp2 values g[k] = (a, b) over w^k, as plain residues (not Montgomery); the references
+# work in the oracle's 12-coefficient polynomial basis Fp[w]/(w^12 - 18 w^6 + 82), where u = w^6 - 9.  The oracle's
+# _f12_mul costs about 50 us, so a power with a 3000-bit exponent (the inverse, the final exponentiation) costs 0.2 s
+# for a dense element and a fraction of that for a sparse one: the operand counts below are sized by that.
+RM_P = MONT % P
+RI_P = pow(RM_P, -1, P)
+F2Z = (0, 0)
+F12_ONE = ((1, 0),) + (F2Z,) * 5
+BN_X = 4965661367192848881
+assert 6 * BN_X * BN_X == o.ATE_LOOP
+
+
+def f12_to_poly(g):
+    """six Fp2 values over w^k -> the oracle's 12 coefficients: (a + b u) w^k = (a - 9 b) w^k + b w^(k+6)"""
+    out = [0] * 12
+    for k, c in enumerate(g):
+        out = [(x + y) % P for x, y in zip(out, o._emb(c, k))]
+    return out
+
+
+def f12_from_poly(c):
+    """the inverse of f12_to_poly"""
+    return tuple(((c[k] + 9 * c[k + 6]) % P, c[k + 6] % P) for k in range(6))
+
+
+def f12_from_bytes(raw):
+    """384-byte flat Fp12 (6 x Fp2 over w^k, Montgomery), the layout g16_pairing returns -> six Fp2 values"""
+    return tuple((o.fp_from_mont_bytes(raw[64 * k:64 * k + 32]), o.fp_from_mont_bytes(raw[64 * k + 32:64 * k + 64]))
+                 for k in range(6))
+
+
+def gt_from_bytes(raw):
+    """384-byte flat Fp12 -> the oracle's degree-12 polynomial basis"""
+    return f12_to_poly(f12_from_bytes(raw))
+
+
+def _fpw(x):
+    return w8(x * RM_P % P)
+
+
+def _f12w(g):
+    return sum((_fpw(c[0]) + _fpw(c[1]) for c in g), [])
+
+
+def _polyw(c):
+    return _f12w(f12_from_poly(c))
+
+
+def _stored(x):
+    """the residue whose Montgomery word is x: edge patterns of the stored limbs, not of the value"""
+    return x * RI_P % P
+
+
+@functools.lru_cache(None)
+def _f12_pool_named():
+    rng = _rng("f12_pool")
+    r2 = lambda: (rng.randrange(P), rng.randrange(P))      # noqa: E731
+
+    def basis(k, c):
+        return tuple(c if i == k else F2Z for i in range(6))
+    pool = [(F2Z,) * 6, F12_ONE]
+    for k in range(6):                                      # one basis element w^k
+        pool += [basis(k, c) for c in ((1, 0), (P - 1, 0), (0, 1), (P - 1, P - 1), (1, P - 1))]
+    pool.append(((P - 1, P - 1),) * 6)                      # all twelve coordinates p - 1 ...
+    pool.append(((_stored(P - 1),) * 2,) * 6)               # ... and all twelve stored words p - 1, and 1
+    pool.append(((_stored(1),) * 2,) * 6)
+    named = {"stored1": pool[-1]}
+    pool.append(basis(0, (rng.randrange(2, P), 0)))         # in Fp, in Fp2
+    named["fp"] = pool[-1]
+    pool.append(basis(0, r2()))
+    pool.append((r2(), F2Z, r2(), F2Z, r2(), F2Z))          # in Fp6: the B = 0 side of inv
+    named["fp6"] = pool[-1]
+    pool.append((F2Z, r2(), F2Z, r2(), F2Z, r2()))          # pure w: the A = 0 side of inv
+    # g[0..2] = 0: among themselves every product term has i + j >= 6, so mul_xi carries the whole result
+    pool.append((F2Z, F2Z, F2Z, r2(), r2(), r2()))
+    pool.append((F2Z, F2Z, F2Z) + ((P - 1, P - 1),) * 3)
+    for _ in range(2):                                      # the cyclotomic subgroup: outputs of the easy part
+        x = [rng.randrange(P) for _ in range(12)]
+        pool.append(f12_from_poly(o._f12_pow(x, (P ** 6 - 1) * (P ** 2 + 1))))
+    named["cyclotomic"] = pool[-1]
+    pool += [tuple(r2() for _ in range(6)) for _ in range(3)]
+    return tuple(dict.fromkeys(pool)), named
+
+
+def f12_pool():
+    return _f12_pool_named()[0]
+
+
+def _f12_rand(rng):
+    return tuple((rng.randrange(P), rng.randrange(P)) for _ in range(6))
+
+
+@functools.lru_cache(None)
+def _pow_ref(g, e):
+    return tuple(o._f12_pow(f12_to_poly(g), e))
+
+
+def case_f12_mul():
+    tup = pair_tuples("f12_mul", f12_pool(), 2, _f12_rand, nrandom=64)
+    inp, exp = [], []
+    for a, b in tup:
+        r = _polyw(o._f12_mul(f12_to_poly(a), f12_to_poly(b)))
+        inp.append(_f12w(a) + _f12w(b))
+        exp.append(r + r)
+    return Case("f12_mul", inp, exp, [("mul(a,b)", 0, 96), ("mul(b,a)", 96, 96)])
+
+
+def case_f12_sqr():
+    tup = pair_tuples("f12_sqr", f12_pool(), 1, _f12_rand, nrandom=64)
+    inp, exp = [], []
+    for (a,) in tup:
+        pa = f12_to_poly(a)
+        r = _polyw(o._f12_mul(pa, pa))
+        inp.append(_f12w(a))
+        exp.append(r + r)
+    return Case("f12_sqr", inp, exp, [("sqr(a)", 0, 96), ("mul(a,a)", 96, 96)])
+
+
+def case_f12_mul_line():
+    rng = _rng("f12_mul_line")
+    r2 = lambda: (rng.randrange(P), rng.randrange(P))      # noqa: E731
+    base = (rng.randrange(P), r2(), r2())
+    lines = [base, (0, F2Z, F2Z), (1, (1, 0), (1, 0)), (P - 1, (P - 1, P - 1), (P - 1, P - 1))]
+    for x in (0, 1, P - 1, _stored(1), _stored(P - 1)):     # each coefficient at its edges in turn
+        lines.append((x, base[1], base[2]))
+    for c in (F2Z, (1, 0), (0, 1), (P - 1, 0), (P - 1, P - 1), (_stored(P - 1), _stored(1))):
+        lines += [(base[0], c, base[2]), (base[0], base[1], c), (0, c, F2Z), (0, F2Z, c)]
+    tup = [(f, l) for f in f12_pool() for l in lines]
+    tup += [(_f12_rand(rng), (rng.randrange(P), r2(), r2())) for _ in range(64)]
+    inp, exp = [], []
+    for f, (l0, l1, l3) in tup:
+        line = [(x + y + z) % P for x, y, z in zip([l0] + [0] * 11, o._emb(l1, 1), o._emb(l3, 3))]
+        inp.append(_f12w(f) + _fpw(l0) + _fpw(l1[0]) + _fpw(l1[1]) + _fpw(l3[0]) + _fpw(l3[1]))
+        exp.append(_polyw(o._f12_mul(line, f12_to_poly(f))))
+    if len(inp) % 64 == 0:
+        inp.append(inp[0]), exp.append(exp[0])
+    return Case("f12_mul_line", inp, exp, [("mul_line", 0, 96)])
+
+
+def case_f12_frob():
+    tup = pair_tuples("f12_frob", f12_pool(), 1, _f12_rand, nrandom=2)
+    inp = [_f12w(a) for (a,) in tup]
+    exp = [sum((_polyw(_pow_ref(a, P ** n)) for n in (6, 1, 2, 3)), []) for (a,) in tup]
+    return Case("f12_frob", inp, exp, [("conj", 0, 96)] + [("frobenius(a,%d)" % n, 96 * n, 96) for n in (1, 2, 3)])
+
+
+def _f6_embed(c):
+    """Fp6 = Fp2[v]/(v^3 - xi) into Fp12 through v = w^2"""
+    return (c[0], F2Z, c[1], F2Z, c[2], F2Z)
+
+
+def _f6_back(g):
+    assert g[1] == g[3] == g[5] == F2Z
+    return (g[0], g[2], g[4])
+
+
+def _f6w(c):
+    return sum((_fpw(x[0]) + _fpw(x[1]) for x in c), [])
+
+
+@functools.lru_cache(None)
+def f6_pool():
+    rng = _rng("f6_pool")
+    r2 = lambda: (rng.randrange(P), rng.randrange(P))      # noqa: E731
+    pool = [(F2Z,) * 3, ((1, 0), F2Z, F2Z)]
+    for k in range(3):
+        pool += [tuple(c if i == k else F2Z for i in range(3)) for c in ((1, 0), (P - 1, 0), (0, 1), (P - 1, P - 1), (1, P - 1))]
+    pool += [((P - 1, P - 1),) * 3, ((_stored(P - 1),) * 2,) * 3, ((rng.randrange(1, P), 0), F2Z, F2Z), (r2(), F2Z, F2Z)]
+    pool += [(F2Z, r2(), r2()), (r2(), F2Z, r2()), (r2(), r2(), F2Z)]
+    pool += [(r2(), r2(), r2()) for _ in range(4)]
+    return tuple(dict.fromkeys(pool))
+
+
+def case_f6_mul():
+    tup = pair_tuples("f6_mul", f6_pool(), 2, lambda r: tuple((r.randrange(P), r.randrange(P)) for _ in range(3)), nrandom=64)
+    inp, exp = [], []
+    for a, b in tup:
+        inp.append(_f6w(a) + _f6w(b))
+        exp.append(_f6w(_f6_back(f12_from_poly(o._f12_mul(f12_to_poly(_f6_embed(a)), f12_to_poly(_f6_embed(b)))))))
+    return Case("f6_mul", inp, exp, [("f6mul", 0, 48)])
+
+
+def _post_inverse(words, embed):
+    """a * inv(a) = 1, on the words the op returned"""
+    def post(row_in, row_out):
+        def elem(row):
+            c = [from_w8(row[8 * i:8 * i + 8]) * RI_P % P for i in range(words // 8)]
+            return embed(tuple((c[2 * i], c[2 * i + 1]) for i in range(words // 16)))
+        assert o._f12_mul(f12_to_poly(elem(row_in[:words])), f12_to_poly(elem(row_out[:words]))) == o._f12_one(), \
+            "a * inv(a) is not 1"
+    return post
+
+
+def case_f6_inv():
+    """nonzero operands only: f6inv hands its norm to Fp2::inv"""
+    rng = _rng("f6_inv")
+    xs = [c for c in f6_pool() if c != (F2Z,) * 3] + [tuple((rng.randrange(P), rng.randrange(P)) for _ in range(3)) for _ in range(4)]
+    inp = [_f6w(c) for c in xs]
+    exp = [_f6w(_f6_back(f12_from_poly(_pow_ref(_f6_embed(c), P ** 12 - 2)))) for c in xs]
+    return Case("f6_inv", inp, exp, [("f6inv", 0, 48)], post=_post_inverse(48, _f6_embed))
+
+
+def case_f12_inv():
+    """nonzero operands only: inv reaches Fp2::inv through f6inv"""
+    rng = _rng("f12_inv")
+    xs = [g for g in f12_pool() if g != (F2Z,) * 6] + [_f12_rand(rng) for _ in range(2)]
+    inp = [_f12w(g) for g in xs]
+    exp = [_polyw(_pow_ref(g, P ** 12 - 2)) for g in xs]
+    return Case("f12_inv", inp, exp, [("inv", 0, 96)], post=_post_inverse(96, lambda g: g))
+
+
+POW_EXPONENTS = (0, 1, 2, 1 << 63, (1 << 64) - 1, BN_X)
+
+
+def case_f12_pow_u64():
+    rng = _rng("f12_pow_u64")
+    tup = [(g, e) for g in f12_pool() for e in POW_EXPONENTS]
+    tup += [(_f12_rand(rng), rng.randrange(1 << 64)) for _ in range(9)]
+    inp = [_f12w(g) + [e & 0xffffffff, e >> 32] for g, e in tup]
+    exp = [_polyw(_pow_ref(g, e)) for g, e in tup]
+    return Case("f12_pow_u64", inp, exp, [("pow_u64", 0, 96)])
+
+
+def case_f12_small_pows():
+    tup = pair_tuples("f12_small_pows", f12_pool(), 1, _f12_rand, nrandom=32)
+    inp = [_f12w(a) for (a,) in tup]
+    exp = [sum((_polyw(_pow_ref(a, e)) for e in (6, 12, 18, 30, 36)), []) for (a,) in tup]
+    return Case("f12_small_pows", inp, exp, [("p%d" % e, 96 * i, 96) for i, e in enumerate((6, 12, 18, 30, 36))])
+
+
+def case_f12_is_one():
+    """the pool, and one with a single bit of a single stored word flipped, in each of the twelve coordinates"""
+    rng = _rng("f12_is_one")
+    one_w = _f12w(F12_ONE)
+    inp = [_f12w(g) for g in f12_pool()]
+    for coord in range(12):
+        for bit in (0, 31, 32 * rng.randrange(1, 7) + rng.randrange(32), 224, 252):
+            row = list(one_w)
+            row[8 * coord + bit // 32] ^= 1 << (bit % 32)
+            if from_w8(row[8 * coord:8 * coord + 8]) < P:      # canonical operands only
+                inp.append(row)
+    inp += [one_w, _f12w(((P - 1, 0),) + (F2Z,) * 5), _f12w(((_stored(1), 0),) + (F2Z,) * 5)]
+    exp = [[1 if row == one_w else 0] for row in inp]
+    assert sum(e[0] for e in exp) == 2 and len(inp) % 64 != 0
+    return Case("f12_is_one", inp, exp, [("is_one", 0, 1)])
+
+
+def twist_walk(x=(3, 1)):
+    """points of the twist outside the order-r subgroup, walking x upwards (as the verifier's subgroup test does)"""
+    while True:
+        y = _fp2_sqrt(o.fp2_add(o.fp2_mul(o.fp2_sqr(x), x), o.TWIST_B))
+        if y is not None and not o.G2.is_inf(o.G2.mul(R, (x, y))):
+            yield (x, y)
+        x = (x[0] + 1, x[1])
+
+
+G2_COFACTOR = 2 * P - R           # #E'(Fp2) = r (2p - r)
+SMALL_ORDER = 10069               # 2p - r = 10069 * (a 241-bit number)
+assert G2_COFACTOR % SMALL_ORDER == 0
+
+
+@functools.lru_cache(None)
+def twist_points():
+    """(a twist point of order 10069, the first twist point outside the order-r subgroup)"""
+    full = None
+    for T in twist_walk():
+        full = full or T
+        Q = o.G2.mul(R * (G2_COFACTOR // SMALL_ORDER), T)
+        if not o.G2.is_inf(Q):
+            assert o.G2.is_on_curve(Q) and o.G2.is_inf(o.G2.mul(SMALL_ORDER, Q))
+            return Q, full
+
+
+@functools.lru_cache(None)
+def miller_ref(Pt, Q):
+    return tuple(o.miller_loop(Pt, Q))
+
+
+@functools.lru_cache(None)
+def miller_pairs():
+    """(P, Q) operands of the Miller loop.  The oracle's loop is the reference for every one of them: it asserts
+    T = -Q wherever it meets T.x = Q.x, and that assertion holds on all of these (no case had to be left out; the
+    multiples 6x^2 visits of the order-10069 point never meet +-Q or infinity modulo 10069)."""
+    rng = _rng("pair_miller")
+    P1, P2, P3 = (o.G1.mul(rng.randrange(1, R), o.GEN1) for _ in range(3))
+    Q1, Q2, Q3 = (o.G2.mul(rng.randrange(1, R), o.GEN2) for _ in range(3))
+    small, full = twist_points()
+    pairs = [(o.INF_G1, Q1), (P1, o.INF_G2), (o.INF_G1, o.INF_G2), (o.GEN1, o.GEN2), (P1, Q1), (o.G1.neg(P1), Q1),
+             (P1, o.G2.neg(Q1)), (P2, Q2), (P3, Q3), (o.GEN1, Q2), (P2, o.GEN2),
+             (P1, small), (o.GEN1, small), (P2, o.G2.neg(small)), (P1, full), (o.GEN1, full), (o.INF_G1, small)]
+    e1, e2 = edge_points(1), edge_points(2)
+    pairs += [(e, (Q1, o.GEN2)[i % 2]) for i, e in enumerate(e1[::max(1, len(e1) // 10)][:10])]
+    pairs += [((P1, o.GEN1)[i % 2], e) for i, e in enumerate(e2[::max(1, len(e2) // 10)][:10])]
+    pairs += [(e1[-1], e2[-1]), (e1[0], e2[0])]
+    pairs = list(dict.fromkeys(pairs))
+    assert len(pairs) <= 40 and len(pairs) % 64 != 0
+    return tuple(pairs)
+
+
+def case_pair_miller():
+    inp = [_pw(o.g1_to_bytes, Pt) + _pw(o.g2_to_bytes, Q) for Pt, Q in miller_pairs()]
+    exp = [_polyw(miller_ref(Pt, Q)) for Pt, Q in miller_pairs()]
+    return Case("pair_miller", inp, exp, [("miller", 0, 96)])
+
+
+def case_pair_final_exp():
+    """nonzero operands only (final_exp inverts its operand)"""
+    rng = _rng("pair_final_exp")
+    named = _f12_pool_named()[1]
+    mp = miller_pairs()
+    # the generators, random pairs, -P and -Q, the order-10069 and the cofactor point, three edge points
+    fs = [f12_from_poly(miller_ref(*mp[i])) for i in (3, 4, 5, 6, 7, 9, 11, 12, 14, -1, -2, -3)]
+    subfield = [F12_ONE, named["fp"], named["fp6"]]         # 1, an element of Fp*, one of Fp6*: all give 1
+    fs += subfield + [named["cyclotomic"], named["stored1"]] + [_f12_rand(rng) for _ in range(3)]
+    assert len(fs) <= 24 and (F2Z,) * 6 not in fs
+    exp = [tuple(o.final_exp(f12_to_poly(f))) for f in fs]
+    for f, e in zip(fs, exp):
+        assert (e == tuple(o._f12_one())) == (f in subfield)
+    return Case("pair_final_exp", [_f12w(f) for f in fs], [_polyw(e) for e in exp], [("final_exp", 0, 96)])
+
+
+
 # ---- msm_digits (device only) ------------------------------------------------------------------------------------------
 def class_weight(c, bucket):
     """weight of a bucket of the class set (msm.cuh), as restated in shim_class_buckets_check"""
@@ -691,9 +1016,23 @@ BUILDERS = {
     "g1_seq29": lambda: case_ec29_seq(1), "g2_seq29": lambda: case_ec29_seq(2),
     "g1_chain29": lambda: case_ec29_chain(1), "g2_chain29": lambda: case_ec29_chain(2),
     "g1_tab29": lambda: case_tab29(1), "g2_tab29": lambda: case_tab29(2),
+    "f12_mul": case_f12_mul, "f12_sqr": case_f12_sqr, "f12_mul_line": case_f12_mul_line, "f12_frob": case_f12_frob,
+    "f6_mul": case_f6_mul, "f6_inv": case_f6_inv, "f12_inv": case_f12_inv, "f12_pow_u64": case_f12_pow_u64,
+    "f12_small_pows": case_f12_small_pows, "f12_is_one": case_f12_is_one, "pair_miller": case_pair_miller,
+    "pair_final_exp": case_pair_final_exp,
 }
 HOST_OPS = tuple(BUILDERS)                    # every op of devops.inc that also compiles with g++
 DEVICE_OPS = HOST_OPS + ("msm_digits",)       # the op groups of the GPU test
+# the ops of pairing.cuh run in the builds whose configuration ships pairing.o: plain, and calls (make DEV=1); the
+# reduced-radix macros of the other three do not reach pairing.cuh, and their builds leave these ops out
+PAIRING_OPS = ("f12_mul", "f12_sqr", "f12_mul_line", "f12_frob", "f6_mul", "f6_inv", "f12_inv", "f12_pow_u64",
+               "f12_small_pows", "f12_is_one", "pair_miller", "pair_final_exp")
+PAIRING_VARIANTS = ("plain", "calls")
+
+
+def variant_ops(variant):
+    """the ops the build `variant` (a name of VARIANTS) carries"""
+    return tuple(op for op in DEVICE_OPS if op not in PAIRING_OPS or variant in PAIRING_VARIANTS)
 
 
 @functools.lru_cache(None)

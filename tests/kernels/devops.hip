@@ -31,7 +31,11 @@
 #endif
 
 #include "../../nim_groth16_amd/csrc/msm.cuh"
+#include "../../nim_groth16_amd/csrc/pairing.cuh"
 #define DEVOPS_WITH_MSM 1
+// pairing.o ships as plain, and as calls under DEV=1; the reduced-radix macros of the other builds do not reach
+// pairing.cuh, so those builds leave the pairing ops out (devops_carries says so; running one there is an error)
+#define DEVOPS_PAIRING (DEVOPS_VARIANT_ID == 0 || DEVOPS_VARIANT_ID == 4)
 #include "devops.inc"
 
 namespace {   // internal linkage: five variants of these templates live in one shared library
@@ -46,8 +50,12 @@ __global__ void __launch_bounds__(64) devops_kernel(const uint32_t* __restrict__
 template <int OP = 0>
 hipError_t launch(int op, const uint32_t* in, size_t n, uint32_t* out) {
   if (op == OP) {
-    devops_kernel<OP><<<dim3((unsigned)((n + 63) / 64)), dim3(64)>>>(in, n, out);
-    return hipGetLastError();
+    if constexpr (devops::Op<OP>::carried) {
+      devops_kernel<OP><<<dim3((unsigned)((n + 63) / 64)), dim3(64)>>>(in, n, out);
+      return hipGetLastError();
+    } else {
+      return hipErrorInvalidValue;
+    }
   }
   if constexpr (OP + 1 < devops::NOPS) return launch<OP + 1>(op, in, n, out);
   return hipErrorInvalidValue;
@@ -58,11 +66,16 @@ hipError_t launch(int op, const uint32_t* in, size_t n, uint32_t* out) {
 #define DEVOPS_CAT2(a, b) a##b
 #define DEVOPS_CAT(a, b) DEVOPS_CAT2(a, b)
 
-// allocate, copy in, ONE launch, copy out, free.  -> the HIP error code (0 = ok), -1 = unknown op / bad argument
+// whether this variant carries the op: 1 / 0
+extern "C" int DEVOPS_CAT(devops_carries_, DEVOPS_VARIANT)(int op) { return devops::carries(op) ? 1 : 0; }
+
+// allocate, copy in, ONE launch, copy out, free.  -> the HIP error code (0 = ok), -1 = unknown op / bad argument,
+// -2 = an op this variant does not carry
 extern "C" int DEVOPS_CAT(devops_run_, DEVOPS_VARIANT)(int op, const void* in, size_t n, void* out) {
   const char* name;
   uint32_t inw, outw;
   if (!devops::info(op, name, inw, outw) || !in || !out || n > (size_t(1) << 24)) return -1;
+  if (!devops::carries(op)) return -2;
   if (n == 0) return 0;
   const size_t inb = n * inw * 4, outb = n * outw * 4;
   uint32_t *din = nullptr, *dout = nullptr;
@@ -84,6 +97,10 @@ int devops_run_g1acc(int, const void*, size_t, void*);
 int devops_run_serial(int, const void*, size_t, void*);
 int devops_run_g2acc(int, const void*, size_t, void*);
 int devops_run_calls(int, const void*, size_t, void*);
+int devops_carries_g1acc(int);
+int devops_carries_serial(int);
+int devops_carries_g2acc(int);
+int devops_carries_calls(int);
 int devops_nops() { return devops::NOPS; }
 int devops_nvariants() { return 5; }
 const char* devops_variant_name(int v) {
@@ -93,6 +110,17 @@ const char* devops_variant_name(int v) {
 // op -> name, words per tuple in and out.  -> 0, or -1 for an unknown op
 int devops_info(int op, const char** name, uint32_t* in_words, uint32_t* out_words) {
   return devops::info(op, *name, *in_words, *out_words) ? 0 : -1;
+}
+// 1 / 0, or -1 for an unknown variant
+int devops_carries(int variant, int op) {
+  switch (variant) {
+    case 0: return devops_carries_plain(op);
+    case 1: return devops_carries_g1acc(op);
+    case 2: return devops_carries_serial(op);
+    case 3: return devops_carries_g2acc(op);
+    case 4: return devops_carries_calls(op);
+    default: return -1;
+  }
 }
 int devops_run(int variant, int op, const void* in, size_t n, void* out) {
   switch (variant) {

@@ -1,10 +1,11 @@
-// Test-only: the field / curve primitives of ff.cuh, ff29.cuh, ec.cuh, ec29.cuh (and, under hipcc, msm_digits of
-// msm.cuh) as numbered ops over flat 32-bit word buffers.  One call of Op<ID>::run handles ONE operand tuple of
-// Op<ID>::in_words words and writes Op<ID>::out_words words.  FF_HD code only: included by the g++ shim
-// (tests/cpu_kernels/ffec_shim.cpp: the portable branches of the headers) and by tests/kernels/devops.hip (one kernel
-// per op, one lane per tuple: the branches the GPU runs).  tests/device_ops.py builds the operands and the expected
-// words from plain integers.  Every op is straight-line or has a fixed trip count, except the ones that reach
-// Field::inv (field "inv", fp2 "inv", the to_affine at the end of the curve ops): canonical operands only.
+// Test-only: the field / curve primitives of ff.cuh, ff29.cuh, ec.cuh, ec29.cuh, the tower and loops of pairing.cuh
+// (and, under hipcc, msm_digits of msm.cuh) as numbered ops over flat 32-bit word buffers.  One call of Op<ID>::run
+// handles ONE operand tuple of Op<ID>::in_words words and writes Op<ID>::out_words words.  FF_HD code only: included by
+// the g++ shim (tests/cpu_kernels/devops_shim.cpp: the portable branches of the headers) and by tests/kernels/devops.hip
+// (one kernel per op, one lane per tuple: the branches the GPU runs).  tests/device_ops.py builds the operands and the
+// expected words from plain integers.  Every op is straight-line or has a fixed trip count, except the ones that reach
+// Field::inv (field "inv", fp2 "inv", the to_affine at the end of the curve ops, the pairing ops that invert):
+// canonical operands only.
 //
 // The including file has the headers included and `using namespace g16` is NOT assumed: everything is qualified.
 namespace devops {
@@ -22,12 +23,16 @@ FF_HD void stw(uint32_t* p, const T& t) {
 
 template <int OP>
 struct Op;
-#define DEVOP(ID, NAME, INW, OUTW)                                     \
+// carried: whether this build runs the op.  An op that is not carried keeps its number, name and sizes, its run() is
+// never instantiated into a kernel, and running it is an error (see DEVOPS_PAIRING below).
+#define DEVOP_IF(CARRIED, ID, NAME, INW, OUTW)                         \
   template <>                                                          \
   struct Op<ID> {                                                      \
     static constexpr const char* name() { return NAME; }               \
     static constexpr uint32_t in_words = (INW), out_words = (OUTW);    \
+    static constexpr bool carried = (CARRIED);                         \
     static FF_HD void run(const uint32_t* in, uint32_t* out)
+#define DEVOP(ID, NAME, INW, OUTW) DEVOP_IF(true, ID, NAME, INW, OUTW)
 #define DEVOP_END };
 
 // ---- Field<Fp> / Field<Fr>, 8 x 32 -----------------------------------------------------------------------------
@@ -264,10 +269,104 @@ DEVOP(35, "g2_tab29", 32, 64) {
   stw(out + 32, E::pack(E::unpack(t)));
 } DEVOP_END
 
+// ---- Pairing of pairing.cuh: the Fp12 tower, the Miller loop, the final exponentiation ------------------------------
+// An Fp12 element is 96 words: g[0..5], six Fp2 values over w^k in Montgomery form (what g16_pairing returns); an Fp6
+// element is 48 words, c[0..2] over v = w^2.  None of the arithmetic configuration macros reaches pairing.cuh except
+// G16_FP2_CALLS, so only the builds whose configuration ships pairing.o carry these ops: the including file may define
+// DEVOPS_PAIRING as 0 to leave them out (number, name and sizes stay, so the table is the same in every build).
+// f12_inv, f6_inv, pair_miller and pair_final_exp reach Fp2::inv: canonical operands, and no zero into an inversion.
+#if !defined(DEVOPS_PAIRING)
+#define DEVOPS_PAIRING 1
+#endif
+#define DEVOP_PAIRING(ID, NAME, INW, OUTW) DEVOP_IF(DEVOPS_PAIRING != 0, ID, NAME, INW, OUTW)
+using PR = g16::Pairing;
+FF_HD g16::fp12_t ld12(const uint32_t* in) { return ldw<g16::fp12_t>(in); }
+
+// (a, b) -> mul(a, b), mul(b, a)
+DEVOP_PAIRING(36, "f12_mul", 192, 192) {
+  const g16::fp12_t a = ld12(in), b = ld12(in + 96);
+  g16::fp12_t r;
+  PR::mul(r, a, b);
+  stw(out, r);
+  PR::mul(r, b, a);
+  stw(out + 96, r);
+} DEVOP_END
+// a -> sqr in place (as the Miller loop and pow_u64 call it), mul(a, a)
+DEVOP_PAIRING(37, "f12_sqr", 96, 192) {
+  const g16::fp12_t a = ld12(in);
+  g16::fp12_t r = a;
+  PR::sqr(r, r);
+  stw(out, r);
+  PR::mul(r, a, a);
+  stw(out + 96, r);
+} DEVOP_END
+// (f, l0 in Fp, l1, l3 in Fp2) -> f * (l0 + l1 w + l3 w^3)
+DEVOP_PAIRING(38, "f12_mul_line", 96 + 8 + 16 + 16, 96) {
+  g16::fp12_t f = ld12(in);
+  PR::mul_line(f, ldw<g16::u256>(in + 96), ldw<g16::fp2_t>(in + 104), ldw<g16::fp2_t>(in + 120));
+  stw(out, f);
+} DEVOP_END
+// a -> conj(a), frobenius(a, 1), frobenius(a, 2), frobenius(a, 3)
+DEVOP_PAIRING(39, "f12_frob", 96, 4 * 96) {
+  const g16::fp12_t a = ld12(in);
+  g16::fp12_t r = a;
+  PR::conj(r);
+  stw(out, r);
+  for (int n = 1; n <= 3; ++n) {
+    r = a;
+    PR::frobenius(r, n);
+    stw(out + 96 * n, r);
+  }
+} DEVOP_END
+DEVOP_PAIRING(40, "f6_mul", 96, 48) {
+  g16::fp6_t r;
+  PR::f6mul(r, ldw<g16::fp6_t>(in), ldw<g16::fp6_t>(in + 48));
+  stw(out, r);
+} DEVOP_END
+DEVOP_PAIRING(41, "f6_inv", 48, 48) {   // a != 0
+  g16::fp6_t r;
+  PR::f6inv(r, ldw<g16::fp6_t>(in));
+  stw(out, r);
+} DEVOP_END
+DEVOP_PAIRING(42, "f12_inv", 96, 96) {   // a != 0
+  g16::fp12_t r;
+  PR::inv(r, ld12(in));
+  stw(out, r);
+} DEVOP_END
+// (a, e: low word, high word) -> a^e
+DEVOP_PAIRING(43, "f12_pow_u64", 96 + 2, 96) {
+  g16::fp12_t r;
+  PR::pow_u64(r, ld12(in), (uint64_t)in[96] | ((uint64_t)in[97] << 32));
+  stw(out, r);
+} DEVOP_END
+// a -> a^6, a^12, a^18, a^30, a^36
+DEVOP_PAIRING(44, "f12_small_pows", 96, 5 * 96) {
+  PR::Pows p;
+  PR::small_pows(p, ld12(in));
+  stw(out, p.p6);
+  stw(out + 96, p.p12);
+  stw(out + 192, p.p18);
+  stw(out + 288, p.p30);
+  stw(out + 384, p.p36);
+} DEVOP_END
+DEVOP_PAIRING(45, "f12_is_one", 96, 1) { out[0] = PR::is_one(ld12(in)) ? 1u : 0u; } DEVOP_END
+// (P affine in G1, Q affine on the twist) -> the Miller value f_{6x^2,Q}(P), before the final exponentiation
+DEVOP_PAIRING(46, "pair_miller", 16 + 32, 96) {
+  g16::fp12_t f;
+  PR::miller(f, ldw<g16::g1_aff>(in), ldw<g16::g2_aff>(in + 16));
+  stw(out, f);
+} DEVOP_END
+DEVOP_PAIRING(47, "pair_final_exp", 96, 96) {   // f != 0
+  g16::fp12_t r;
+  PR::final_exp(r, ld12(in));
+  stw(out, r);
+} DEVOP_END
+#undef DEVOP_PAIRING
+
 #if defined(__HIPCC__) && defined(DEVOPS_WITH_MSM)
 // ---- msm_digits (msm.cuh; device only) ------------------------------------------------------------------------------
 // in: c, mtab, scalars_mont, pad, scalar.  out: count, then per digit  neg << 31 | window (+ selector * nwin) << 24 | bucket
-DEVOP(36, "msm_digits", 12, 64) {
+DEVOP(48, "msm_digits", 12, 64) {
 #if defined(__HIP_DEVICE_COMPILE__)
   g16::MsmParams P{};
   P.n = 1;
@@ -288,12 +387,13 @@ DEVOP(36, "msm_digits", 12, 64) {
   out[0] = 0;
 #endif
 } DEVOP_END
-constexpr int NOPS = 37;
+constexpr int NOPS = 49;
 #else
-constexpr int NOPS = 36;
+constexpr int NOPS = 48;
 #endif
 
 #undef DEVOP
+#undef DEVOP_IF
 #undef DEVOP_END
 
 // op -> (name, words in, words out) and the call itself, by linear template recursion
@@ -306,6 +406,13 @@ inline bool info(int op, const char*& name, uint32_t& inw, uint32_t& outw) {
     return true;
   }
   if constexpr (OP + 1 < NOPS) return info<OP + 1>(op, name, inw, outw);
+  return false;
+}
+// whether this build runs the op
+template <int OP = 0>
+inline bool carries(int op) {
+  if (op == OP) return Op<OP>::carried;
+  if constexpr (OP + 1 < NOPS) return carries<OP + 1>(op);
   return false;
 }
 

@@ -1,22 +1,17 @@
 """GPU parity for the verifier row through the C ABI: the raw ate pairing bit-exact against the
 oracle, and verifyProof on the reference's toy circuit (tests/groth16/testProver.nim:59-73: prove -> verify),
-incl. the negative cases (tampered proof / public input, malformed points, subgroup check)."""
+incl. the negative cases (tampered proof / public input, malformed points, subgroup check); instances built in log
+space (points at infinity on every side, vk_x at infinity, edge public inputs, no public input, a B of small order)
+with the verdict of the oracle's Miller loop and final exponentiation on the same points."""
 import pytest
 
 from oracle import bn254_ref as o
+from tests import device_ops as D
 from tests import inputs as I
 
 pytestmark = pytest.mark.gpu
 
-
-def _gt(raw):
-    """384-byte flat Fp12 (6 x Fp2 over w^k, Montgomery) -> the oracle's degree-12 polynomial basis"""
-    out = [0] * 12
-    for k in range(6):
-        a = o.fp_from_mont_bytes(raw[64 * k:64 * k + 32])
-        b = o.fp_from_mont_bytes(raw[64 * k + 32:64 * k + 64])
-        out = [(x + y) % o.P for x, y in zip(out, o._emb((a, b), k))]
-    return out
+_gt = D.gt_from_bytes       # 384-byte flat Fp12 (6 x Fp2 over w^k, Montgomery) -> the oracle's degree-12 polynomial basis
 
 
 def test_pairing_vs_oracle_and_bilinear(ctx):
@@ -154,3 +149,141 @@ def _fp2_sqrt(a):
             if o.fp2_sqr((x0, x1)) == (a[0] % p, a[1] % p):
                 return (x0, x1)
     return None
+
+
+# ---- instances built in log space: the verdict is known without a prover ----------------------------------------------
+# A = a G1, B = b G2, C = c G1, alpha1 = alpha G1, beta2 = beta G2, gamma2 = gamma G2, delta2 = delta G2, IC_i = ic_i G1:
+#   e(-A, B) e(alpha1, beta2) e(C, delta2) e(sum pub_i IC_i, gamma2) = 1   <=>   -ab + alpha beta + c delta + x gamma = 0
+# (mod r), x = sum pub_i ic_i with pub_0 = 1.
+class _LogKey:
+    def __init__(self, ctx, seed, npubs):
+        from nim_groth16_amd.verifier import VKey, loadVerifyingKey
+        from nim_groth16_amd.zkey_types import SpecPoints
+        rng = o.SplitMix64(seed)
+        self.alpha, self.beta, self.gamma, self.delta = (rng.fr() or 1 for _ in range(4))
+        self.ics = [rng.fr() or 1 for _ in range(npubs + 1)]
+        self.rng = rng
+        self.alpha1, self.beta2 = o.G1.mul(self.alpha, o.GEN1), o.G2.mul(self.beta, o.GEN2)
+        self.gamma2, self.delta2 = o.G2.mul(self.gamma, o.GEN2), o.G2.mul(self.delta, o.GEN2)
+        self.ic = [o.G1.mul(k, o.GEN1) for k in self.ics]
+        spec = SpecPoints(alpha1=o.g1_to_bytes(self.alpha1), beta2=o.g2_to_bytes(self.beta2),
+                          gamma2=o.g2_to_bytes(self.gamma2), delta2=o.g2_to_bytes(self.delta2))
+        self.dev = loadVerifyingKey(VKey("bn128", spec, b"".join(o.g1_to_bytes(q) for q in self.ic)), ctx)
+        self.ab = D.miller_ref(self.alpha1, self.beta2)
+
+    def x(self, pubs):
+        return sum(p * k for p, k in zip(pubs, self.ics)) % o.R
+
+    def solve_c(self, a, b, pubs):
+        return (a * b - self.alpha * self.beta - self.x(pubs) * self.gamma) * pow(self.delta, -1, o.R) % o.R
+
+    def solve_a(self, b, c, pubs):
+        return (self.alpha * self.beta + c * self.delta + self.x(pubs) * self.gamma) * pow(b, -1, o.R) % o.R
+
+    def holds(self, a, b, c, pubs):
+        return (-a * b + self.alpha * self.beta + c * self.delta + self.x(pubs) * self.gamma) % o.R == 0
+
+    def oracle_status(self, A, B, C, pubs):
+        """the pairing product of verifier.nim:31-52 with the oracle's Miller loop and final exponentiation"""
+        vk_x = o.G1.msm_naive(pubs, self.ic)
+        f = list(self.ab)
+        for Pt, Q in ((o.G1.neg(A), B), (C, self.delta2), (vk_x, self.gamma2)):
+            f = o._f12_mul(f, o.miller_loop(Pt, Q))
+        return 1 if o.final_exp(f) == o._f12_one() else 0
+
+
+def _run_instances(key, insts, subgroup=False):
+    """insts: (A, B, C, pubs, expected status).  Each alone and all in one batch (twice over, so that lanes differ),
+    with the public inputs in Montgomery and in standard form: the same statuses"""
+    proofs = [(o.g1_to_bytes(A), o.g2_to_bytes(B), o.g1_to_bytes(C)) for A, B, C, _, _ in insts]
+    want = [e for *_, e in insts]
+    for mont in (True, False):
+        enc = I.fr_mont_bytes if mont else (lambda xs: b"".join(o.fr_to_std_bytes(x) for x in xs))
+        pub = [enc(pubs) for _, _, _, pubs, _ in insts]
+        for i in range(len(insts)):
+            assert key.dev.verify([proofs[i]], pub[i], mont=mont, subgroup=subgroup) == [want[i]], (i, mont)
+        order = list(range(len(insts))) + list(reversed(range(len(insts))))
+        st = key.dev.verify([proofs[i] for i in order], b"".join(pub[i] for i in order), mont=mont, subgroup=subgroup)
+        assert st == [want[i] for i in order], (mont, st)
+
+
+LOG_CASES = ("A_inf", "C_inf", "B_inf", "vk_x_inf", "pub_0_and_r_minus_1", "npubs_0")
+
+
+@pytest.mark.parametrize("case", LOG_CASES)
+def test_verify_log_space_instances(ctx, case):
+    """an accepting instance and a neighbour that is off by one in a single scalar; the expected status is the
+    oracle's verdict on the same points, and it is 1 and 0 as the scalars say"""
+    key = _LogKey(ctx, 40 + LOG_CASES.index(case), 0 if case == "npubs_0" else 2)
+    rng = key.rng
+    a, b, c = rng.fr() or 1, rng.fr() or 1, rng.fr() or 1
+    pubs = [1] + [rng.fr() for _ in range(len(key.ics) - 1)]
+    if case == "A_inf":
+        a = 0
+    elif case == "B_inf":
+        b = 0
+    elif case == "vk_x_inf":      # the public inputs cancel IC_0
+        pubs[1] = -(key.ics[0] + pubs[2] * key.ics[2]) * pow(key.ics[1], -1, o.R) % o.R
+        assert key.x(pubs) == 0
+    elif case == "pub_0_and_r_minus_1":
+        pubs = [1, 0, o.R - 1]
+    if case == "C_inf":
+        c = 0
+        a = key.solve_a(b, c, pubs)
+        scalars = [(a, b, c, pubs), ((a + 1) % o.R, b, c, pubs)]
+    else:
+        c = key.solve_c(a, b, pubs)
+        scalars = [(a, b, c, pubs), (a, b, (c + 1) % o.R, pubs)]
+    if case == "vk_x_inf":
+        scalars.append((a, b, c, [1, (pubs[1] + 1) % o.R, pubs[2]]))
+    elif case == "pub_0_and_r_minus_1":
+        scalars += [(a, b, c, [1, 1, o.R - 1]), (a, b, c, [1, 0, o.R - 2])]
+    insts = []
+    for k, (a_, b_, c_, pubs_) in enumerate(scalars):
+        A, B, C = o.G1.mul(a_, o.GEN1), o.G2.mul(b_, o.GEN2), o.G1.mul(c_, o.GEN1)
+        status = key.oracle_status(A, B, C, pubs_)
+        assert status == (1 if k == 0 else 0) and key.holds(a_, b_, c_, pubs_) == (k == 0)
+        insts.append((A, B, C, pubs_, status))
+    A, B, C, pubs0, _ = insts[0]
+    assert {"A_inf": A == o.INF_G1, "B_inf": B == o.INF_G2, "C_inf": C == o.INF_G1,
+            "vk_x_inf": o.G1.msm_naive(pubs0, key.ic) == o.INF_G1}.get(case, True)
+    _run_instances(key, insts)
+    _run_instances(key, insts, subgroup=True)       # every B here is in the subgroup (or at infinity)
+    key.dev.destroy()
+
+
+def test_verify_b_of_small_order(ctx):
+    """B of order 10069 on the twist (the G2 cofactor 2p - r is 10069 x a 241-bit number): without the subgroup flag
+    the status is the oracle's verdict on that pairing product, with it -4; next to an accepting instance"""
+    key = _LogKey(ctx, 50, 2)
+    rng = key.rng
+    small, _ = D.twist_points()
+    a, b = rng.fr() or 1, rng.fr() or 1
+    pubs = [1, rng.fr(), rng.fr()]
+    c = key.solve_c(a, b, pubs)
+    A, C = o.G1.mul(a, o.GEN1), o.G1.mul(c, o.GEN1)
+    good = (A, o.G2.mul(b, o.GEN2), C, pubs)
+    rogue = (A, small, C, pubs)
+    st_good, st_rogue = key.oracle_status(*good), key.oracle_status(*rogue)
+    assert st_good == 1 and st_rogue == 0     # a product with a factor outside GT's order-r structure is not 1
+    _run_instances(key, [good + (st_good,), rogue + (st_rogue,)])
+    _run_instances(key, [good + (1,), rogue + (-4,)], subgroup=True)
+    key.dev.destroy()
+
+
+def test_pairing_batch_with_infinities_across_block_boundaries(ctx):
+    """131 pairs in one g16_pairing call (three 64-lane blocks, the last one partial), infinity on either side or both at
+    lanes 0, 63, 64, 127 and the last; every finite lane is one of three pairs whose oracle value is computed once"""
+    rng = o.SplitMix64(61)
+    distinct = [(o.GEN1, o.GEN2), (o.G1.mul(rng.fr(), o.GEN1), o.G2.mul(rng.fr(), o.GEN2)),
+                (o.G1.neg(o.G1.mul(rng.fr(), o.GEN1)), o.G2.mul(rng.fr(), o.GEN2))]
+    want = [o.final_exp(list(D.miller_ref(p, q))) for p, q in distinct]
+    n = 131
+    infs = {0: (o.INF_G1, distinct[0][1]), 63: (distinct[1][0], o.INF_G2), 64: (o.INF_G1, o.INF_G2),
+            127: (o.INF_G1, distinct[2][1]), n - 1: (distinct[2][0], o.INF_G2)}
+    lanes = [infs.get(i, distinct[(i + i // 64) % 3]) for i in range(n)]
+    raw = ctx.pairing(b"".join(o.g1_to_bytes(p) for p, _ in lanes), b"".join(o.g2_to_bytes(q) for _, q in lanes))
+    assert len(raw) == 384 * n
+    for i in range(n):
+        exp = o._f12_one() if i in infs else want[(i + i // 64) % 3]
+        assert _gt(raw[384 * i:384 * i + 384]) == exp, i
