@@ -11,56 +11,12 @@
 #include <vector>
 
 
+#include "g16_env.hpp"
 #include "hip_owners.hpp"
 #include "msm_params.hpp"
+#include "msm_plan.hpp"
 
-// Experiment knobs (G16_* environment variables), read ONCE per process -- at the first g16_ctx_create -- and never
-// again on the per-proof path.  0 / '\0' = not set.
-struct G16Env {
-  int msm_window = 0;      // G16_MSM_WINDOW   5..22: window bits of the one-shot MSMs
-  int table_window = 0;    // G16_TABLE_WINDOW 5..22: window bits of registered point sets
-  int msm_seg = 0;         // G16_MSM_SEG      8..4096: accumulate segment length
-  char msm_sort = 0;       // G16_MSM_SORT     'a': atomic histogram/scatter instead of the partition sort
-  int g1_lanes[3] = {3, 2, 0};   // G16_G1_LANES  lanes of the A1 / B1 / C1 MSMs (three digits from {0,2,3}).  C1 goes first,
-                                 // on the sort's own lane: the H accumulation continues C1's bucket sums, so a late C1
-                                 // delays the last chain of the proof (single-proof latency 11.2 -> 10.8 ms, same
-                                 // throughput: profiles/r04_ab_g1_lanes.txt; rounds 1-3: 0, 2, 3)
-  char stream_prio[7] = "lhllln";   // G16_STREAM_PRIO  six characters from {h, n, l}
-  int red_slice_log2 = 0;  // G16_RED_SLICE    log2 of the chunks per reduce2 slice of a merged bucket set (8..11)
-  int inf_compact_pct = 10;   // G16_INF_COMPACT  point sets with at least this percentage of (0,0) points get their own
-                              // entry lists without them (0: always, 101: never); prover.hip
-  int r2_width = -1;       // G16_R2_WIDTH  0: reduce2 with 512 / 256-thread workgroups, 1: 128 / 64, 2: 64 / 64; unset:
-                           // narrow inside proofs, wide for stand-alone MSMs (msm_stage.cuh)
-  int ntt_tile = 2048;            // G16_NTT_TILE = 1024 | 2048 | 4096: NTT workgroup geometry (ntt.cuh)
-  // launch order of a proof (the defaults are the measured optimum: profiles/r05_ab_quotient_first*.txt):
-  int quotient_first = 1;         // G16_QUOTIENT_FIRST=0: enqueue the witness MSMs before buildABC + quotient + sort(qs) (rounds 1-4)
-  int lanes_after_quotient = 0;   // G16_LANES_AFTER_QUOTIENT=1 (with the above): the witness accumulations wait for them
-  int g1_batch = 0;               // G16_G1_BATCH=1: ONE batched launch sequence (blockIdx.y = MSM) for A1, B1, C1 on one stream
-                                  // instead of one stream and one sequence per G1 MSM (prover.hip; measured slower)
-  int mtab = 2;                   // G16_MTAB=1: registered sets without the second multiplier table / class bucket set
-  int chain_ch = 1;               // G16_CHAIN_CH=0: C1 and H1 as two MSMs instead of H1 continuing C1's bucket sums
-  int tail_quad = 1;              // G16_TAIL_QUAD=0: reduce2 / fold with one lane per slot instead of a cooperating quad (msm.cuh,
-                                  // msm_stage.cuh)
-  int red_chunk = 0;              // G16_RED_CHUNK = 2 | 4 | 8 | 16: buckets per thread of msm_reduce1 (unset: msm_red_chunk)
-  int cu_split = 0;               // G16_CU_SPLIT=k (1..24): main stream on k CUs per XCD, MSM lanes on the other 32 - k (g16hip.hip)
-  int heavy_grid = 0;             // G16_HEAVY_GRID: workgroups of msm_heavy (unset: 1024 / 512; msm_stage.cuh)
-  int cz_on_the_fly = 1;          // G16_CZ_FLY=0: buildABC writes Cz with a kernel of its own instead of the quotient's first
-                                  // pass forming it while loading (ntt.cuh mul_src)
-  int abc_dict = 1;               // G16_ABC_DICT=0: buildABC reads a 32-byte value per entry even when the key's coefficients
-                                  // come from a small set (spmv.hip: value dictionary)
-  int g2_first = -1;              // G16_G2_FIRST = 0 | 1 | 2: A1 and B1 (2: C1 too) accumulate after B2 (unset: 1 for small shards,
-                                  // prover.hip)
-};
-const G16Env& g16_env();
-
-// Buckets per thread of the first reduction stage (msm_reduce1).  16 keeps the chunk records (two accumulators per
-// chunk) and reduce2's work small where the reduction is throughput: a 2^20 proof's 352 k buckets.  A small bucket set
-// (a shard's point sets, a small MSM) is a latency chain on a mostly empty GPU: with 4 the chain of reduce1 is 8
-// additions instead of 32 and reduce2, run wide, pays 2 more scan steps (a G2 addition is ~20 us of wave time).
-inline uint32_t msm_red_chunk(const g16::MsmParams& P) {
-  if (g16_env().red_chunk) return (uint32_t)g16_env().red_chunk;
-  return P.nbuckets <= (1u << 17) ? 4u : 16u;
-}
+const G16Env& g16_env();   // g16hip.hip: the knobs of this process
 
 struct ProfEntry {
   const char* name;
@@ -86,7 +42,7 @@ struct g16_ctx {
   struct MsmSort {
     Buf buf;
     g16::MsmParams P;
-    bool narrow_tail = false;   // reduce2 geometry: see stage_reduce2_fold, msm_stage.cuh (set by the prover's lanes: throughput)
+    bool narrow_tail = false;   // reduce2 geometry: an input of msm_tail_plan, msm_plan.hpp (set by the prover's lanes: throughput)
     uint32_t *count = nullptr, *cursor = nullptr, *offset = nullptr, *xoff = nullptr, *heavy = nullptr,
              *info = nullptr, *entries = nullptr, *perm = nullptr, *ghist = nullptr, *blk_base = nullptr, *tile_hist = nullptr;
     uint2* tmp = nullptr;
@@ -251,9 +207,6 @@ struct g16_points {
 // the live bitmap of a registered set if it holds enough (0,0) points for its own entry lists to pay (G16_INF_COMPACT;
 // g16hip.hip)
 const uint32_t* g16_points_live_if_sparse(const g16_points* p);
-// window bits / multiplier tables of a registered set of n points (the cost model of msm_sort.hip)
-uint32_t g16_pick_table_window(size_t n);
-uint32_t g16_pick_mtab(uint32_t c);
 // the two halves of an MSM: (1) arrange one scalar vector into buckets, (2) accumulate + reduce a point set
 // against that arrangement.  Several point sets may share one sort (same scalars, same n, same c).
 // table_c == 0: plain point arrays; else g16_points::cfg() of the registered sets that will run against the sort
@@ -300,12 +253,15 @@ int32_t msm_device(g16_ctx* ctx, const void* d_scalars, uint32_t flags, const vo
 // the stages of phase 2 over the first `ny` jobs of a batch
 template <class C>
 int32_t stage_accum(g16_ctx* ctx, hipStream_t st, const g16::MsmParams& P, const g16::MsmBatch<C>& B, uint32_t ny);
+// T: the tail plan of the batch (msm_plan.hpp), built once by msm_batch
 template <class C>
-int32_t stage_heavy(g16_ctx* ctx, hipStream_t st, const g16::MsmParams& P, const g16::MsmBatch<C>& B, uint32_t ny);
+int32_t stage_heavy(g16_ctx* ctx, hipStream_t st, const g16::MsmParams& P, const g16::MsmTailPlan& T,
+                    const g16::MsmBatch<C>& B, uint32_t ny);
 template <class C>
-int32_t stage_reduce1(g16_ctx* ctx, hipStream_t st, const g16::MsmParams& P, const g16::MsmBatch<C>& B, uint32_t ny);
+int32_t stage_reduce1(g16_ctx* ctx, hipStream_t st, const g16::MsmParams& P, const g16::MsmTailPlan& T,
+                      const g16::MsmBatch<C>& B, uint32_t ny);
 template <class C>
-int32_t stage_reduce2_fold(g16_ctx* ctx, hipStream_t st, const g16::MsmParams& P, bool narrow_tail,
+int32_t stage_reduce2_fold(g16_ctx* ctx, hipStream_t st, const g16::MsmParams& P, const g16::MsmTailPlan& T,
                            const g16::MsmBatch<C>& B, uint32_t ny);
 // reference-layout points -> reduced-radix entries (one-shot MSMs) / window tables (registered sets)
 template <class C>

@@ -274,9 +274,9 @@ static int32_t points_register(g16_ctx* ctx, const void* points, size_t n, bool 
   h->device = ctx->device;
   h->group = group_of<C>;
   h->n = n;
-  h->c = g16_pick_table_window(n);
+  h->c = msm_pick_table_window(n, g16_env());
   h->nwin = 254 / h->c + 1;
-  h->mtab = g16_pick_mtab(h->c);
+  h->mtab = msm_pick_mtab(h->c, g16_env());
   constexpr size_t psz = sizeof(typename C::Aff);
   // Two multiplier tables per window double the set's HBM footprint (~10 GB for a 2^20 key, ~40 GB at 2^22): a set
   // that does not fit that way -- table indices beyond 31 bits, or no room in HBM -- falls back to one table per window

@@ -23,7 +23,6 @@
 
 namespace g16 {
 
-constexpr int MSM_BLOCK = 256;
 #ifndef G16_ACC_BLOCK
 #define G16_ACC_BLOCK 256
 #endif
@@ -31,7 +30,6 @@ constexpr int ACC_BLOCK = G16_ACC_BLOCK;   // workgroup size of the accumulate k
 #ifndef G16_G2_WAVES
 #define G16_G2_WAVES 2
 #endif
-constexpr int FR_BITS = 254;
 
 // Wave priority of the latency-bound kernels (split-bucket combine, reduce, fold; the sort): their few waves share the
 // SIMDs with the register-filling accumulate waves of the other streams, and every instruction they wait for the
@@ -201,20 +199,7 @@ __device__ __forceinline__ uint32_t lds_rank_add(uint32_t* ctr, uint32_t key) {
   return atomicAdd(&ctr[key], 1u);
 }
 
-// 1024 threads x 4 scalars: the pass is a chain of dependent LDS atomics and scattered 8-byte stores per thread, and a
-// 2^20-scalar sort has only 256 tiles -- one workgroup per CU -- so the workgroup is as wide as it gets (16 waves per
-// CU hide that latency; rounds 1-2 ran 256 threads x 16 scalars = ONE wave per SIMD)
-// Low bucket bits sorted inside a partition (bucket_hist / bucket_place: one thread per low value).  Round 4: 9 instead
-// of 8 -- half as many partitions (688 for the class set of c = 20), hence half as many (tile, partition) runs that
-// part_pass<true> keeps open at once: 32 tiles per XCD x 1376 runs x one active 128-byte line were 5.6 MB against a
-// 4-MB L2, and lines left the L2 half written (WRITE_SIZE 3.4 x the record bytes); 688 runs are 2.8 MB.
-constexpr int BS_LOG = 9;
-constexpr int BS_LOW = 1 << BS_LOG;
-constexpr int PART_BLOCK = 1024;
-constexpr int PART_PER_THREAD = 4;
-constexpr int PART_TILE = PART_BLOCK * PART_PER_THREAD;  // scalars per workgroup
-constexpr int PART_MAX = 8192;                           // max partitions (LDS histogram, 32 KB)
-
+// (the geometry of the partition sort -- PART_*, BS_LOG, BS_LOW -- and why it is what it is: msm_params.hpp)
 // tile of a partition pass: XCD x takes a contiguous range of tiles, so that neighbouring tiles -- whose (tile,
 // partition) runs of tmp records share cache lines at their ends -- mostly write through the same L2
 __device__ __forceinline__ uint32_t part_tile_of_block(uint32_t bid, uint32_t ntiles) {
@@ -286,7 +271,6 @@ static __global__ void __launch_bounds__(BS_LOW) bucket_hist(const uint2* __rest
 // launches for -- the extra-segment bookkeeping of split buckets (xoff[], heavy list; split buckets are rare, so
 // their range of extra-segment slots comes from one global atomic each instead of a device-wide scan) and the size
 // histogram of the permutation (perm_hist).
-constexpr int PERM_BINS = 256;   // size classes of the bucket-order permutation (perm_hist / perm_scatter below)
 // extra segments of a bucket of cnt entries cut into segments of L: max(ceil(cnt / L) - 1, 0)
 __device__ __forceinline__ uint32_t extra_segs(uint32_t cnt, uint32_t L) { return cnt > L ? (cnt - 1) / L : 0u; }
 static __global__ void __launch_bounds__(BS_LOW) bucket_place(const uint2* __restrict__ tmp,
@@ -364,9 +348,7 @@ static __global__ void __launch_bounds__(BS_LOW) bucket_place(const uint2* __res
 // ---- three-phase exclusive scan over the bucket histogram ------------------------------------------
 // produces offset[b] = sum_{b'<b} count[b'], xoff[b] = sum_{b'<b} extra(b') with
 // extra(b) = max(ceil(count/L) - 1, 0), and appends buckets with extra(b) > 0 to the heavy list.
-constexpr int SCAN_BLOCK = 256;
-constexpr int SCAN_ITEMS = 8;                       // per thread
-constexpr int SCAN_TILE = SCAN_BLOCK * SCAN_ITEMS;  // 2048 buckets per workgroup
+// (SCAN_BLOCK, SCAN_ITEMS, SCAN_TILE: msm_params.hpp)
 
 // split buckets with at least this many extra segments are combined by a workgroup (msm_heavy), the others by
 // one thread each (phase 1 of msm_heavy)
@@ -513,7 +495,6 @@ static __global__ void __launch_bounds__(MSM_BLOCK) msm_make_extra(const uint32_
 // (~70 % lane efficiency at avg 32).  perm[] lists the buckets by descending min(count, 255), so the 64
 // lanes of a wave get (nearly) equal trip counts.  Two small kernels: per-block LDS histogram + one global
 // atomic per (block, size class) to reserve a range, then ranks from LDS atomics.
-constexpr int PERM_BLOCK = BS_LOW;   // = one partition of the fused sort (bucket_place writes blk_base per partition)
 static __global__ void __launch_bounds__(PERM_BLOCK) perm_hist(const uint32_t* __restrict__ count, uint32_t nb,
                                                                uint32_t* __restrict__ ghist,
                                                                uint32_t* __restrict__ blk_base) {
@@ -690,7 +671,7 @@ __global__ void __launch_bounds__(heavy_block<C>(), tail_waves<C>()) msm_heavy(c
 
 // ---- K6: bucket reduction  S_w = sum_{k=1}^{K} k * B_{w,k},  K = 2^(c-1) -----------------------------
 // stage 1: thread per chunk of RC consecutive buckets: R_j = sum B_k, A_j = sum (k - j*RC) B_k
-// (RC = msm_red_chunk, g16_internal.hpp: 16, or 4 for small bucket sets)
+// (RC = msm_red_chunk, msm_plan.hpp: 16, or 4 for small bucket sets)
 // A job that continues another MSM's bucket sums (MsmJob::init): a bucket without entries of its own still
 // holds the other MSM's sum, so every bucket is added (infinity is skipped inside the addition).
 template <class C>

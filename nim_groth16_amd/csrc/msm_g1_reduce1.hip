@@ -1,4 +1,4 @@
 // G1 split-bucket combine and first bucket-reduction stage
 #include "msm_stage.cuh"
-template int32_t stage_heavy<G1>(g16_ctx*, hipStream_t, const MsmParams&, const MsmBatch<G1>&, uint32_t);
-template int32_t stage_reduce1<G1>(g16_ctx*, hipStream_t, const MsmParams&, const MsmBatch<G1>&, uint32_t);
+template int32_t stage_heavy<G1>(g16_ctx*, hipStream_t, const MsmParams&, const MsmTailPlan&, const MsmBatch<G1>&, uint32_t);
+template int32_t stage_reduce1<G1>(g16_ctx*, hipStream_t, const MsmParams&, const MsmTailPlan&, const MsmBatch<G1>&, uint32_t);

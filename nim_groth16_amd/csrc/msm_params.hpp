@@ -28,6 +28,30 @@ constexpr uint32_t MSM_CLASS_SLICES = 32 + 8 + 2 + 1;   // slices of 2^(c-7) buc
 #else
 #define G16_MSMP_HD inline
 #endif
+
+// ---- launch geometry that the kernels (msm.cuh) and the host sizing (msm_plan.hpp) both use ------------------------
+constexpr int MSM_BLOCK = 256;
+constexpr int FR_BITS = 254;
+// 1024 threads x 4 scalars: the pass is a chain of dependent LDS atomics and scattered 8-byte stores per thread, and a
+// 2^20-scalar sort has only 256 tiles -- one workgroup per CU -- so the workgroup is as wide as it gets (16 waves per
+// CU hide that latency; rounds 1-2 ran 256 threads x 16 scalars = ONE wave per SIMD)
+// Low bucket bits sorted inside a partition (bucket_hist / bucket_place: one thread per low value).  Round 4: 9 instead
+// of 8 -- half as many partitions (688 for the class set of c = 20), hence half as many (tile, partition) runs that
+// part_pass<true> keeps open at once: 32 tiles per XCD x 1376 runs x one active 128-byte line were 5.6 MB against a
+// 4-MB L2, and lines left the L2 half written (WRITE_SIZE 3.4 x the record bytes); 688 runs are 2.8 MB.
+constexpr int BS_LOG = 9;
+constexpr int BS_LOW = 1 << BS_LOG;
+constexpr int PART_BLOCK = 1024;
+constexpr int PART_PER_THREAD = 4;
+constexpr int PART_TILE = PART_BLOCK * PART_PER_THREAD;  // scalars per workgroup
+constexpr int PART_MAX = 8192;                           // max partitions (LDS histogram, 32 KB)
+constexpr int PERM_BINS = 256;   // size classes of the bucket-order permutation (perm_hist / perm_scatter, msm.cuh)
+constexpr int PERM_BLOCK = BS_LOW;   // = one partition of the fused sort (bucket_place writes blk_base per partition)
+// the three-phase exclusive scan over the bucket histogram (msm.cuh)
+constexpr int SCAN_BLOCK = 256;
+constexpr int SCAN_ITEMS = 8;                       // per thread
+constexpr int SCAN_TILE = SCAN_BLOCK * SCAN_ITEMS;  // 2048 buckets per workgroup
+
 // (partition, slice) of workgroup `bid` of bucket_hist / bucket_place; see msm.cuh
 constexpr int BS_SPLIT = 8;
 G16_MSMP_HD void bs_block(uint32_t bid, uint32_t nparts, uint32_t& part, uint32_t& q) {

@@ -53,6 +53,20 @@ static int32_t ntt_kernels_init(g16_ctx* ctx) {
   return G16_OK;
 }
 
+// The kernels of the three geometries (ntt.cuh), in the order small / mid / default: what ntt_batched launches for
+// G16_NTT_TILE = 1024 / 2048 / anything else.  (Within a row the fused last pass is named first: the order in which the
+// kernels are first named is their order in the code object, and it is kept as it was.)
+struct NttKernels {
+  uint32_t block;
+  decltype(&ntt_last_pass_abc<NTT_BLOCK, NTT_TILE>) last_pass_abc;
+  decltype(&ntt_pass<NTT_BLOCK>) pass;
+};
+static const NttKernels ntt_kernels[3] = {
+    {NTT_BLOCK_SMALL, ntt_last_pass_abc<NTT_BLOCK_SMALL, NTT_TILE_SMALL>, ntt_pass<NTT_BLOCK_SMALL>},
+    {NTT_BLOCK_MID, ntt_last_pass_abc<NTT_BLOCK_MID, NTT_TILE_MID>, ntt_pass<NTT_BLOCK_MID>},
+    {NTT_BLOCK, ntt_last_pass_abc<NTT_BLOCK, NTT_TILE>, ntt_pass<NTT_BLOCK>},
+};
+
 // `batch` independent transforms: in + b*in_stride -> out + b*out_stride (strides in elements).
 // `in` may equal `out` only for multi-pass sizes (log2n > NTT_MAX_RHO), where the first pass writes to a temporary.
 // scale: optional per-output-index factor applied in the last pass (replaces 1/n).
@@ -71,8 +85,9 @@ static int32_t ntt_batched(g16_ctx* ctx, const u256* in, size_t in_stride, u256*
     return G16_OK;  // n = 1: 1/n = 1 and eta^0 = 1
   }
   // passes of <= 10 stages: one up to 2^10, two up to 2^20, three beyond (small geometry: <= 8 stages per pass)
-  const bool small = g16_env().ntt_tile == NTT_TILE_SMALL, mid = g16_env().ntt_tile == NTT_TILE_MID;
-  const NttGeom geom = ntt_geom(g16_env().ntt_tile);
+  const int tile = g16_env().ntt_tile;
+  const NttGeom geom = ntt_geom(tile);
+  const NttKernels& K = ntt_kernels[tile == NTT_TILE_SMALL ? 0 : tile == NTT_TILE_MID ? 1 : 2];
   const uint32_t npass = ntt_npass(geom, log2n);
   u256 *tmpA = nullptr, *tmpB = nullptr;
   if (npass > 1) {
@@ -84,35 +99,17 @@ static int32_t ntt_batched(g16_ctx* ctx, const u256* in, size_t in_stride, u256*
   size_t src_stride = in_stride;
   for (uint32_t p = 0; p < npass; ++p) {
     const NttPass plan = ntt_pass_plan(geom, log2n, p);
-    const uint32_t rho = plan.rho, log2b = plan.log2b, log2s = plan.log2s, ntiles = plan.ntiles;
     const bool last = p + 1 == npass;
-    const size_t shmem = plan.shmem;
     if (last && fuse_abc) {
-      if (small)
-        KLAUNCH(ctx, "ntt_last_pass_abc", (ntt_last_pass_abc<NTT_BLOCK_SMALL, NTT_TILE_SMALL>), ntiles, NTT_BLOCK_SMALL,
-                shmem, src, out, (const u256*)ctx->ntt_tw.p(), log2n, log2s, rho, log2b, src_stride, fuse_abc == 2 ? 1 : 0);
-      else if (mid)
-        KLAUNCH(ctx, "ntt_last_pass_abc", (ntt_last_pass_abc<NTT_BLOCK_MID, NTT_TILE_MID>), ntiles, NTT_BLOCK_MID,
-                shmem, src, out, (const u256*)ctx->ntt_tw.p(), log2n, log2s, rho, log2b, src_stride, fuse_abc == 2 ? 1 : 0);
-      else
-        KLAUNCH(ctx, "ntt_last_pass_abc", (ntt_last_pass_abc<NTT_BLOCK, NTT_TILE>), ntiles, NTT_BLOCK, shmem, src, out,
-                (const u256*)ctx->ntt_tw.p(), log2n, log2s, rho, log2b, src_stride, fuse_abc == 2 ? 1 : 0);
+      KLAUNCH(ctx, "ntt_last_pass_abc", K.last_pass_abc, plan.ntiles, K.block, plan.shmem, src, out,
+              (const u256*)ctx->ntt_tw.p(), log2n, plan.log2s, plan.rho, plan.log2b, src_stride, fuse_abc == 2 ? 1 : 0);
       break;
     }
     u256* dst = last ? out : ((p & 1) ? tmpB : tmpA);
     const size_t dst_stride = last ? out_stride : n;
-    if (small)
-      KLAUNCH(ctx, inverse ? "ntt_pass_inv" : "ntt_pass_fwd", ntt_pass<NTT_BLOCK_SMALL>, dim3(ntiles, batch),
-              NTT_BLOCK_SMALL, shmem, src, dst, (const u256*)ctx->ntt_tw.p(), log2n, log2s, rho, log2b, inverse,
-              last ? 1 : 0, src_stride, dst_stride, last ? scale : (const u256*)nullptr, p == 0 ? c_from_ab : 0);
-    else if (mid)
-      KLAUNCH(ctx, inverse ? "ntt_pass_inv" : "ntt_pass_fwd", ntt_pass<NTT_BLOCK_MID>, dim3(ntiles, batch),
-              NTT_BLOCK_MID, shmem, src, dst, (const u256*)ctx->ntt_tw.p(), log2n, log2s, rho, log2b, inverse,
-              last ? 1 : 0, src_stride, dst_stride, last ? scale : (const u256*)nullptr, p == 0 ? c_from_ab : 0);
-    else
-      KLAUNCH(ctx, inverse ? "ntt_pass_inv" : "ntt_pass_fwd", ntt_pass<NTT_BLOCK>, dim3(ntiles, batch), NTT_BLOCK, shmem,
-              src, dst, (const u256*)ctx->ntt_tw.p(), log2n, log2s, rho, log2b, inverse, last ? 1 : 0, src_stride,
-              dst_stride, last ? scale : (const u256*)nullptr, p == 0 ? c_from_ab : 0);
+    KLAUNCH(ctx, inverse ? "ntt_pass_inv" : "ntt_pass_fwd", K.pass, dim3(plan.ntiles, batch), K.block, plan.shmem, src, dst,
+            (const u256*)ctx->ntt_tw.p(), log2n, plan.log2s, plan.rho, plan.log2b, inverse, last ? 1 : 0, src_stride,
+            dst_stride, last ? scale : (const u256*)nullptr, p == 0 ? c_from_ab : 0);
     src = dst;
     src_stride = dst_stride;
   }

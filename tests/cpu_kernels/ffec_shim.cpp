@@ -3,6 +3,7 @@
 #include "../../nim_groth16_amd/csrc/ec29.cuh"
 #include "../../nim_groth16_amd/csrc/pairing.cuh"
 #include "../../nim_groth16_amd/csrc/msm_params.hpp"
+#include "../../nim_groth16_amd/csrc/msm_plan.hpp"
 #include "../../nim_groth16_amd/csrc/spmv_params.hpp"
 #include "../../nim_groth16_amd/csrc/ntt_plan.hpp"
 #include <cstring>
@@ -108,6 +109,85 @@ uint32_t shim_ntt_plan(int tile, uint32_t log2n, uint64_t* out) {
     o[4] = q.shmem;
   }
   return npass;
+}
+
+// The MSM launch plan (msm_plan.hpp) of n pairs.  table_cfg 0: a plain MSM, 1: a registered set (window and multiplier
+// tables chosen as registration does).  knobs: {msm_window, table_window, msm_seg, msm_sort, red_slice_log2, r2_width,
+// mtab, tail_quad, red_chunk, heavy_grid} as G16Env holds them.  out:
+//   [0..8]   MsmParams  n c nwin nbuckets seg scalars_mont tables max_extra mtab
+//   [9..18]  sort plan  lo_bits nparts ptiles nth use_part fused nblk ntiles nt2 pblk
+//   [19..35] offsets of the 16 parts of the sort workspace, in order, and its size
+//   [36..45] G1 then G2: offsets of the 4 parts of a job workspace and its size
+//   [46..56] tail plan  rc nchunks nsets log2ks cps r2 r2_threads r2_lds fold heavy_grid(1) heavy_grid(3)
+// The mirrors of g16_ctx::MsmSort / MsmJob hold the parts as bytes; the carver runs over a base that is never touched.
+struct ShimSortParts {
+  char *count, *cursor, *offset, *xoff, *heavy, *info, *tiles, *entries, *xseg, *perm, *ghist, *blk_base, *tile_hist, *tmp,
+      *tiles2, *slice_hist;
+};
+struct ShimJobParts {
+  char *partial, *chunkR, *chunkA, *wsum;
+};
+static G16Env shim_env(const int* knobs) {
+  G16Env env;
+  env.msm_window = knobs[0];
+  env.table_window = knobs[1];
+  env.msm_seg = knobs[2];
+  env.msm_sort = (char)knobs[3];
+  env.red_slice_log2 = knobs[4];
+  env.r2_width = knobs[5];
+  env.mtab = knobs[6];
+  env.tail_quad = knobs[7];
+  env.red_chunk = knobs[8];
+  env.heavy_grid = knobs[9];
+  return env;
+}
+static void shim_tail_out(const MsmTailPlan& T, uint64_t* out) {
+  const uint64_t t[11] = {T.rc, T.nchunks, T.nsets, T.log2ks, T.cps, (uint64_t)T.r2, T.r2_threads, T.r2_lds, (uint64_t)T.fold,
+                          T.heavy_grid(1), T.heavy_grid(3)};
+  for (int i = 0; i < 11; ++i) out[i] = t[i];
+}
+// the tail plan alone, of parameters given field by field (the order of out[0..8] below): bucket sets that no point
+// count produces, such as one of 511 chunks
+void shim_msm_tail_plan(const uint32_t* p, int is_g1, int narrow_tail, const int* knobs, uint64_t* out) {
+  MsmParams P;
+  P.n = p[0], P.c = p[1], P.nwin = p[2], P.nbuckets = p[3], P.seg = p[4], P.scalars_mont = p[5], P.tables = p[6];
+  P.max_extra = p[7], P.mtab = p[8];
+  shim_tail_out(msm_tail_plan(P, is_g1 != 0, narrow_tail != 0, shim_env(knobs)), out);
+}
+void shim_msm_plan(uint64_t n, uint32_t flags, int table_cfg, int is_g1, int narrow_tail, const int* knobs, uint64_t* out) {
+  const G16Env env = shim_env(knobs);
+  uint32_t cfg = 0;
+  if (table_cfg) {
+    const uint32_t c = msm_pick_table_window(n, env);
+    cfg = c | (msm_pick_mtab(c, env) << 8);
+  }
+  const MsmParams P = msm_params(n, flags, cfg, env);
+  const uint32_t p[9] = {P.n, P.c, P.nwin, P.nbuckets, P.seg, P.scalars_mont, P.tables, P.max_extra, P.mtab};
+  for (int i = 0; i < 9; ++i) out[i] = p[i];
+  const MsmSortPlan L = msm_sort_plan(P, env);
+  const uint64_t l[10] = {L.lo_bits, L.nparts, L.ptiles, L.nth, L.use_part, L.fused, L.nblk, L.ntiles, L.nt2, L.pblk};
+  for (int i = 0; i < 10; ++i) out[9 + i] = l[i];
+  char* const base = reinterpret_cast<char*>(uintptr_t(1) << 40);
+  ShimSortParts S;
+  Carver sort{base};
+  msm_sort_layout(S, P, L, sort);
+  char* const sp[16] = {S.count, S.cursor, S.offset, S.xoff, S.heavy, S.info, S.tiles, S.entries, S.xseg, S.perm, S.ghist,
+                        S.blk_base, S.tile_hist, S.tmp, S.tiles2, S.slice_hist};
+  for (int i = 0; i < 16; ++i) out[19 + i] = (uint64_t)(sp[i] - base);
+  Carver sort_size{nullptr};
+  msm_sort_layout(S, P, L, sort_size);
+  out[35] = sort_size.bytes;
+  const MsmTailPlan T = msm_tail_plan(P, is_g1 != 0, narrow_tail != 0, env);
+  for (int g = 0; g < 2; ++g) {
+    ShimJobParts J;
+    Carver job{base}, job_size{nullptr};
+    msm_job_layout(J, P, T.nchunks, g ? 256 : 128, g ? 288 : 144, job);
+    char* const jp[4] = {J.partial, J.chunkR, J.chunkA, J.wsum};
+    for (int i = 0; i < 4; ++i) out[36 + 5 * g + i] = (uint64_t)(jp[i] - base);
+    msm_job_layout(J, P, T.nchunks, g ? 256 : 128, g ? 288 : 144, job_size);
+    out[40 + 5 * g] = job_size.bytes;
+  }
+  shim_tail_out(T, out + 46);
 }
 
 // the class bucket set of registered point sets with two multiplier tables (msm_params.hpp): every digit magnitude
