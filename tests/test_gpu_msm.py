@@ -1,9 +1,12 @@
 """GPU parity: HIP MSM (through the C ABI) == oracle, bit-exact on the canonical affine encoding.
 Mirrors what the reference can check about msmMultiThreadedG1/G2 (groth16/bn128/msm.nim:89-158)."""
+import os
+
 import pytest
 
 from oracle import bn254_ref as o
 from tests import inputs as I
+from tests.msm_pictures import geometry
 
 pytestmark = pytest.mark.gpu
 
@@ -37,6 +40,8 @@ def test_msm_edge_scalars_and_points(ctx, orc, group):
     dec = o.g1_from_bytes if group == 1 else o.g2_from_bytes
     enc = o.g1_to_bytes if group == 1 else o.g2_to_bytes
     negP0 = enc(C.neg(dec(P[0])))
+    # the window this process runs a 4-point MSM with (5 bits by default: 2^15 / 2^16 are NOT its half-window edge)
+    c = geometry(4, False, group == 1, {k: v for k, v in os.environ.items() if k.startswith("G16_")}).c
     cases = {
         "all zero scalars": ([0] * 8, P),
         "scalar one": ([1] * 8, P),
@@ -46,6 +51,8 @@ def test_msm_edge_scalars_and_points(ctx, orc, group):
         "infinity inputs": ([11, 12, 13], [INF[group], P[1], INF[group]]),
         "cancels to infinity": ([9, 9], [P[0], negP0]),
         "half window edge": ([1 << 15, (1 << 15) + 1, (1 << 16) - 1, 1 << 16], P[:4]),
+        "half window edge of the window run": ([1 << (c - 1), (1 << (c - 1)) + 1, (1 << c) - 1, 1 << c], P[:4]),
+        "... in the second window": ([1 << (2 * c - 1), (1 << (2 * c - 1)) + 1, (1 << 2 * c) - 1, 1 << 2 * c], P[:4]),
         "doubling inside bucket": ([3, 3], [P[4], P[4]]),
     }
     for name, (sc, pl) in cases.items():
