@@ -11,8 +11,7 @@
 #include <new>
 
 #include "g16_internal.hpp"
-#include "ec.cuh"
-#include "host_ff64.hpp"
+#include "host_curve.hpp"   // the host-side O(1) curve algebra of the combine step (ec.cuh, host_ff64.hpp)
 
 using namespace g16;
 
@@ -41,78 +40,6 @@ struct g16_pkey {
   DevMem<uint32_t> liveB;            // owned (the union), or empty
   size_t deadB = 0;               // wires whose B1 AND B2 points are both (0,0)
 };
-
-// ---- host-side O(1) curve helpers (the reference does these on the host too: curves.nim:136-214) ------
-// 64-bit-limb host field (host_ff64.hpp) under the same curve templates; 4-bit fixed windows.
-using HG1 = Curve<HFp>;
-using HG2 = Curve<HFp2>;
-template <class HC, class DevAff>
-static DevAff host_mul(const u256& k_std, const DevAff& p_dev) {
-  static_assert(sizeof(DevAff) == sizeof(typename HC::Aff), "layout");
-  typename HC::Aff p;
-  memcpy(&p, &p_dev, sizeof p);
-  typename HC::Acc tab[16];
-  tab[0] = HC::acc_inf();
-  tab[1] = HC::from_affine(p);
-  for (int i = 2; i < 16; ++i) {
-    tab[i] = tab[i - 1];
-    HC::madd(tab[i], p);
-  }
-  typename HC::Acc acc = HC::acc_inf();
-  for (int i = 7; i >= 0; --i)
-    for (int nib = 7; nib >= 0; --nib) {
-      if (!HC::is_inf(acc))
-        for (int d = 0; d < 4; ++d) acc = HC::dbl(acc);
-      uint32_t w = (k_std.v[i] >> (4 * nib)) & 15u;
-      if (w) HC::add(acc, tab[w]);
-    }
-  typename HC::Aff r = HC::to_affine(acc);
-  DevAff out;
-  memcpy(&out, &r, sizeof out);
-  return out;
-}
-template <class HC, class DevAff>
-static DevAff host_add(const DevAff& a_dev, const DevAff& b_dev) {
-  typename HC::Aff a, b;
-  memcpy(&a, &a_dev, sizeof a);
-  memcpy(&b, &b_dev, sizeof b);
-  typename HC::Acc acc = HC::from_affine(a);
-  HC::madd(acc, b);
-  typename HC::Aff r = HC::to_affine(acc);
-  DevAff out;
-  memcpy(&out, &r, sizeof out);
-  return out;
-}
-// k1 * p1 + k2 * p2 with ONE doubling chain (Shamir's trick, 2-bit joint windows: 16-entry table i*p1 + j*p2):
-// 254 doublings + <= 127 additions instead of two separate 4-bit-window multiplications (512 + 156)
-template <class HC, class DevAff>
-static DevAff host_mul2(const u256& k1_std, const DevAff& p1_dev, const u256& k2_std, const DevAff& p2_dev) {
-  typename HC::Aff p1, p2;
-  memcpy(&p1, &p1_dev, sizeof p1);
-  memcpy(&p2, &p2_dev, sizeof p2);
-  typename HC::Acc tab[16];   // tab[4 i + j] = i*p1 + j*p2
-  tab[0] = HC::acc_inf();
-  for (int j = 1; j < 4; ++j) {
-    tab[j] = tab[j - 1];
-    HC::madd(tab[j], p2);
-  }
-  for (int i = 1; i < 4; ++i)
-    for (int j = 0; j < 4; ++j) {
-      tab[4 * i + j] = tab[4 * (i - 1) + j];
-      HC::madd(tab[4 * i + j], p1);
-    }
-  typename HC::Acc acc = HC::acc_inf();
-  for (int limb = 7; limb >= 0; --limb)
-    for (int pos = 15; pos >= 0; --pos) {
-      if (!HC::is_inf(acc)) acc = HC::dbl(HC::dbl(acc));
-      const uint32_t w = 4 * ((k1_std.v[limb] >> (2 * pos)) & 3u) + ((k2_std.v[limb] >> (2 * pos)) & 3u);
-      if (w) HC::add(acc, tab[w]);
-    }
-  typename HC::Aff r = HC::to_affine(acc);
-  DevAff out;
-  memcpy(&out, &r, sizeof out);
-  return out;
-}
 
 extern "C" void g16_pkey_destroy(g16_pkey* k) {
   if (!k) return;
@@ -636,18 +563,7 @@ static __global__ void prove_combine_kernel(const unsigned char* __restrict__ ga
 // Enqueue half: stage copy + prove_combine_kernel on the context's main stream, the host algebra that needs only the
 // mask and the key, then the copy of the five affine MSM sums (384 bytes) into `res_host` and, if `done` is given, an
 // event behind it.  Into pageable memory the copy makes the host wait for the stream; into pinned memory it does not.
-struct CombineRes {
-  g1_aff a, b1;
-  g2_aff b2;
-  g1_aff h, c;
-};
 static_assert(sizeof(CombineRes) == G16_COMBINE_RES_BYTES, "slot layout");
-struct CombinePre {
-  u256 r_std, s_std;
-  g1_aff a_pre;
-  g2_aff b_pre;
-  g1_aff c_pre;
-};
 static_assert(sizeof(CombinePre) == sizeof(g16_combine_pre), "g16_combine_pre layout");
 
 int32_t g16_combine_enqueue(g16_ctx* ctx, const g16_pkey* k, const void* partials, size_t count, uint32_t flags,
@@ -664,20 +580,11 @@ int32_t g16_combine_enqueue(g16_ctx* ctx, const g16_pkey* k, const void* partial
           d_res);
 
   // Everything that depends on the mask and the key alone is computed while the GPU works -- in g16_prove that is the
-  // whole proof, which is enqueued without a host wait (prover.nim:267-268, 279-302 regrouped):
-  //   pi_a = (alpha1 + r delta1) + A                      pi_b = (beta2 + s delta2) + B2
-  //   pi_c = s pi_a + r rho - rs delta1 + H + C           with rho = beta1 + s delta1 + B1
-  //        = (s alpha1 + r beta1 + rs delta1) + (s A + r B1) + H + C
-  // The same group elements as the reference's order of operations, hence the same canonical affine bytes.
+  // whole proof, which is enqueued without a host wait (host_curve.hpp: host_combine_pre)
   u256 r = Fr::zero(), s = Fr::zero();
   if (mask_r) memcpy(&r, mask_r, 32);
   if (mask_s) memcpy(&s, mask_s, 32);
-  CombinePre pre;
-  pre.r_std = Fr::from_mont(r), pre.s_std = Fr::from_mont(s);
-  const u256 rs_std = Fr::from_mont(Fr::mul(r, s));
-  pre.a_pre = host_add<HG1>(k->alpha1, host_mul<HG1>(pre.r_std, k->delta1));
-  pre.b_pre = host_add<HG2>(k->beta2, host_mul<HG2>(pre.s_std, k->delta2));
-  pre.c_pre = host_add<HG1>(host_mul2<HG1>(pre.s_std, k->alpha1, pre.r_std, k->beta1), host_mul<HG1>(rs_std, k->delta1));
+  const CombinePre pre = host_combine_pre(k->alpha1, k->beta1, k->delta1, k->beta2, k->delta2, r, s);
   memcpy(pre_out, &pre, sizeof pre);
   // (a copy into pageable host memory makes the host wait for the stream: it comes AFTER the host arithmetic above)
   HIPCHK(ctx, hipMemcpyAsync(res_host, d_res, sizeof(CombineRes), hipMemcpyDeviceToHost, ctx->stream));
@@ -692,11 +599,9 @@ void g16_combine_finish(const g16_combine_pre* pre_in, const void* res_host, g16
   CombineRes res;
   memcpy(&pre, pre_in, sizeof pre);
   memcpy(&res, res_host, sizeof res);
-  g1_aff pi_a = host_add<HG1>(pre.a_pre, res.a);
-  g2_aff pi_b = host_add<HG2>(pre.b_pre, res.b2);
-  g1_aff pi_c = host_add<HG1>(pre.c_pre, host_mul2<HG1>(pre.s_std, res.a, pre.r_std, res.b1));
-  pi_c = host_add<HG1>(pi_c, res.h);
-  pi_c = host_add<HG1>(pi_c, res.c);
+  g1_aff pi_a, pi_c;
+  g2_aff pi_b;
+  host_combine_finish(pre, res, pi_a, pi_b, pi_c);
   memcpy(out->pi_a, &pi_a, 64);
   memcpy(out->pi_b, &pi_b, 128);
   memcpy(out->pi_c, &pi_c, 64);
