@@ -1,5 +1,5 @@
 // The experiment knobs of the library as plain data: no HIP, so that the launch plans that take them as an argument
-// (msm_plan.hpp) also build with g++ for the CPU tests.
+// (msm_plan.hpp, proof_plan.hpp) also build with g++ for the CPU tests.
 #pragma once
 
 // Experiment knobs (G16_* environment variables), read ONCE per process -- at the first g16_ctx_create -- and never
@@ -16,7 +16,7 @@ struct G16Env {
   char stream_prio[7] = "lhllln";   // G16_STREAM_PRIO  six characters from {h, n, l}
   int red_slice_log2 = 0;  // G16_RED_SLICE    log2 of the chunks per reduce2 slice of a merged bucket set (8..11)
   int inf_compact_pct = 10;   // G16_INF_COMPACT  point sets with at least this percentage of (0,0) points get their own
-                              // entry lists without them (0: always, 101: never); prover.hip
+                              // entry lists without them (0: always, 101: never); proof_plan.hpp
   int r2_width = -1;       // G16_R2_WIDTH  0: reduce2 with 512 / 256-thread workgroups, 1: 128 / 64, 2: 64 / 64; unset:
                            // narrow inside proofs, wide for stand-alone MSMs (msm_stage.cuh)
   int ntt_tile = 2048;            // G16_NTT_TILE = 1024 | 2048 | 4096: NTT workgroup geometry (ntt.cuh)
@@ -24,7 +24,7 @@ struct G16Env {
   int quotient_first = 1;         // G16_QUOTIENT_FIRST=0: enqueue the witness MSMs before buildABC + quotient + sort(qs) (rounds 1-4)
   int lanes_after_quotient = 0;   // G16_LANES_AFTER_QUOTIENT=1 (with the above): the witness accumulations wait for them
   int g1_batch = 0;               // G16_G1_BATCH=1: ONE batched launch sequence (blockIdx.y = MSM) for A1, B1, C1 on one stream
-                                  // instead of one stream and one sequence per G1 MSM (prover.hip; measured slower)
+                                  // instead of one stream and one sequence per G1 MSM (proof_plan.hpp; measured slower)
   int mtab = 2;                   // G16_MTAB=1: registered sets without the second multiplier table / class bucket set
   int chain_ch = 1;               // G16_CHAIN_CH=0: C1 and H1 as two MSMs instead of H1 continuing C1's bucket sums
   int tail_quad = 1;              // G16_TAIL_QUAD=0: reduce2 / fold with one lane per slot instead of a cooperating quad (msm.cuh,
@@ -37,5 +37,5 @@ struct G16Env {
   int abc_dict = 1;               // G16_ABC_DICT=0: buildABC reads a 32-byte value per entry even when the key's coefficients
                                   // come from a small set (spmv.hip: value dictionary)
   int g2_first = -1;              // G16_G2_FIRST = 0 | 1 | 2: A1 and B1 (2: C1 too) accumulate after B2 (unset: 1 for small shards,
-                                  // prover.hip)
+                                  // proof_plan.hpp)
 };

@@ -15,6 +15,7 @@
 #include "hip_owners.hpp"
 #include "msm_params.hpp"
 #include "msm_plan.hpp"
+#include "proof_plan.hpp"
 
 const G16Env& g16_env();   // g16hip.hip: the knobs of this process
 
@@ -58,8 +59,7 @@ struct g16_ctx {
   };
   MsmSort sort[4];   // 0: witness (all pairs)  1: H scalars  2: witness, A1's live pairs  3: witness, B1/B2's live pairs
   MsmLane lane[5];
-  enum { EV_A, EV_B, EV_Q, EV_B2, EV_C, EV_G2, EV_COUNT };
-  Event ev[EV_COUNT];   // the cross-stream edges of a proof (prover.hip)
+  Event ev[g16::EV_COUNT];   // the cross-stream edges of a proof (ProofEvent, proof_plan.hpp)
   Buf stage_s;   // staged scalars (host-pointer API)
   Buf stage_p;   // staged points
   Buf stage_p29; // the same points as reduced-radix entries (one-shot MSMs; registered sets keep their own tables)
@@ -204,8 +204,8 @@ struct g16_points {
   DevMem<uint32_t> d_live;      // bitmap: bit i set <=> point i is not (0,0); ceil(n/32) words
   size_t n_inf = 0;             // points at infinity in the set
 };
-// the live bitmap of a registered set if it holds enough (0,0) points for its own entry lists to pay (G16_INF_COMPACT;
-// g16hip.hip)
+// the live bitmap of a registered set if it holds enough (0,0) points for its own entry lists to pay (points_sparse,
+// proof_plan.hpp; g16hip.hip)
 const uint32_t* g16_points_live_if_sparse(const g16_points* p);
 // the two halves of an MSM: (1) arrange one scalar vector into buckets, (2) accumulate + reduce a point set
 // against that arrangement.  Several point sets may share one sort (same scalars, same n, same c).
@@ -231,7 +231,6 @@ int32_t g16_msm_batch(g16_ctx* ctx, hipStream_t stream, int group, const g16_msm
                       hipEvent_t after_heavy);
 inline const void* g16_msm_partial_ptr(const g16_ctx::Buf& acc) { return acc.p(); }
 int32_t g16_lanes_init(g16_ctx* ctx);   // g16hip.hip
-int g16_stream_priority(int index);
 // d_out = d_a | d_b over bitmaps of n bits; *d_n_dead (device u32, zeroed by the caller) += bits clear in
 // the union (msm_g1_misc.hip)
 int32_t g16_bitmap_or_device(g16_ctx* ctx, uint32_t* d_out, const uint32_t* d_a, const uint32_t* d_b, size_t n,

@@ -46,21 +46,31 @@ const G16Env& g16_env() {
   return env;
 }
 
-// ---- CU partition (experiment, G16_CU_SPLIT=k) -----------------------------------------------------
-// With k > 0 the context's main stream (witness upload, buildABC, NTTs, sorts, the fold of H) is created over k CUs of
+// ---- the streams of a context: priorities, or a CU partition ---------------------------------------------------------
+// CU partition (experiment, G16_CU_SPLIT=k).  With k > 0 the context's main stream (witness upload, buildABC, NTTs, sorts, the fold of H) is created over k CUs of
 // every XCD and the five MSM lanes over the remaining 32 - k: the front of a proof then owns CUs instead of waiting for
 // accumulate waves of other streams to drain.  CU-mask bit i is CU (i / 8) of XCD (i % 8) on this part (the mask is dealt
 // round robin over the XCCs).  Such streams have no priority.  Measured: profiles/r05_ab_cu_split.txt.
+//
+// Stream priorities.  Index 0..4 = lanes (0: witness sort + C1, 1: B2, 2: B1, 3: A1, 4: spare), 5 = main stream
+// (buildABC, quotient NTTs, H).  Default "lhllln" (G2 high, main normal, G1 lanes low): the G2 MSM has the longest
+// latency chain of a proof; prioritising it lets its reduce/fold tail overlap the G1 accumulations of this and
+// of the other in-flight proofs (measured with 3 proofs in flight: 78 proofs/s flat, 90 "lhlllh", 97 "lhllln").
+// G16_STREAM_PRIO = six characters from {h, n, l} overrides it (read once per process, g16_env).
+//
+// The mask and the priority themselves are pure functions of the knobs: stream_cu_mask, stream_priority (proof_plan.hpp).
 static hipError_t ctx_stream_create(Stream& out, int prio_index, bool front) {
-  const int k = g16_env().cu_split;
-  uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (int bit = 0; bit < 256; ++bit) {
-    const bool in_front = bit / 8 < k;
-    if (in_front == front) mask[bit / 32] |= 1u << (bit % 32);
-  }
   hipStream_t st = nullptr;
-  const hipError_t e = k <= 0 ? hipStreamCreateWithPriority(&st, hipStreamNonBlocking, g16_stream_priority(prio_index))
-                              : hipExtStreamCreateWithCUMask(&st, 8, mask);
+  hipError_t e;
+  if (g16_env().cu_split <= 0) {
+    int lo = 0, hi = 0;
+    (void)hipDeviceGetStreamPriorityRange(&lo, &hi);   // numerically: hi <= lo
+    e = hipStreamCreateWithPriority(&st, hipStreamNonBlocking, stream_priority(g16_env(), prio_index, lo, hi));
+  } else {
+    uint32_t mask[8];
+    stream_cu_mask(g16_env(), front, mask);
+    e = hipExtStreamCreateWithCUMask(&st, 8, mask);
+  }
   out.reset(st);
   return e;
 }
@@ -82,22 +92,6 @@ extern "C" int32_t g16_ctx_create(int32_t device, g16_ctx** out) {
   if (g16_lanes_init(ctx.get()) != G16_OK) return G16_ENODEV;
   *out = ctx.release();
   return G16_OK;
-}
-
-// Stream priorities.  Index 0..4 = lanes (0: witness sort + C1, 1: B2, 2: B1, 3: A1, 4: spare), 5 = main stream
-// (buildABC, quotient NTTs, H).  Default "lhllln" (G2 high, main normal, G1 lanes low): the G2 MSM has the longest
-// latency chain of a proof; prioritising it lets its reduce/fold tail overlap the G1 accumulations of this and
-// of the other in-flight proofs (measured with 3 proofs in flight: 78 proofs/s flat, 90 "lhlllh", 97 "lhllln").
-// G16_STREAM_PRIO = six characters from {h, n, l} overrides it (read once per process, g16_env).
-int g16_stream_priority(int index) {
-  int lo = 0, hi = 0;
-  (void)hipDeviceGetStreamPriorityRange(&lo, &hi);   // numerically: hi <= lo
-  const char* cfg = g16_env().stream_prio;
-  switch (cfg[index]) {
-    case 'h': return hi;
-    case 'l': return lo;
-    default: return (lo + hi) / 2;
-  }
 }
 
 int32_t g16_lanes_init(g16_ctx* ctx) {
@@ -339,8 +333,7 @@ extern "C" void g16_points_release(g16_points* h) {
 }
 extern "C" size_t g16_points_inf_count(const g16_points* h) { return h ? h->n_inf : 0; }
 const uint32_t* g16_points_live_if_sparse(const g16_points* p) {
-  return p && p->d_live && p->n && p->n_inf * 100 >= (size_t)g16_env().inf_compact_pct * p->n && p->n_inf ? p->d_live.get()
-                                                                                                        : nullptr;
+  return p && p->d_live && p->n && points_sparse(p->n_inf, p->n, g16_env()) ? p->d_live.get() : nullptr;
 }
 extern "C" size_t g16_points_count(const g16_points* h) { return h ? h->n : 0; }
 extern "C" int32_t g16_points_info(const g16_points* h, uint32_t* window_bits, uint32_t* ntables) {

@@ -150,7 +150,7 @@ static int32_t pkey_create(g16_ctx* ctx, const g16_pkey_desc* d, const CoeffSour
       HIPCHK(ctx, hipMemcpyAsync(&dead, d_cnt, 4, hipMemcpyDeviceToHost, ctx->stream));
       HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
       k->deadB = dead;
-      if (!dead || (size_t)dead * 100 < (size_t)g16_env().inf_compact_pct * nw) k->liveB.reset();   // dense: share the witness sort
+      if (!points_sparse(dead, nw, g16_env())) k->liveB.reset();   // dense: share the witness sort
     }
   }
   // the A and B entries in row order, rows binned by length (sum order is irrelevant mod r)
@@ -244,8 +244,95 @@ extern "C" int32_t g16_build_abc(g16_ctx* ctx, const g16_pkey* k, const void* wi
 //   [0,128) A1 | [128,256) B1 | [256,512) B2 (G2) | [512,640) H1 | [640,768) C1
 static constexpr size_t PART_A = 0, PART_B1 = 128, PART_B2 = 256, PART_H = 512, PART_C = 640, PART_BYTES = 768;
 
-static int32_t prove_partials_impl(g16_ctx* ctx, const g16_pkey* k, const void* witness, uint32_t flags,
-                                   void* out_partials);
+// ---- a proof's launch sequence: the plan (proof_plan.hpp) decides, run_plan issues ------------------------------
+static ProofShape proof_shape(const g16_pkey* k) {
+  return ProofShape{k->w_hi - k->w_lo, k->h_hi - k->h_lo, k->log2n, k->liveA != nullptr, (bool)k->liveB,
+                    k->C1->cfg() == k->H1->cfg()};
+}
+
+// what the steps of one entry point work on
+struct ProofArgs {
+  const void* witness = nullptr;   // (whole proof, _begin)
+  uint32_t flags = 0;
+  u256* task_out = nullptr;        // _begin: the coset vectors, n Fr each
+  const void *d_a1 = nullptr, *d_b1 = nullptr, *d_c1 = nullptr;   // _end: this key's slices of them
+  bool qs_is_slice = false;        // _end: the H scalars lie at the start of the qs buffer, not at h_lo
+  void* out_partials = nullptr;
+};
+
+static int32_t run_plan(g16_ctx* ctx, const g16_pkey* k, ProofEntry entry, uint32_t task_mask, bool host_sync,
+                        const ProofArgs& a) {
+  ProofPlan plan;
+  if (!proof_plan_build(plan, g16_env(), entry, task_mask, host_sync, proof_shape(k))) {
+    ctx->err = "proof launch plan exceeds its capacity";
+    return G16_EINVAL;
+  }
+  const size_t n = size_t(1) << k->log2n, nw = k->w_hi - k->w_lo, nh = k->h_hi - k->h_lo;
+  int32_t rc;
+  if ((rc = ensure(ctx, ctx->prove, ((size_t)k->nvars + 4 * n) * 32))) return rc;
+  if ((rc = ensure(ctx, ctx->stage_o, 2048))) return rc;
+  u256* const d_w = (u256*)ctx->prove.p();   // per-proof scalars: witness | Az | Bz | Cz | qs
+  u256* const d_abc = d_w + k->nvars;
+  u256* const d_qs = d_abc + 3 * n;
+  char* const slots = (char*)ctx->stage_o.p();
+  const u256* const d_wr = d_w + k->w_lo;
+  const u256* const d_qs_slice = a.qs_is_slice ? d_qs : d_qs + k->h_lo;   // the H scalars of [h_lo, h_hi), Montgomery
+  const uint32_t wit_mont = (a.flags & G16_SCALARS_MONT) ? 1u : 0u;
+  g16_ctx::MsmLane* L = ctx->lane;
+  // the five MSMs (ProofRun order): arrangement, workspace, tables, slot of the record
+  const g16_points* const sets[RUN_COUNT] = {k->A1, k->B1, k->C1, k->B2, k->H1};
+  g16_msm_run runs[RUN_COUNT] = {
+      {&ctx->sort[plan.sort_a], &L[0].acc, k->A1->d_tables.get(), nullptr, slots + PART_A, nullptr},
+      {&ctx->sort[plan.sort_b], &L[2].acc, k->B1->d_tables.get(), nullptr, slots + PART_B1, nullptr},
+      {&ctx->sort[SORT_W], &L[3].acc, k->C1->d_tables.get(), nullptr, slots + PART_C, nullptr},
+      {&ctx->sort[plan.sort_b], &L[1].acc, k->B2->d_tables.get(), nullptr, slots + PART_B2, nullptr},
+      {&ctx->sort[SORT_H], &L[4].acc, k->H1->d_tables.get(), nullptr, slots + PART_H, nullptr}};
+  auto event = [&](int e) { return e == EV_NONE ? nullptr : e < EV_COUNT ? ctx->ev[e].get() : L[e - EV_DONE0].done.get(); };
+  for (int i = 0; i < plan.count; ++i) {
+    const ProofStep& s = plan.steps[i];
+    rc = G16_OK;
+    hipStream_t st = s.stream == PS_MAIN ? ctx->stream : L[s.stream].stream.get();
+    switch (s.op) {
+      case OP_UPLOAD:
+        HIPCHK(ctx, hipMemcpyAsync(d_w, a.witness, (size_t)k->nvars * 32,
+                                   (a.flags & G16_SCALARS_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipMemsetAsync(slots, 0, PART_BYTES, st));   // empty range -> XYZZ infinity (all zero)
+        break;
+      case OP_WAIT: HIPCHK(ctx, hipStreamWaitEvent(st, event(s.a), 0)); break;
+      case OP_RECORD: HIPCHK(ctx, hipEventRecord(event(s.a), st)); break;
+      case OP_SORT_W:
+        ctx->sort[s.a].narrow_tail = plan.narrow_tail;
+        rc = g16_msm_sort(ctx, st, d_wr, wit_mont ? G16_SCALARS_MONT : 0u, nw, sets[s.c]->cfg(), ctx->sort[s.a],
+                          s.b == 0 ? nullptr : s.b == 1 ? k->liveA : k->liveB.get());
+        break;
+      case OP_SORT_H:
+        ctx->sort[SORT_H].narrow_tail = plan.narrow_tail;
+        rc = g16_msm_sort(ctx, st, d_qs_slice, G16_SCALARS_MONT, nh, k->H1->cfg(), ctx->sort[SORT_H]);
+        break;
+      case OP_BUILD_ABC: rc = build_abc_device(ctx, k, d_w, wit_mont, d_abc, s.a != 0); break;
+      case OP_QUOTIENT:
+        rc = g16_quotient_device(ctx, d_abc, d_abc + n, d_abc + 2 * n, k->log2n, (int)k->flavour, d_qs, s.a);
+        break;
+      case OP_COSET: {   // (the outputs of the set bits of task_mask lie one after the other)
+        const int at = __builtin_popcount(task_mask & ((1u << s.a) - 1));
+        rc = g16_coset_pipeline_device(ctx, d_abc + s.a * n, k->log2n, a.task_out + at * n);
+        break;
+      }
+      case OP_POINTWISE: rc = g16_abc_pointwise_device(ctx, a.d_a1, a.d_b1, a.d_c1, nh, d_qs); break;
+      case OP_MSM:
+        runs[RUN_H].init_partial = s.e ? g16_msm_partial_ptr(L[3].acc) : nullptr;   // (read by H's step alone)
+        rc = g16_msm_batch(ctx, st, s.a == RUN_B2 ? 2 : 1, &runs[s.a], s.b, s.c, event(s.d));
+        break;
+      case OP_COPY_OUT:
+        HIPCHK(ctx, hipMemcpyAsync(a.out_partials, slots, PART_BYTES,
+                                   (a.flags & G16_OUT_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+        break;
+      case OP_HOST_SYNC: HIPCHK(ctx, hipStreamSynchronize(st)); break;
+    }
+    if (rc) return rc;
+  }
+  return G16_OK;
+}
 
 extern "C" int32_t g16_prove_partials(g16_ctx* ctx, const g16_pkey* k, const void* witness, uint32_t flags,
                                       void* out_partials) {
@@ -255,217 +342,17 @@ extern "C" int32_t g16_prove_partials(g16_ctx* ctx, const g16_pkey* k, const voi
     return G16_EINVAL;
   }
   CTX_ENTER(ctx);
-  const int32_t rc = prove_partials_impl(ctx, k, witness, flags, out_partials);
+  ProofArgs a;
+  a.witness = witness, a.flags = flags, a.out_partials = out_partials;
+  // G16_NO_HOST_SYNC (device output only): the record is complete in stream order; the caller's next operation on
+  // the context's stream (an all-gather enqueued on it, g16_prove_combine) is ordered behind it without a host wait
+  const bool host_sync = !((flags & G16_NO_HOST_SYNC) && (flags & G16_OUT_DEVICE));
+  const int32_t rc = run_plan(ctx, k, PROOF_WHOLE, 0, host_sync, a);
   // an error exit may leave work queued on the lane streams (e.g. a failed allocation after the witness MSMs were
   // launched): drain all of them before returning, so that the caller -- or the next call's ensure() -- can never
   // free a buffer a lane kernel is still reading
   if (rc != G16_OK) ctx_quiesce(ctx);
   return rc;
-}
-
-// ---- the pieces of a proof's launch sequence ---------------------------------------------------------------
-struct ProveBufs {
-  u256 *d_w, *d_abc, *d_qs;
-  char* slots;
-};
-static int32_t prove_bufs(g16_ctx* ctx, const g16_pkey* k, ProveBufs& b) {
-  const size_t n = size_t(1) << k->log2n;
-  int32_t rc;
-  if ((rc = ensure(ctx, ctx->prove, ((size_t)k->nvars + 4 * n) * 32))) return rc;
-  if ((rc = ensure(ctx, ctx->stage_o, 2048))) return rc;
-  b.d_w = (u256*)ctx->prove.p();
-  b.d_abc = b.d_w + k->nvars;
-  b.d_qs = b.d_abc + 3 * n;
-  b.slots = (char*)ctx->stage_o.p();
-  return G16_OK;
-}
-
-// witness -> HBM (main stream); ev_a marks its arrival
-static int32_t upload_witness(g16_ctx* ctx, const g16_pkey* k, const void* witness, uint32_t flags, const ProveBufs& b) {
-  HIPCHK(ctx, hipMemcpyAsync(b.d_w, witness, (size_t)k->nvars * 32,
-                             (flags & G16_SCALARS_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-                             ctx->stream));
-  HIPCHK(ctx, hipMemsetAsync(b.slots, 0, PART_BYTES, ctx->stream));   // empty range -> XYZZ infinity (all zero)
-  HIPCHK(ctx, hipEventRecord(ctx->ev[g16_ctx::EV_A].get(), ctx->stream));                // witness resident
-  return G16_OK;
-}
-
-// C1 and H1 enter the proof only as their sum (pi_c = ... + H + C, prover.nim:301-302), and both point sets are
-// registered with the same window, i.e. over the same bucket set: the H accumulation then STARTS from C1's bucket sums
-// instead of from infinity, and the pair needs one bucket reduction (reduce1 / reduce2 / fold) instead of two.  The
-// C1 slot of the record stays at infinity.  G16_CHAIN_CH=0 restores two separate MSMs.
-static bool chain_c_into_h(const g16_pkey* k) {
-  return g16_env().chain_ch && k->w_hi > k->w_lo && k->h_hi > k->h_lo && k->C1->cfg() == k->H1->cfg();
-}
-
-// The four MSMs that consume the witness (A1, B1, B2, C1: prover.nim:282, 288, 294, 302) on the lane streams.  The
-// witness' signed-digit bucket arrangement is computed once (lane 0) and shared; the four accumulate / reduce pipelines
-// run on four streams so that their latency-bound tails overlap the other pipelines' accumulation.  Nothing is waited
-// for here.  Round 4 measured four other schedules against this one, same box, same session (profiles/r04_ab_*.txt):
-//  * A1, B1, C1 as ONE batched launch sequence on one stream (every stage kernel takes blockIdx.y = MSM: three-wide
-//    tails, 15 launches and 2 streams less): 110.2 vs 115.2 proofs/s.  Kept as G16_G1_BATCH=1.
-//  * one accumulate stream per context with the tails on the lanes (a context then offers one accumulate kernel at a
-//    time): 110.7 vs 117.4, and 33 / 10 proofs/s with 4 / 5 proofs in flight (the runtime's cross-stream waits stall).
-//  * one accumulate stream for ALL in-flight proofs of the device: 8-12 proofs/s (stalls of 10-45 ms at the waits).
-//  * an admission gate (the whole front of a proof -- upload, both sorts, buildABC, quotient -- first, then at most n
-//    proofs past the gate, 4-6 in flight): 119.2-120.2 vs 119.5 -- the share of wall time without a resident
-//    accumulate kernel falls from 12 % to 8 % (tools/overlap.py) and the throughput does not move.
-// The step is bound by the instructions of ALL its kernels; what these schedules rearrange is latency.
-// `after` (optional): an event the accumulations wait for in addition to the sort -- the quotient's last kernel
-// (G16_QUOTIENT_FIRST / G16_LANES_AFTER_QUOTIENT experiments).
-// phase 1: the bucket arrangements of the witness (lane 0; lane 1 for the live pairs of B1 / B2)
-static int32_t launch_witness_sorts(g16_ctx* ctx, const g16_pkey* k, uint32_t flags) {
-  const uint32_t wflags = (flags & G16_SCALARS_MONT) ? G16_SCALARS_MONT : 0u;
-  const size_t nw = k->w_hi - k->w_lo;
-  if (!nw) return G16_OK;
-  int32_t rc;
-  g16_ctx::MsmLane* L = ctx->lane;
-  ProveBufs b;
-  if ((rc = prove_bufs(ctx, k, b))) return rc;
-  const u256* d_wr = b.d_w + k->w_lo;
-  HIPCHK(ctx, hipStreamWaitEvent(L[0].stream.get(), ctx->ev[g16_ctx::EV_A].get(), 0));
-  for (auto& srt : ctx->sort) srt.narrow_tail = true;   // proofs overlap their MSM tails with other work (msm_stage.cuh)
-  if ((rc = g16_msm_sort(ctx, L[0].stream.get(), d_wr, wflags, nw, k->A1->cfg(), ctx->sort[0]))) return rc;
-  if (k->liveA)   // A1 with many (0,0) points: its own arrangement, behind the shared one
-    if ((rc = g16_msm_sort(ctx, L[0].stream.get(), d_wr, wflags, nw, k->A1->cfg(), ctx->sort[2], k->liveA))) return rc;
-  HIPCHK(ctx, hipEventRecord(ctx->ev[g16_ctx::EV_B].get(), L[0].stream.get()));
-  // B1 / B2 with many (0,0) points: their own arrangement of the witness (live pairs only), built on B2's lane
-  // while lane 0 arranges the full witness
-  if (k->liveB) {
-    HIPCHK(ctx, hipStreamWaitEvent(L[1].stream.get(), ctx->ev[g16_ctx::EV_A].get(), 0));
-    if ((rc = g16_msm_sort(ctx, L[1].stream.get(), d_wr, wflags, nw, k->B2->cfg(), ctx->sort[3], k->liveB.get()))) return rc;
-    HIPCHK(ctx, hipEventRecord(ctx->ev[g16_ctx::EV_B2].get(), L[1].stream.get()));
-  }
-  return G16_OK;
-}
-// phase 2: accumulate + reduce A1, B1, B2, C1 against them
-constexpr size_t G2_FIRST_MAX = size_t(1) << 18;
-static int32_t launch_witness_msms(g16_ctx* ctx, const g16_pkey* k, const ProveBufs& b, hipEvent_t after) {
-  int32_t rc;
-  const size_t nw = k->w_hi - k->w_lo;
-  if (!nw) return G16_OK;
-  g16_ctx::MsmLane* L = ctx->lane;
-  const bool batch = g16_env().g1_batch != 0;
-  const bool chain = chain_c_into_h(k);
-  // lanes of the three G1 MSMs (A1, B1, C1); G16_G1_LANES (read once per process, g16_env) reassigns them
-  const int la = batch ? 0 : g16_env().g1_lanes[0], lb = batch ? 0 : g16_env().g1_lanes[1],
-            lc = batch ? 0 : g16_env().g1_lanes[2];
-  const int nlanes = batch ? 2 : 4;
-  const g16_ctx::MsmSort* sortA = k->liveA ? &ctx->sort[2] : &ctx->sort[0];
-  const g16_ctx::MsmSort* sortB = k->liveB ? &ctx->sort[3] : &ctx->sort[0];
-  // workspaces: the accumulate buffers of lanes 1, 0, 2, 3 serve B2, A1, B1, C1 in every mode
-  const g16_msm_run runB2{sortB, &L[1].acc, k->B2->d_tables.get(), nullptr, b.slots + PART_B2, nullptr};
-  g16_msm_run runs[3] = {{sortA, &L[0].acc, k->A1->d_tables.get(), nullptr, b.slots + PART_A, nullptr},
-                         {sortB, &L[2].acc, k->B1->d_tables.get(), nullptr, b.slots + PART_B1, nullptr},
-                         {&ctx->sort[0], &L[3].acc, k->C1->d_tables.get(), nullptr, b.slots + PART_C, nullptr}};
-  for (int i = 1; i < nlanes; ++i)   // (lane 1 sorted for itself when B is sparse)
-    HIPCHK(ctx, hipStreamWaitEvent(L[i].stream.get(), i == 1 && k->liveB ? ctx->ev[g16_ctx::EV_B2].get() : ctx->ev[g16_ctx::EV_B].get(), 0));
-  if (k->liveB) HIPCHK(ctx, hipStreamWaitEvent(L[lb].stream.get(), ctx->ev[g16_ctx::EV_B2].get(), 0));
-  if (k->liveA && la != 0) HIPCHK(ctx, hipStreamWaitEvent(L[la].stream.get(), ctx->ev[g16_ctx::EV_B].get(), 0));
-  if (after)
-    for (int i = 0; i < nlanes; ++i) HIPCHK(ctx, hipStreamWaitEvent(L[i].stream.get(), after, 0));
-  // Small witness ranges (the shards of a proof spread over GPUs): the four accumulations together do not fill the
-  // GPU, every kernel is a latency chain and B2's -- G2 additions, ~4 x the wave time of G1's -- is the longest: its
-  // accumulation goes first, next to C1's only (the H accumulation continues C1's bucket sums: the second longest
-  // chain); A1 and B1 then run under B2's reduce / fold tail.
-  const bool g2_first = g16_env().g2_first >= 0 ? g16_env().g2_first != 0 : nw <= G2_FIRST_MAX;
-  if ((rc = g16_msm_batch(ctx, L[1].stream.get(), 2, &runB2, 1, 1, g2_first ? ctx->ev[g16_ctx::EV_G2].get() : nullptr))) return rc;
-  if (g2_first) {
-    HIPCHK(ctx, hipStreamWaitEvent(L[la].stream.get(), ctx->ev[g16_ctx::EV_G2].get(), 0));
-    HIPCHK(ctx, hipStreamWaitEvent(L[lb].stream.get(), ctx->ev[g16_ctx::EV_G2].get(), 0));
-    if (!chain || g16_env().g2_first == 2) HIPCHK(ctx, hipStreamWaitEvent(L[lc].stream.get(), ctx->ev[g16_ctx::EV_G2].get(), 0));
-  }
-  if (batch) {
-    if ((rc = g16_msm_batch(ctx, L[0].stream.get(), 1, runs, 3, chain ? 2 : 3, chain ? ctx->ev[g16_ctx::EV_C].get() : nullptr))) return rc;
-  } else {
-    if ((rc = g16_msm_batch(ctx, L[la].stream.get(), 1, &runs[0], 1, 1, nullptr))) return rc;
-    if ((rc = g16_msm_batch(ctx, L[lb].stream.get(), 1, &runs[1], 1, 1, nullptr))) return rc;
-    if ((rc = g16_msm_batch(ctx, L[lc].stream.get(), 1, &runs[2], 1, chain ? 0 : 1, chain ? ctx->ev[g16_ctx::EV_C].get() : nullptr))) return rc;
-  }
-  for (int i = 0; i < nlanes; ++i) HIPCHK(ctx, hipEventRecord(L[i].done.get(), L[i].stream.get()));
-  return G16_OK;
-}
-
-// the H MSM over this key's domain range (prover.nim:301), then join the lanes and hand out the five partials.
-// d_qs_slice: the H scalars of [h_lo, h_hi), Montgomery.
-static int32_t launch_h_sort(g16_ctx* ctx, const g16_pkey* k, const u256* d_qs_slice) {
-  const size_t nh = k->h_hi - k->h_lo;
-  ctx->sort[1].narrow_tail = true;
-  return nh ? g16_msm_sort(ctx, ctx->stream, d_qs_slice, G16_SCALARS_MONT, nh, k->H1->cfg(), ctx->sort[1]) : G16_OK;
-}
-static int32_t launch_h_and_collect(g16_ctx* ctx, const g16_pkey* k, const u256* d_qs_slice, uint32_t flags,
-                                    const ProveBufs& b, void* out_partials, bool sorted = false) {
-  int32_t rc;
-  hipStream_t M = ctx->stream;
-  const size_t nw = k->w_hi - k->w_lo, nh = k->h_hi - k->h_lo;
-  const int nlanes = g16_env().g1_batch ? 2 : 4;
-  if (nh) {
-    if (!sorted && (rc = launch_h_sort(ctx, k, d_qs_slice))) return rc;
-    const bool chain = chain_c_into_h(k);
-    const g16_msm_run run{&ctx->sort[1], &ctx->lane[4].acc, k->H1->d_tables.get(), nullptr, b.slots + PART_H,
-                          chain ? g16_msm_partial_ptr(ctx->lane[3].acc) : nullptr};
-    // G16_CU_SPLIT: the main stream owns a few CUs per XCD only; the H accumulation then runs on the spare lane (the
-    // large partition), ordered behind the H sort and joined again below
-    hipStream_t HS = g16_env().cu_split ? ctx->lane[4].stream.get() : M;
-    if (HS != M) {
-      HIPCHK(ctx, hipEventRecord(ctx->ev[g16_ctx::EV_Q].get(), M));
-      HIPCHK(ctx, hipStreamWaitEvent(HS, ctx->ev[g16_ctx::EV_Q].get(), 0));
-    }
-    if (chain) HIPCHK(ctx, hipStreamWaitEvent(HS, ctx->ev[g16_ctx::EV_C].get(), 0));   // C1's bucket sums are final
-    if ((rc = g16_msm_batch(ctx, HS, 1, &run, 1, 1, nullptr))) return rc;
-    if (HS != M) {
-      HIPCHK(ctx, hipEventRecord(ctx->lane[4].done.get(), HS));
-      HIPCHK(ctx, hipStreamWaitEvent(M, ctx->lane[4].done.get(), 0));
-    }
-  }
-  if (nw)
-    for (int i = 0; i < nlanes; ++i) HIPCHK(ctx, hipStreamWaitEvent(M, ctx->lane[i].done.get(), 0));
-  HIPCHK(ctx, hipMemcpyAsync(out_partials, b.slots, PART_BYTES,
-                             (flags & G16_OUT_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
-  // G16_NO_HOST_SYNC (device output only): the record is complete in stream order; the caller's next operation on
-  // the context's stream (an all-gather enqueued on it, g16_prove_combine) is ordered behind it without a host wait
-  if (!((flags & G16_NO_HOST_SYNC) && (flags & G16_OUT_DEVICE))) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return G16_OK;
-}
-
-static int32_t prove_partials_impl(g16_ctx* ctx, const g16_pkey* k, const void* witness, uint32_t flags,
-                                   void* out_partials) {
-  const size_t n = size_t(1) << k->log2n;
-  const uint32_t wit_mont = (flags & G16_SCALARS_MONT) ? 1u : 0u;
-  ProveBufs b;
-  int32_t rc;
-  if ((rc = prove_bufs(ctx, k, b))) return rc;
-  if ((rc = upload_witness(ctx, k, witness, flags, b))) return rc;
-  // Launch order.  Rounds 1-4 enqueued the four witness MSMs first and buildABC + quotient + H behind them on the main
-  // stream: with the thread-per-row buildABC of those rounds the other order lost (r02: 107.6-108.5 vs 107.9-110.4
-  // proofs/s, 13.1 vs 12.0 ms single proof).  Since round 5 the head of the longest dependency chain -- buildABC (one
-  // row-balanced launch) -> quotient (Cz formed on the fly) -> sort(qs) -> H MSM -- goes to the GPU BEFORE the ~60
-  // launches of the witness lanes: two sessions, same box, identical proof bytes: single proof 10.61 -> 10.34 and
-  // 10.67 -> 10.46 ms, proofs/s 121.5 -> 122.2 and 119.9 -> 120.3 (profiles/r05_ab_quotient_first*.txt).  Holding the
-  // lanes back until the quotient is done (G16_LANES_AFTER_QUOTIENT=1) still loses (118.5, 11.4 ms).
-  // G16_QUOTIENT_FIRST=0 restores the old order.  Replicated on every rank of a sharded proof unless the caller uses the
-  // task-parallel pair g16_prove_partials_begin / _end.
-  const int fly = k->log2n >= 1 && g16_env().cz_on_the_fly ? 1 : 0;   // Cz formed by the quotient's first pass
-  if (!g16_env().quotient_first) {
-    if ((rc = launch_witness_sorts(ctx, k, flags))) return rc;
-    if ((rc = launch_witness_msms(ctx, k, b, nullptr))) return rc;
-    if ((rc = build_abc_device(ctx, k, b.d_w, wit_mont, b.d_abc, fly == 0))) return rc;
-    if ((rc = g16_quotient_device(ctx, b.d_abc, b.d_abc + n, b.d_abc + 2 * n, k->log2n, (int)k->flavour, b.d_qs, fly))) return rc;
-    return launch_h_and_collect(ctx, k, b.d_qs + k->h_lo, flags, b, out_partials);
-  }
-  if ((rc = build_abc_device(ctx, k, b.d_w, wit_mont, b.d_abc, fly == 0))) return rc;
-  if ((rc = g16_quotient_device(ctx, b.d_abc, b.d_abc + n, b.d_abc + 2 * n, k->log2n, (int)k->flavour, b.d_qs, fly))) return rc;
-  // ... and the bucket arrangement of the H scalars too: its dozen short kernels would otherwise queue, one after the
-  // other, behind the GPU-filling accumulate waves of the four witness lanes (measured: 6 ms for a 0.5-ms sort)
-  if ((rc = launch_h_sort(ctx, k, b.d_qs + k->h_lo))) return rc;
-  hipEvent_t after = nullptr;
-  if (g16_env().lanes_after_quotient) {
-    HIPCHK(ctx, hipEventRecord(ctx->ev[g16_ctx::EV_Q].get(), ctx->stream));
-    after = ctx->ev[g16_ctx::EV_Q].get();
-  }
-  if ((rc = launch_witness_sorts(ctx, k, flags))) return rc;
-  if ((rc = launch_witness_msms(ctx, k, b, after))) return rc;
-  return launch_h_and_collect(ctx, k, b.d_qs + k->h_lo, flags, b, out_partials, true);
 }
 
 // ---- sharded proof with a task-parallel quotient ------------------------------------------------------------
@@ -488,28 +375,9 @@ extern "C" int32_t g16_prove_partials_begin(g16_ctx* ctx, const g16_pkey* k, con
     return G16_EINVAL;
   }
   CTX_ENTER(ctx);
-  const size_t n = size_t(1) << k->log2n;
-  ProveBufs b;
-  int32_t rc = prove_bufs(ctx, k, b);
-  if (!rc) rc = upload_witness(ctx, k, witness, flags, b);
-  if (!rc && task_mask) {   // this rank's coset pipelines go to the GPU first: every other rank waits for their slices
-    rc = build_abc_device(ctx, k, b.d_w, (flags & G16_SCALARS_MONT) ? 1u : 0u, b.d_abc, (task_mask & 4u) != 0);
-    u256* out = (u256*)d_task_out;
-    for (int v = 0; v < 3 && !rc; ++v)
-      if (task_mask & (1u << v)) {
-        rc = g16_coset_pipeline_device(ctx, b.d_abc + v * n, k->log2n, out);
-        out += n;
-      }
-  }
-  hipEvent_t after = nullptr;
-  if (!rc && task_mask && g16_env().quotient_first && g16_env().lanes_after_quotient) {
-    rc = g16_hip_check(ctx->err, "hipEventRecord(ev_q)", hipEventRecord(ctx->ev[g16_ctx::EV_Q].get(), ctx->stream));
-    after = ctx->ev[g16_ctx::EV_Q].get();
-  }
-  if (!rc) rc = launch_witness_sorts(ctx, k, flags);
-  if (!rc) rc = launch_witness_msms(ctx, k, b, after);
-  if (!rc && !(flags & G16_NO_HOST_SYNC))   // the task outputs are complete; the lanes run on
-    rc = g16_hip_check(ctx->err, "hipStreamSynchronize", hipStreamSynchronize(ctx->stream));
+  ProofArgs a;
+  a.witness = witness, a.flags = flags, a.task_out = (u256*)d_task_out;
+  const int32_t rc = run_plan(ctx, k, PROOF_BEGIN, task_mask, !(flags & G16_NO_HOST_SYNC), a);
   if (rc != G16_OK) {
     ctx_quiesce(ctx);
     return rc;
@@ -532,10 +400,9 @@ extern "C" int32_t g16_prove_partials_end(g16_ctx* ctx, const g16_pkey* k, const
   }
   CTX_ENTER_KEEP(ctx);
   ctx->shard_begun = nullptr;
-  ProveBufs b;
-  int32_t rc = prove_bufs(ctx, k, b);
-  if (!rc) rc = g16_abc_pointwise_device(ctx, d_a1, d_b1, d_c1, nh, b.d_qs);
-  if (!rc) rc = launch_h_and_collect(ctx, k, b.d_qs, flags, b, out_partials);
+  ProofArgs a;
+  a.flags = flags, a.d_a1 = d_a1, a.d_b1 = d_b1, a.d_c1 = d_c1, a.qs_is_slice = true, a.out_partials = out_partials;
+  const int32_t rc = run_plan(ctx, k, PROOF_END, 0, !((flags & G16_NO_HOST_SYNC) && (flags & G16_OUT_DEVICE)), a);
   if (rc != G16_OK) ctx_quiesce(ctx);
   return rc;
 }

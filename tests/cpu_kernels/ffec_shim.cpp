@@ -6,6 +6,7 @@
 #include "../../nim_groth16_amd/csrc/msm_plan.hpp"
 #include "../../nim_groth16_amd/csrc/spmv_params.hpp"
 #include "../../nim_groth16_amd/csrc/ntt_plan.hpp"
+#include "../../nim_groth16_amd/csrc/proof_plan.hpp"
 #include <cstring>
 #include <vector>
 using namespace g16;
@@ -188,6 +189,44 @@ void shim_msm_plan(uint64_t n, uint32_t flags, int table_cfg, int is_g1, int nar
     out[40 + 5 * g] = job_size.bytes;
   }
   shim_tail_out(T, out + 46);
+}
+
+// The launch schedule of a proof (proof_plan.hpp).  knobs: {quotient_first, lanes_after_quotient, g1_batch, chain_ch,
+// cu_split, cz_on_the_fly, g2_first, g1_lanes[3]} as G16Env holds them; shape: {nw, nh, log2n, liveA, liveB, cfg_equal}.
+// out: {fits, count, narrow_tail, sort_a, sort_b}, then {op, stream, a, b, c, d, e} per step.  -> count
+int shim_proof_plan(const int* knobs, int entry, uint32_t task_mask, int host_sync, const uint64_t* shape, int cap,
+                    int32_t* out) {
+  G16Env env;
+  env.quotient_first = knobs[0], env.lanes_after_quotient = knobs[1], env.g1_batch = knobs[2], env.chain_ch = knobs[3];
+  env.cu_split = knobs[4], env.cz_on_the_fly = knobs[5], env.g2_first = knobs[6];
+  for (int i = 0; i < 3; ++i) env.g1_lanes[i] = knobs[7 + i];
+  const ProofShape s{(size_t)shape[0], (size_t)shape[1], (uint32_t)shape[2], shape[3] != 0, shape[4] != 0, shape[5] != 0};
+  ProofPlan p;
+  out[0] = proof_plan_build(p, env, (ProofEntry)entry, task_mask, host_sync != 0, s, cap) ? 1 : 0;
+  out[1] = p.count, out[2] = p.narrow_tail, out[3] = p.sort_a, out[4] = p.sort_b;
+  for (int i = 0; i < p.count; ++i) {
+    const ProofStep& t = p.steps[i];
+    const int32_t v[7] = {t.op, t.stream, t.a, t.b, t.c, t.d, t.e};
+    for (int j = 0; j < 7; ++j) out[5 + 7 * i + j] = v[j];
+  }
+  return p.count;
+}
+// the helpers next to it: the sparsity predicate at G16_INF_COMPACT = pct, the CU mask at G16_CU_SPLIT = k, the
+// priority of stream `index` under G16_STREAM_PRIO = cfg (six characters)
+int shim_points_sparse(uint64_t n_inf, uint64_t n, int pct) {
+  G16Env env;
+  env.inf_compact_pct = pct;
+  return points_sparse(n_inf, n, env) ? 1 : 0;
+}
+void shim_cu_mask(int k, int front, uint32_t* mask) {
+  G16Env env;
+  env.cu_split = k;
+  stream_cu_mask(env, front != 0, mask);
+}
+int shim_stream_priority(const char* cfg, int index, int lo, int hi) {
+  G16Env env;
+  memcpy(env.stream_prio, cfg, 6);
+  return stream_priority(env, index, lo, hi);
 }
 
 // the class bucket set of registered point sets with two multiplier tables (msm_params.hpp): every digit magnitude
