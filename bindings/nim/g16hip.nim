@@ -42,6 +42,7 @@ proc g16_msm_g2(ctx: ptr G16Ctx, scalars: pointer, flags: uint32, points: pointe
 proc g16_ntt_fr(ctx: ptr G16Ctx, src, dst: pointer, log2n: uint32, inverse: int32): int32 {.importc, header: "g16hip.h".}
 proc g16_quotient(ctx: ptr G16Ctx, az, bz, cz: pointer, log2n, flavour: uint32, res: pointer): int32 {.importc, header: "g16hip.h".}
 proc g16_pkey_create(ctx: ptr G16Ctx, desc: ptr G16PKeyDesc, key: ptr ptr G16PKey): int32 {.importc, header: "g16hip.h".}
+proc g16_pkey_create_lean(ctx: ptr G16Ctx, desc: ptr G16PKeyDesc, tableStride: uint32, key: ptr ptr G16PKey): int32 {.importc, header: "g16hip.h".}
 proc g16_prove(ctx: ptr G16Ctx, key: ptr G16PKey, witness: pointer, flags: uint32, r, s: pointer, res: ptr G16Proof): int32 {.importc, header: "g16hip.h".}
 # points at infinity per ProverPoints array (A1, B1, B2, C1, H1, B1-and-B2) and whether A1 / B1+B2 run on compacted
 # entry lists: snarkjs keys hold (0,0) for every wire absent from a matrix (curves.nim:95-107 accepts them)
@@ -90,7 +91,9 @@ proc computeQuotientGpu*(valuesAz, valuesBz, valuesCz: seq[Fr], flavour: Flavour
                      uint32(createDomain(n).logDomainSize), uint32(ord(flavour)), addr result[0])
 
 var gkey: ptr G16PKey
-proc loadKeyGpu*(zkey: ZKey) =
+proc loadKeyGpu*(zkey: ZKey, tableStride = 0) =
+  ## tableStride >= 2: a lean key -- every ProverPoints array keeps window tables for every tableStride-th window only:
+  ## about 1 / tableStride of the HBM, more bucket reduction per proof, the same proof bytes (include/g16hip.h "lean")
   var cs = newSeq[G16Coeff](zkey.coeffs.len)
   for i, c in zkey.coeffs:                                  # zkey_types.nim:48-52
     cs[i] = G16Coeff(matrix: uint32(ord(c.matrix)), row: uint32(c.row), col: uint32(c.col))
@@ -103,7 +106,7 @@ proc loadKeyGpu*(zkey: ZKey) =
     alpha1: unsafeAddr zkey.specPoints.alpha1, beta1: unsafeAddr zkey.specPoints.beta1,
     delta1: unsafeAddr zkey.specPoints.delta1, beta2: unsafeAddr zkey.specPoints.beta2,
     delta2: unsafeAddr zkey.specPoints.delta2, shard_index: 0, shard_count: 1)
-  check g16_pkey_create(gctx, addr d, addr gkey)
+  check g16_pkey_create_lean(gctx, addr d, uint32(tableStride), addr gkey)
 
 proc generateProofWithMask*(nthreads: int, printTimings: bool, zkey: ZKey, wtns: Witness, mask: Mask): Proof =
   assert zkey.header.curve == wtns.curve and zkey.header.nvars == wtns.values.len   # prover.nim:224,236
@@ -182,6 +185,7 @@ type
 proc g16_group_create(devices: ptr int32, ndev: int32, grp: ptr ptr G16Group): int32 {.importc, header: "g16hip.h".}
 proc g16_group_last_error(grp: ptr G16Group): cstring {.importc, header: "g16hip.h".}
 proc g16_group_pkey_create(grp: ptr G16Group, desc: ptr G16PKeyDesc, key: ptr ptr G16GroupKey): int32 {.importc, header: "g16hip.h".}
+proc g16_group_pkey_create_lean(grp: ptr G16Group, desc: ptr G16PKeyDesc, tableStride: uint32, key: ptr ptr G16GroupKey): int32 {.importc, header: "g16hip.h".}
 proc g16_group_prove(grp: ptr G16Group, key: ptr G16GroupKey, witness: pointer, flags: uint32, r, s: pointer,
                      res: ptr G16Proof): int32 {.importc, header: "g16hip.h".}
 
@@ -199,7 +203,7 @@ proc initG16Hip*(devices: openArray[int]) =
   if g16_group_create(addr ds[0], int32(ds.len), addr ggroup) != 0:
     raise newException(AssertionDefect, "g16hip: g16_group_create failed")
 
-proc loadKeyGroup*(zkey: ZKey) =
+proc loadKeyGroup*(zkey: ZKey, tableStride = 0) =
   ## like loadKeyGpu, sharded: member g keeps index range g of every ProverPoints array (msm.nim:105-115)
   var cs = newSeq[G16Coeff](zkey.coeffs.len)
   for i, c in zkey.coeffs:
@@ -213,7 +217,7 @@ proc loadKeyGroup*(zkey: ZKey) =
     alpha1: unsafeAddr zkey.specPoints.alpha1, beta1: unsafeAddr zkey.specPoints.beta1,
     delta1: unsafeAddr zkey.specPoints.delta1, beta2: unsafeAddr zkey.specPoints.beta2,
     delta2: unsafeAddr zkey.specPoints.delta2, shard_index: 0, shard_count: 1)
-  checkGroup g16_group_pkey_create(ggroup, addr d, addr ggroupKey)
+  checkGroup g16_group_pkey_create_lean(ggroup, addr d, uint32(tableStride), addr ggroupKey)
 
 proc generateProofWithMaskGroup*(nthreads: int, printTimings: bool, zkey: ZKey, wtns: Witness, mask: Mask): Proof =
   ## generateProofWithMask (prover.nim:215-304) over the device group: bit-identical to the one-GPU proof

@@ -113,6 +113,35 @@ size_t g16_points_inf_count(const g16_points* pts);
  * ([m][w][i] = 2^(c w + m) P_i).  An MSM against it performs count * W bucket additions + 2 reduction additions per
  * bucket: 2^(c-1) buckets with one table per window, 0.67 * 2^(c-1) with two (the class bucket set, msm.cuh) */
 int32_t g16_points_info(const g16_points* pts, uint32_t* window_bits, uint32_t* ntables);
+
+/* ---- lean point sets: window tables at a stride ------------------------------------------------------
+ * The calls above store a table for EVERY window (two with the class bucket set): about 10 GB of HBM per 2^20
+ * constraints of a proving key.  A set registered at table_stride s >= 2 stores a table for every s-th window only --
+ * table j holds 2^(c s j) P_i -- and window w = s j + r gathers from table j into bucket set r:
+ *     sum_w 2^(c w) D_w  =  sum_{r < s} 2^(c r) * ( sum_j 2^(c s j) D_{s j + r} ).
+ * The trade, in the terms of the cost model that picks c (W = 254 / c + 1 windows):
+ *     bucket additions     count * W, as before
+ *     reduction additions  2 * s * 2^(c-1): s bucket sets of 2^(c-1) buckets instead of one (c <= 16, as for a
+ *                          one-shot MSM), then a Horner fold of s sums with c doublings each
+ *     tables               ceil(W / s) instead of W: the bytes shrink by about s
+ * s above W is W: one table, the layout of a one-shot MSM with the points resident.  A lean set has one table per stored
+ * window (never the class bucket set).  table_stride 0 or 1 is exactly g16_points_register_*: same tables, same
+ * launches, same results.  Everything that takes a g16_points takes a lean one; results are the same canonical bytes. */
+int32_t g16_points_register_g1_lean(g16_ctx* ctx, const void* points, size_t n, uint32_t table_stride, g16_points** out);
+int32_t g16_points_register_g2_lean(g16_ctx* ctx, const void* points, size_t n, uint32_t table_stride, g16_points** out);
+int32_t g16_points_register_g1_lean_dev(g16_ctx* ctx, const void* d_points, size_t n, uint32_t table_stride,
+                                        g16_points** out);
+int32_t g16_points_register_g2_lean_dev(g16_ctx* ctx, const void* d_points, size_t n, uint32_t table_stride,
+                                        g16_points** out);
+/* HBM held by the set's tables: ntables * count * 64 bytes (G1) or * 128 (G2), ntables as g16_points_info reports it
+ * (ceil(W / s) for a lean set) */
+int32_t g16_points_table_bytes(const g16_points* pts, size_t* bytes);
+/* What registering n points of group 1 (G1) or 2 (G2) at table_stride would choose: window bits, tables, and the bytes
+ * of HBM they take.  A pure function -- no device, no context: what a caller with a memory budget calls before
+ * registering.  (With two tables per window, a set that finds no room in HBM falls back to one; g16_points_table_bytes
+ * reports what a registered set holds.)  Any out pointer may be NULL. */
+int32_t g16_points_plan(int group, size_t n, uint32_t table_stride, uint32_t* window_bits, uint32_t* ntables,
+                        size_t* bytes);
 /* sum_i scalars[i] * P_i over the whole registered set (scalars: g16_points_count elements);
  * flags = G16_SCALARS_MONT/STD | G16_SCALARS_DEVICE | G16_OUT_PARTIAL.  This is the call a prover makes
  * per proof for msmMultiThreadedG1/G2 (groth16/prover.nim:282,288,294,301,302). */
@@ -191,6 +220,11 @@ int32_t g16_pkey_create(g16_ctx* ctx, const g16_pkey_desc* desc, g16_pkey** out)
  * without being parsed.  c R^2 is also exactly what buildABC multiplies a raw .wtns value with: (c R^2) w / R = c w R. */
 int32_t g16_pkey_create_zkey(g16_ctx* ctx, const g16_pkey_desc* desc, const void* section4, size_t section4_bytes,
                              g16_pkey** out);
+/* The same two with all five point sets of the key registered at one table stride (g16_points_register_*_lean):
+ * table_stride 0 or 1 is exactly g16_pkey_create / g16_pkey_create_zkey.  Proofs are the same bytes at every stride. */
+int32_t g16_pkey_create_lean(g16_ctx* ctx, const g16_pkey_desc* desc, uint32_t table_stride, g16_pkey** out);
+int32_t g16_pkey_create_zkey_lean(g16_ctx* ctx, const g16_pkey_desc* desc, const void* section4, size_t section4_bytes,
+                                  uint32_t table_stride, g16_pkey** out);
 void g16_pkey_destroy(g16_pkey* key);
 /* points at infinity per ProverPoints array of this key (this shard): out[0..4] = A1, B1, B2, C1, H1; out[5] = wires
  * whose B1 AND B2 points are both (0,0); out[6] / out[7] = 1 if A1 / B1+B2 run on compacted entry lists (their own
@@ -279,6 +313,9 @@ void g16_group_destroy(g16_group* group);
 int32_t g16_group_size(const g16_group* group);
 const char* g16_group_last_error(const g16_group* group);
 int32_t g16_group_pkey_create(g16_group* group, const g16_pkey_desc* desc, g16_group_pkey** out);
+/* ... with every member's point sets at one table stride (g16_pkey_create_lean) */
+int32_t g16_group_pkey_create_lean(g16_group* group, const g16_pkey_desc* desc, uint32_t table_stride,
+                                   g16_group_pkey** out);
 void g16_group_pkey_destroy(g16_group_pkey* key);
 int32_t g16_group_prove(g16_group* group, const g16_group_pkey* key, const void* witness, uint32_t flags,
                         const void* mask_r, const void* mask_s, g16_proof* out);

@@ -6,7 +6,7 @@ libg16hip.so (include/g16hip.h).  All arithmetic runs in hand-written HIP kernel
 fallback -- importing works anywhere, but every compute call raises without the HIP library + a GPU.
 """
 from ._lib import (G16Error, Context, DeviceGroup, GroupKey, HostBuffer, ProverPool, ProvingKey,  # noqa: F401
-                   PointSet, VerifyingKey, lib_path, load_library)
+                   PointSet, VerifyingKey, lib_path, load_library, points_plan)
 from .msm import (msmMultiThreadedG1, msmMultiThreadedG2, msmG1, msmG2)  # noqa: F401
 from .ntt import (Domain, createDomain, forwardNTT, inverseNTT, extendAndForwardNTT,  # noqa: F401
                   polyForwardNTT, polyInverseNTT)

@@ -28,6 +28,9 @@ SYMBOLS = [
     "g16_group_pkey_create", "g16_group_pkey_destroy", "g16_group_prove",
     "g16_prover_create", "g16_prover_destroy", "g16_prover_last_error", "g16_prover_submit", "g16_prover_poll",
     "g16_prover_collect", "g16_host_alloc", "g16_host_free",
+    "g16_points_register_g1_lean", "g16_points_register_g2_lean", "g16_points_register_g1_lean_dev",
+    "g16_points_register_g2_lean_dev", "g16_points_table_bytes", "g16_points_plan", "g16_pkey_create_lean",
+    "g16_pkey_create_zkey_lean", "g16_group_pkey_create_lean",
 ]
 VERIFY_SUBGROUP = 16
 GT_BYTES = 384
@@ -126,6 +129,14 @@ def load_library():
     for name in ("g16_points_register_g1", "g16_points_register_g2", "g16_points_register_g1_dev",
                  "g16_points_register_g2_dev"):
         getattr(lib, name).argtypes = [vp, vp, sz, ctypes.POINTER(vp)]
+    for name in ("g16_points_register_g1_lean", "g16_points_register_g2_lean", "g16_points_register_g1_lean_dev",
+                 "g16_points_register_g2_lean_dev"):
+        getattr(lib, name).argtypes = [vp, vp, sz, u32, ctypes.POINTER(vp)]
+    lib.g16_points_table_bytes.argtypes = [vp, ctypes.POINTER(sz)]
+    lib.g16_points_plan.argtypes = [ctypes.c_int, sz, u32, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(sz)]
+    lib.g16_pkey_create_lean.argtypes = [vp, ctypes.POINTER(PkeyDesc), u32, ctypes.POINTER(vp)]
+    lib.g16_pkey_create_zkey_lean.argtypes = [vp, ctypes.POINTER(PkeyDesc), vp, sz, u32, ctypes.POINTER(vp)]
+    lib.g16_group_pkey_create_lean.argtypes = [vp, ctypes.POINTER(PkeyDesc), u32, ctypes.POINTER(vp)]
     lib.g16_points_release.argtypes = [vp]
     lib.g16_points_release.restype = None
     lib.g16_points_count.argtypes = [vp]
@@ -272,10 +283,17 @@ class Context:
         self._check(fn(self._h, s, SCALARS_MONT if mont else SCALARS_STD, p, n, out))
         return out.raw
 
-    def register_points(self, group: int, points, n: int, device: bool = False) -> "PointSet":
+    def register_points(self, group: int, points, n: int, device: bool = False, table_stride: int = 0) -> "PointSet":
+        """table_stride >= 2: a lean set -- window tables for every table_stride-th window only (points_plan tells the
+        bytes beforehand); 0 or 1: a table per window"""
         h = ctypes.c_void_p()
-        name = f"g16_points_register_g{group}" + ("_dev" if device else "")
-        self._check(getattr(self._lib, name)(self._h, _buf(points) if n else None, n, ctypes.byref(h)))
+        p = _buf(points) if n else None
+        if table_stride:
+            name = f"g16_points_register_g{group}_lean" + ("_dev" if device else "")
+            self._check(getattr(self._lib, name)(self._h, p, n, table_stride, ctypes.byref(h)))
+        else:
+            name = f"g16_points_register_g{group}" + ("_dev" if device else "")
+            self._check(getattr(self._lib, name)(self._h, p, n, ctypes.byref(h)))
         return PointSet(self, h, group, n)
 
     def msm_points(self, pts: "PointSet", scalars, mont: bool = True, device: bool = False,
@@ -377,12 +395,17 @@ class Context:
 class ProvingKey:
     """Device-resident proving key (g16_pkey): registered ProverPoints + CSR of the A/B matrices."""
 
-    def __init__(self, ctx: Context, desc: PkeyDesc, keepalive, section4: bytes = None):
+    def __init__(self, ctx: Context, desc: PkeyDesc, keepalive, section4: bytes = None, table_stride: int = 0):
         """section4: the .zkey file's coefficient section as it lies on disk (g16_pkey_create_zkey); desc.coeffs must
-        then be NULL"""
+        then be NULL.  table_stride: all five point sets as lean sets (Context.register_points)"""
         self.ctx = ctx
         h = ctypes.c_void_p()
-        if section4 is not None:
+        if table_stride and section4 is not None:
+            ctx._check(ctx._lib.g16_pkey_create_zkey_lean(ctx._h, ctypes.byref(desc), _buf(section4), len(section4),
+                                                          table_stride, ctypes.byref(h)))
+        elif table_stride:
+            ctx._check(ctx._lib.g16_pkey_create_lean(ctx._h, ctypes.byref(desc), table_stride, ctypes.byref(h)))
+        elif section4 is not None:
             ctx._check(ctx._lib.g16_pkey_create_zkey(ctx._h, ctypes.byref(desc), _buf(section4), len(section4),
                                                      ctypes.byref(h)))
         else:
@@ -516,9 +539,12 @@ class DeviceGroup:
     def size(self) -> int:
         return self._lib.g16_group_size(self._h)
 
-    def load_key(self, desc: PkeyDesc, keepalive=None) -> "GroupKey":
+    def load_key(self, desc: PkeyDesc, keepalive=None, table_stride: int = 0) -> "GroupKey":
         h = ctypes.c_void_p()
-        self._check(self._lib.g16_group_pkey_create(self._h, ctypes.byref(desc), ctypes.byref(h)))
+        if table_stride:
+            self._check(self._lib.g16_group_pkey_create_lean(self._h, ctypes.byref(desc), table_stride, ctypes.byref(h)))
+        else:
+            self._check(self._lib.g16_group_pkey_create(self._h, ctypes.byref(desc), ctypes.byref(h)))
         return GroupKey(self, h, desc.nvars)
 
     def close(self):
@@ -705,6 +731,17 @@ class VerifyingKey:
             pass
 
 
+def points_plan(group: int, n: int, table_stride: int = 0):
+    """(window bits, tables, bytes of HBM) that registering n points of group 1 (G1) / 2 (G2) at table_stride would
+    choose: g16_points_plan, a pure function -- no GPU, no context.  What a caller with a memory budget asks first."""
+    lib = load_library()
+    c, t, b = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_size_t()
+    rc = lib.g16_points_plan(group, n, table_stride, ctypes.byref(c), ctypes.byref(t), ctypes.byref(b))
+    if rc != G16_OK:
+        raise G16Error(rc, "g16_points_plan: bad group, or too many points for 31-bit entry indices")
+    return c.value, t.value, b.value
+
+
 class PointSet:
     """Device-resident point set with precomputed window tables (g16_points)."""
 
@@ -721,6 +758,13 @@ class PointSet:
         c, w = ctypes.c_uint32(), ctypes.c_uint32()
         self.ctx._check(self.ctx._lib.g16_points_info(self._h, ctypes.byref(c), ctypes.byref(w)))
         return c.value, w.value
+
+    @property
+    def table_bytes(self) -> int:
+        """HBM held by the set's window tables (g16_points_table_bytes)"""
+        b = ctypes.c_size_t()
+        self.ctx._check(self.ctx._lib.g16_points_table_bytes(self._h, ctypes.byref(b)))
+        return b.value
 
     def _free(self):
         if self._h:

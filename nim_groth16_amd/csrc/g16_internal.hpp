@@ -199,8 +199,10 @@ struct g16_points {
   size_t n = 0;
   uint32_t c = 0, nwin = 0;
   uint32_t mtab = 1;         // multiplier tables per window: 1, or 2 = {1, 2} with the class bucket set (msm.cuh)
-  uint32_t cfg() const { return c | (mtab << 8); }   // the `table_cfg` of g16_msm_sort / msm_device
-  DevMem<> d_tables;         // mtab * nwin * n affine points: [m][w][i] = 2^(c w + m) P_i
+  uint32_t stride = 1;       // a table for every stride-th window: 1, or >= 2 for a lean set (msm_plan.hpp; mtab == 1)
+  uint32_t ntables() const { return mtab * ((nwin + stride - 1) / stride); }
+  uint32_t cfg() const { return g16::msm_table_cfg(c, mtab, stride); }   // the `table_cfg` of g16_msm_sort / msm_device
+  DevMem<> d_tables;         // ntables() * n affine points: [m][j][i] = 2^(c stride j + m) P_i
   DevMem<uint32_t> d_live;      // bitmap: bit i set <=> point i is not (0,0); ceil(n/32) words
   size_t n_inf = 0;             // points at infinity in the set
 };
@@ -266,7 +268,8 @@ int32_t stage_reduce2_fold(g16_ctx* ctx, hipStream_t st, const g16::MsmParams& P
 template <class C>
 int32_t to29_device(g16_ctx* ctx, hipStream_t st, const void* d_points, size_t n, void* d_out);
 template <class C>
-int32_t precompute_device(g16_ctx* ctx, const void* d_points, size_t n, uint32_t c, uint32_t mtab, void* d_tables);
+int32_t precompute_device(g16_ctx* ctx, const void* d_points, size_t n, uint32_t c, uint32_t mtab, uint32_t stride,
+                          void* d_tables);
 // d_out[i] = d_scalars[i] * generator; d_table: 32*255 points, built first unless table_ready
 template <class C>
 int32_t fixed_base_device(g16_ctx* ctx, void* d_table, bool table_ready, const void* d_scalars, uint32_t mont, size_t n,

@@ -255,7 +255,8 @@ static int32_t msm_entry(g16_ctx* ctx, const void* scalars, uint32_t flags, cons
 
 // ---- registered point sets (ProverPoints are constant per circuit: zkey_types.nim:36-41) ----------------
 template <class C>
-static int32_t points_register(g16_ctx* ctx, const void* points, size_t n, bool on_device, g16_points** out) {
+static int32_t points_register(g16_ctx* ctx, const void* points, size_t n, bool on_device, uint32_t table_stride,
+                               g16_points** out) {
   if (!ctx) return G16_EINVAL;
   if (!out || (n && !points) || n >= (size_t(1) << 26)) {
     ctx->err = "bad argument";
@@ -268,25 +269,28 @@ static int32_t points_register(g16_ctx* ctx, const void* points, size_t n, bool 
   h->device = ctx->device;
   h->group = group_of<C>;
   h->n = n;
-  h->c = msm_pick_table_window(n, g16_env());
+  // window, multiplier tables and stride: msm_table_choice (msm_plan.hpp), which g16_points_plan answers from as well
+  const MsmTableChoice choice = msm_table_choice(n, table_stride, g16_env());
+  h->c = choice.c;
   h->nwin = 254 / h->c + 1;
-  h->mtab = msm_pick_mtab(h->c, g16_env());
+  h->mtab = choice.mtab;
+  h->stride = choice.stride;
   constexpr size_t psz = sizeof(typename C::Aff);
   // Two multiplier tables per window double the set's HBM footprint (~10 GB for a 2^20 key, ~40 GB at 2^22): a set
   // that does not fit that way -- table indices beyond 31 bits, or no room in HBM -- falls back to one table per window
   // and the plain bucket set (the rounds 1-3 layout) instead of failing.
-  if ((size_t)h->mtab * h->nwin * n >= (size_t(1) << 31)) h->mtab = 1;
-  if ((size_t)h->mtab * h->nwin * n >= (size_t(1) << 31)) {
+  // (a lean set, stride >= 2, has one table for every stride-th window and never two per window)
+  if (!choice.fits) {
     ctx->err = "point set too large for 31-bit table indices";
     return G16_EINVAL;
   }
   if (n) {
     // packed reduced-radix entries: 64 / 128 B
-    if (h->mtab == 2 && dev_alloc(h->d_tables, 2 * (size_t)h->nwin * n * psz) != hipSuccess) {
+    if (h->mtab == 2 && dev_alloc(h->d_tables, (size_t)h->ntables() * n * psz) != hipSuccess) {
       (void)hipGetLastError();
       h->mtab = 1;
     }
-    if (!h->d_tables) HIPCHK(ctx, dev_alloc(h->d_tables, (size_t)h->nwin * n * psz));
+    if (!h->d_tables) HIPCHK(ctx, dev_alloc(h->d_tables, (size_t)h->ntables() * n * psz));
     const void* d_src = points;
     int32_t rc;
     if (!on_device) {
@@ -294,7 +298,7 @@ static int32_t points_register(g16_ctx* ctx, const void* points, size_t n, bool 
       HIPCHK(ctx, hipMemcpyAsync(ctx->stage_p.p(), points, n * psz, hipMemcpyHostToDevice, ctx->stream));
       d_src = ctx->stage_p.p();
     }
-    if ((rc = precompute_device<C>(ctx, d_src, n, h->c, h->mtab, h->d_tables.get()))) return rc;
+    if ((rc = precompute_device<C>(ctx, d_src, n, h->c, h->mtab, h->stride, h->d_tables.get()))) return rc;
     // which points are (0,0): snarkjs keys hold the point at infinity for every wire absent from a matrix
     uint32_t n_inf = 0;
     HIPCHK(ctx, dev_alloc(h->d_live, ((n + 31) / 32 + 1) * 4));
@@ -310,16 +314,51 @@ static int32_t points_register(g16_ctx* ctx, const void* points, size_t n, bool 
   return G16_OK;
 }
 extern "C" int32_t g16_points_register_g1(g16_ctx* ctx, const void* points, size_t n, g16_points** out) {
-  return points_register<G1>(ctx, points, n, false, out);
+  return points_register<G1>(ctx, points, n, false, 0, out);
 }
 extern "C" int32_t g16_points_register_g2(g16_ctx* ctx, const void* points, size_t n, g16_points** out) {
-  return points_register<G2>(ctx, points, n, false, out);
+  return points_register<G2>(ctx, points, n, false, 0, out);
 }
 extern "C" int32_t g16_points_register_g1_dev(g16_ctx* ctx, const void* d_points, size_t n, g16_points** out) {
-  return points_register<G1>(ctx, d_points, n, true, out);
+  return points_register<G1>(ctx, d_points, n, true, 0, out);
 }
 extern "C" int32_t g16_points_register_g2_dev(g16_ctx* ctx, const void* d_points, size_t n, g16_points** out) {
-  return points_register<G2>(ctx, d_points, n, true, out);
+  return points_register<G2>(ctx, d_points, n, true, 0, out);
+}
+// ... at a table stride (0 / 1: exactly the calls above)
+extern "C" int32_t g16_points_register_g1_lean(g16_ctx* ctx, const void* points, size_t n, uint32_t table_stride,
+                                               g16_points** out) {
+  return points_register<G1>(ctx, points, n, false, table_stride, out);
+}
+extern "C" int32_t g16_points_register_g2_lean(g16_ctx* ctx, const void* points, size_t n, uint32_t table_stride,
+                                               g16_points** out) {
+  return points_register<G2>(ctx, points, n, false, table_stride, out);
+}
+extern "C" int32_t g16_points_register_g1_lean_dev(g16_ctx* ctx, const void* d_points, size_t n, uint32_t table_stride,
+                                                   g16_points** out) {
+  return points_register<G1>(ctx, d_points, n, true, table_stride, out);
+}
+extern "C" int32_t g16_points_register_g2_lean_dev(g16_ctx* ctx, const void* d_points, size_t n, uint32_t table_stride,
+                                                   g16_points** out) {
+  return points_register<G2>(ctx, d_points, n, true, table_stride, out);
+}
+// What registering n points of `group` at `table_stride` chooses, without a device or a context: window bits, tables and
+// the HBM they take (64 B per G1 entry, 128 B per G2 entry) -- what a caller with a memory budget asks first.  (A set
+// with two tables per window that finds no room in HBM falls back to one at registration; g16_points_table_bytes tells.)
+extern "C" int32_t g16_points_plan(int group, size_t n, uint32_t table_stride, uint32_t* window_bits, uint32_t* ntables,
+                                   size_t* bytes) {
+  if ((group != 1 && group != 2) || n >= (size_t(1) << 26)) return G16_EINVAL;
+  const MsmTableChoice choice = msm_table_choice(n, table_stride, g16_env());
+  if (!choice.fits) return G16_EINVAL;
+  if (window_bits) *window_bits = choice.c;
+  if (ntables) *ntables = choice.ntables;
+  if (bytes) *bytes = (size_t)choice.ntables * n * (group == 1 ? sizeof(g1_aff) : sizeof(g2_aff));
+  return G16_OK;
+}
+extern "C" int32_t g16_points_table_bytes(const g16_points* h, size_t* bytes) {
+  if (!h || !bytes) return G16_EINVAL;
+  *bytes = (size_t)h->ntables() * h->n * (h->group == 1 ? sizeof(g1_aff) : sizeof(g2_aff));
+  return G16_OK;
 }
 extern "C" void g16_points_release(g16_points* h) {
   if (!h) return;
@@ -339,7 +378,7 @@ extern "C" size_t g16_points_count(const g16_points* h) { return h ? h->n : 0; }
 extern "C" int32_t g16_points_info(const g16_points* h, uint32_t* window_bits, uint32_t* ntables) {
   if (!h) return G16_EINVAL;
   if (window_bits) *window_bits = h->c;
-  if (ntables) *ntables = h->nwin * h->mtab;
+  if (ntables) *ntables = h->ntables();
   return G16_OK;
 }
 

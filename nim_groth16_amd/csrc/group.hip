@@ -118,7 +118,9 @@ static int32_t for_members(g16_group* g, F fn) {
   return G16_OK;
 }
 
-extern "C" int32_t g16_group_pkey_create(g16_group* g, const g16_pkey_desc* desc, g16_group_pkey** out) {
+// table_stride: every member registers its shard's point sets at this stride (0 / 1: a table per window)
+extern "C" int32_t g16_group_pkey_create_lean(g16_group* g, const g16_pkey_desc* desc, uint32_t table_stride,
+                                              g16_group_pkey** out) {
   if (!g) return G16_EINVAL;
   if (!desc || !out) {
     g->err = "null argument";
@@ -147,7 +149,7 @@ extern "C" int32_t g16_group_pkey_create(g16_group* g, const g16_pkey_desc* desc
     d.shard_index = (uint32_t)i;
     d.shard_count = (uint32_t)G;
     g16_ctx* ctx = g->m[i].ctx;   // for_members reports this member's error text
-    int32_t r = g16_pkey_create(ctx, &d, &k->key[i]);
+    int32_t r = g16_pkey_create_lean(ctx, &d, table_stride, &k->key[i]);
     if (r != G16_OK) return r;
     k->h_lo[i] = (n * i) / G;               // msm.nim:107-115: b = (N * (k + 1)) div ntasks
     k->h_hi[i] = (n * (i + 1)) / G;
@@ -163,6 +165,9 @@ extern "C" int32_t g16_group_pkey_create(g16_group* g, const g16_pkey_desc* desc
   if (rc != G16_OK) return rc;
   *out = k.release();
   return G16_OK;
+}
+extern "C" int32_t g16_group_pkey_create(g16_group* g, const g16_pkey_desc* desc, g16_group_pkey** out) {
+  return g16_group_pkey_create_lean(g, desc, 0, out);
 }
 
 extern "C" int32_t g16_group_prove(g16_group* g, const g16_group_pkey* k, const void* witness, uint32_t flags,

@@ -137,6 +137,25 @@ __device__ __forceinline__ void msm_digits(const u256* __restrict__ scalars, con
   }
 }
 
+// Where the entry of digit (window w, pair i) goes: the offset of its bucket set, in units of 1 << shift buckets, and the
+// table-major index of its point.  LEAN: a set with tables at a stride >= 2 (msm_window_slot divides).  The two ends of
+// the family -- no tables, a table per window -- divide nothing and keep the expressions they always had; the host picks
+// the instantiation (g16_msm_sort).
+template <bool LEAN>
+__device__ __forceinline__ void msm_entry_place(const MsmParams& P, uint32_t w, uint32_t i, uint32_t shift,
+                                                uint32_t& set_off, uint32_t& pidx) {
+  if (LEAN) {
+    uint32_t table, set;
+    msm_window_slot(w, P.tstride, table, set);
+    set_off = set << shift;
+    pidx = table * P.n + i;
+  } else {
+    set_off = P.tables ? 0u : (w << shift);
+    pidx = P.tables ? (w * P.n + i) : i;
+  }
+}
+
+template <bool LEAN>
 static __global__ void __launch_bounds__(MSM_BLOCK) msm_count(const u256* __restrict__ scalars,
                                                               const uint32_t* __restrict__ live, MsmParams P,
                                                               uint32_t* __restrict__ count) {
@@ -144,10 +163,13 @@ static __global__ void __launch_bounds__(MSM_BLOCK) msm_count(const u256* __rest
   if (i >= P.n) return;
   const uint32_t bshift = P.c - 1;
   msm_digits(scalars, live, i, P, [&](uint32_t w, uint32_t k, uint32_t) {
-    atomicAdd(&count[(P.tables ? 0u : (w << bshift)) + k], 1u);
+    uint32_t set_off, pidx;
+    msm_entry_place<LEAN>(P, w, i, bshift, set_off, pidx);
+    atomicAdd(&count[set_off + k], 1u);
   });
 }
 
+template <bool LEAN>
 static __global__ void __launch_bounds__(MSM_BLOCK) msm_scatter(const u256* __restrict__ scalars,
                                                          const uint32_t* __restrict__ live, MsmParams P,
                                                          const uint32_t* __restrict__ offset,
@@ -157,10 +179,11 @@ static __global__ void __launch_bounds__(MSM_BLOCK) msm_scatter(const u256* __re
   if (i >= P.n) return;
   const uint32_t bshift = P.c - 1;
   msm_digits(scalars, live, i, P, [&](uint32_t w, uint32_t k, uint32_t neg) {
-    uint32_t b = (P.tables ? 0u : (w << bshift)) + k;
+    uint32_t set_off, pidx;
+    msm_entry_place<LEAN>(P, w, i, bshift, set_off, pidx);
+    uint32_t b = set_off + k;
     uint32_t pos = offset[b] + atomicAdd(&cursor[b], 1u);
     // entry = point index (table-major when tables are used) | sign in bit 31
-    uint32_t pidx = P.tables ? (w * P.n + i) : i;
     entries[pos] = pidx | (neg << 31);
   });
 }
@@ -205,7 +228,7 @@ __device__ __forceinline__ uint32_t lds_rank_add(uint32_t* ctr, uint32_t key) {
 __device__ __forceinline__ uint32_t part_tile_of_block(uint32_t bid, uint32_t ntiles) {
   return (ntiles & 7u) ? bid : (bid & 7u) * (ntiles >> 3) + (bid >> 3);
 }
-template <bool SCATTER>
+template <bool SCATTER, bool LEAN>
 static __global__ void __launch_bounds__(PART_BLOCK) part_pass(const u256* __restrict__ scalars,
                                                                const uint32_t* __restrict__ live, MsmParams P,
                                                                uint32_t lo_bits, uint32_t nparts, uint32_t ntiles,
@@ -221,9 +244,11 @@ static __global__ void __launch_bounds__(PART_BLOCK) part_pass(const u256* __res
     uint32_t i = tile * PART_TILE + r * PART_BLOCK + threadIdx.x;
     if (i < P.n) {
       msm_digits(scalars, live, i, P, [&](uint32_t w, uint32_t k, uint32_t neg) {
-        uint32_t part = (P.tables ? 0u : (w << hi_bits)) | (k >> lo_bits);
+        uint32_t set_off, pidx;
+        msm_entry_place<LEAN>(P, w, i, hi_bits, set_off, pidx);
+        uint32_t part = set_off | (k >> lo_bits);
         uint32_t pos = lds_rank_add(hist, part);
-        if (SCATTER) tmp[pos] = make_uint2((k & lo_mask) | (neg << BS_LOG), P.tables ? w * P.n + i : i);
+        if (SCATTER) tmp[pos] = make_uint2((k & lo_mask) | (neg << BS_LOG), pidx);
       });
     }
   }
@@ -1142,25 +1167,26 @@ __global__ void __launch_bounds__(512, tail_waves<C>()) msm_fold_classes_quad(co
   }
 }
 
-// ---- registration-time precomputation:  table[w][i] = 2^(c w) * P_i  (affine), w = 0..nwin-1 ---------
-// One thread per point: c doublings per window, one inversion per stored point.  Runs once per circuit
-// (the reference loads ProverPoints once per zkey, zkey_types.nim:36-41); trades HBM capacity
-// (nwin x the point set) for the removal of the serial doubling chain from every MSM.
-// mtab == 2: a second set of tables [1][w][i] = 2 * 2^(c w) P_i behind the first (MsmParams::mtab)
+// ---- registration-time precomputation:  table[j][i] = 2^(c s j) * P_i  (affine), j = 0..ntab-1 -------
+// One thread per point: `step` = c s doublings per stored table (s = the table stride, 1 for a table per window), one
+// inversion per stored point.  Runs once per circuit (the reference loads ProverPoints once per zkey,
+// zkey_types.nim:36-41); trades HBM capacity (ntab x the point set) for the removal of the serial doubling chain from
+// every MSM.
+// mtab == 2: a second set of tables [1][j][i] = 2 * 2^(c j) P_i behind the first (MsmParams::mtab; stride 1 only)
 template <class C>
 __global__ void __launch_bounds__(MSM_BLOCK) msm_precompute(const typename C::Aff* __restrict__ points, uint32_t n,
-                                                            uint32_t c, uint32_t nwin, uint32_t mtab,
+                                                            uint32_t step, uint32_t ntab, uint32_t mtab,
                                                             typename Ec29<C>::Tab* __restrict__ tables) {
   uint32_t i = blockIdx.x * MSM_BLOCK + threadIdx.x;
   if (i >= n) return;
   typename C::Aff p = points[i];
   tables[i] = Ec29<C>::tab_from_std(p);
   typename C::Acc acc = C::from_affine(p);
-  for (uint32_t w = 0; w < nwin; ++w) {
+  for (uint32_t w = 0; w < ntab; ++w) {
     if (w) tables[(size_t)w * n + i] = Ec29<C>::tab_from_std(C::to_affine(acc));
     acc = C::dbl(acc);
-    if (mtab == 2) tables[((size_t)nwin + w) * n + i] = Ec29<C>::tab_from_std(C::to_affine(acc));
-    for (uint32_t k = 1; k < c; ++k) acc = C::dbl(acc);
+    if (mtab == 2) tables[((size_t)ntab + w) * n + i] = Ec29<C>::tab_from_std(C::to_affine(acc));
+    for (uint32_t k = 1; k < step; ++k) acc = C::dbl(acc);
   }
 }
 

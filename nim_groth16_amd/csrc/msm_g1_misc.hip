@@ -8,7 +8,7 @@ struct CurveConsts<G1> {
   static u256 b() { return Fp::add(Fp::dbl(Fp::one()), Fp::one()); }
 };
 template int32_t to29_device<G1>(g16_ctx*, hipStream_t, const void*, size_t, void*);
-template int32_t precompute_device<G1>(g16_ctx*, const void*, size_t, uint32_t, uint32_t, void*);
+template int32_t precompute_device<G1>(g16_ctx*, const void*, size_t, uint32_t, uint32_t, uint32_t, void*);
 template int32_t fixed_base_device<G1>(g16_ctx*, void*, bool, const void*, uint32_t, size_t, void*);
 template int32_t on_curve_device<G1>(g16_ctx*, const void*, size_t, uint32_t*);
 template int32_t live_bitmap_device<G1>(g16_ctx*, const void*, size_t, uint32_t*, uint32_t*);

@@ -7,7 +7,7 @@ struct MsmParams {
   uint32_t n;            // number of (scalar, point) pairs
   uint32_t c;            // window bits
   uint32_t nwin;         // number of windows  = 254 / c + 1
-  uint32_t nbuckets;     // tables: 1 << (c-1) (ONE bucket set shared by all windows); else nwin << (c-1)
+  uint32_t nbuckets;     // tables: 1 << (c-1) (ONE bucket set shared by all windows; tstride << (c-1) for a lean set); else nwin << (c-1)
   uint32_t seg;          // L: max entries per accumulate task
   uint32_t scalars_mont; // 1: scalars are Montgomery Fr limbs (Nim seq[Fr]); 0: canonical LE (.wtns)
   uint32_t tables;       // 1: points array holds nwin tables [w][i] = 2^(c w) P_i (registered point set);
@@ -16,6 +16,10 @@ struct MsmParams {
   uint32_t mtab;         // multiplier tables per window (registered sets): 1, or 2 = {1, 2} -- the points array then
                          //    holds tables [m][w][i] = 2^(c w + m) P_i and the bucket set is the CLASS set of msm.cuh
                          //    (msm_class_bucket): 0.67 x the buckets for the same windows
+  uint32_t tstride = 0;  // table stride s of a registered set: a table for every s-th window, [j][i] = 2^(c s j) P_i, and
+                         //    window w = s j + r gathers from table j into bucket set r (msm_window_slot).  0: no tables,
+                         //    1: a table per window (one bucket set; `tables`, `mtab` as above), >= 2: a lean set --
+                         //    ceil(nwin / s) tables, s bucket sets of 2^(c-1) buckets, mtab = 1
 };
 // number of buckets of a merged (registered) bucket set
 inline uint32_t msm_table_buckets(uint32_t c, uint32_t mtab) {
@@ -62,6 +66,22 @@ G16_MSMP_HD void bs_block(uint32_t bid, uint32_t nparts, uint32_t& part, uint32_
   } else {
     part = bid / BS_SPLIT;
     q = bid % BS_SPLIT;
+  }
+}
+// window w of a point set stored at table stride s -> (table j, bucket set r), w = s j + r:
+//   sum_w 2^(c w) D_w  =  sum_{r < s} 2^(c r) * ( sum_j 2^(c s j) D_{s j + r} ).
+// s = 0 (no tables: every window is its own bucket set) and s = 1 (a table per window: one bucket set) are the two ends
+// and divide nothing.
+G16_MSMP_HD void msm_window_slot(uint32_t w, uint32_t tstride, uint32_t& table, uint32_t& set) {
+  if (tstride == 1) {
+    table = w;
+    set = 0;
+  } else if (tstride == 0) {
+    table = 0;
+    set = w;
+  } else {
+    table = w / tstride;
+    set = w - table * tstride;
   }
 }
 // digit magnitude t in [1, 2^(c-1)] -> (class bucket, table selector s): t = 2^s * weight(bucket); see msm.cuh

@@ -17,7 +17,8 @@ namespace g16 {
 // with precomputed 2^(c w) tables (`merged`).  A short top window (t = 254 - (nwin-1) c bits) would map all n
 // scalars onto 2^t buckets, so candidates need t >= min(c-2, 6).  2^20 points: c = 16 plain, c = 20 merged
 // (13 tables instead of 16 windows).
-inline uint32_t msm_pick_window_cost(size_t n, bool merged, int forced, uint32_t cmax) {
+// `stride` >= 2 (a lean registered set, below): min(stride, nwin) bucket sets.
+inline uint32_t msm_pick_window_cost(size_t n, bool merged, int forced, uint32_t cmax, uint32_t stride = 0) {
   if (forced) return (uint32_t)forced;   // G16_MSM_WINDOW / G16_TABLE_WINDOW
   uint32_t best = 5;
   double best_cost = 1e300;
@@ -26,7 +27,7 @@ inline uint32_t msm_pick_window_cost(size_t n, bool merged, int forced, uint32_t
     if (((size_t)nwin * n) >> 31) continue;   // table index / entry count must fit 31 bits
     const uint32_t t = FR_BITS - (nwin - 1) * c, tmin = c - 2 < 6 ? c - 2 : 6;
     if (t < tmin && c > 5) continue;
-    const double sets = merged ? 1.0 : (double)nwin;
+    const double sets = merged ? 1.0 : (double)(stride >= 2 && stride < nwin ? stride : nwin);
     const double cost = 10.0 * (double)n * nwin + 28.0 * sets * (double)(1u << (c - 1));
     if (cost < best_cost) {
       best_cost = cost;
@@ -45,11 +46,50 @@ inline uint32_t msm_pick_table_window(size_t n, const G16Env& env) {
 // multiplier tables of a registered set with window c: the 43 slices of 2^(c-7) buckets of the class bucket set must
 // be whole 256-bucket partitions of the sort
 inline uint32_t msm_pick_mtab(uint32_t c, const G16Env& env) { return env.mtab == 2 && c >= 15 ? 2u : 1u; }
+// Lean registered sets: tables at a stride.  Table j of a set registered at stride s holds 2^(c s j) P_i, and window
+// w = s j + r gathers from table j into bucket set r (msm_window_slot): ceil(nwin / s) tables instead of nwin, s bucket
+// sets of 2^(c-1) buckets instead of one.  A stride above nwin is nwin -- the one-shot layout with the points resident.
+// The window comes from the same cost model over s bucket sets, capped like a one-shot MSM's: every bucket set the tail
+// then sees has a shape that the one-shot path runs as well.
+inline uint32_t msm_pick_lean_window(size_t n, uint32_t stride, const G16Env& env) {
+  return msm_pick_window_cost(n ? n : 1, false, env.table_window, 16, stride);
+}
+inline uint32_t msm_clamp_stride(uint32_t stride, uint32_t c) {
+  const uint32_t nwin = FR_BITS / c + 1;
+  return stride > nwin ? nwin : stride;
+}
+// what registration decides for n points at a table stride (0 / 1: a table per window), before any fallback for lack of
+// HBM: window bits, multiplier tables, the stride as it is used, and the tables that hold the set
+struct MsmTableChoice {
+  uint32_t c, mtab, stride, ntables;
+  bool fits;   // table indices and entry counts stay below 2^31
+};
+inline MsmTableChoice msm_table_choice(size_t n, uint32_t stride, const G16Env& env) {
+  MsmTableChoice t;
+  if (stride >= 2) {
+    t.c = msm_pick_lean_window(n, stride, env);
+    t.mtab = 1;
+    t.stride = msm_clamp_stride(stride, t.c);
+  } else {
+    t.c = msm_pick_table_window(n, env);
+    t.mtab = msm_pick_mtab(t.c, env);
+    t.stride = 1;
+  }
+  const uint32_t nwin = FR_BITS / t.c + 1;
+  if ((size_t)t.mtab * nwin * n >= (size_t(1) << 31)) t.mtab = 1;
+  t.ntables = t.mtab * ((nwin + t.stride - 1) / t.stride);
+  t.fits = (size_t)nwin * n < (size_t(1) << 31);   // the entries; the table index ntables * n is no larger
+  return t;
+}
+// table_cfg of a registered set (g16_points::cfg): window bits | multiplier tables << 8 | table stride << 16 (0 = 1)
+inline uint32_t msm_table_cfg(uint32_t c, uint32_t mtab, uint32_t stride) {
+  return c | (mtab << 8) | (stride >= 2 ? stride << 16 : 0u);
+}
 
 constexpr uint32_t MSM_FLAG_SCALARS_MONT = 1u;   // = G16_SCALARS_MONT of the C ABI (asserted in msm_sort.hip)
 
-// table_cfg: 0 for a plain point array, else the window bits of a registered set | its multiplier tables << 8
-// (g16_points::cfg)
+// table_cfg: 0 for a plain point array, else the window bits of a registered set | its multiplier tables << 8 | its
+// table stride << 16 (g16_points::cfg, msm_table_cfg; a stride of 0 there is 1)
 inline MsmParams msm_params(size_t n, uint32_t flags, uint32_t table_cfg, const G16Env& env) {
   MsmParams P;
   const uint32_t table_c = table_cfg & 0xffu;
@@ -57,8 +97,10 @@ inline MsmParams msm_params(size_t n, uint32_t flags, uint32_t table_cfg, const 
   P.c = table_c ? table_c : msm_pick_window(n, env);
   P.nwin = FR_BITS / P.c + 1;
   P.tables = table_c ? 1u : 0u;
-  P.mtab = table_c && (table_cfg >> 8) == 2 ? 2u : 1u;
-  P.nbuckets = P.tables ? msm_table_buckets(P.c, P.mtab) : (P.nwin << (P.c - 1));
+  const uint32_t stride = table_c ? msm_clamp_stride(table_cfg >> 16, P.c) : 0u;
+  P.tstride = table_c ? (stride >= 2 ? stride : 1u) : 0u;
+  P.mtab = table_c && P.tstride == 1 && ((table_cfg >> 8) & 0xffu) == 2 ? 2u : 1u;
+  P.nbuckets = P.tstride >= 2 ? (P.tstride << (P.c - 1)) : P.tables ? msm_table_buckets(P.c, P.mtab) : (P.nwin << (P.c - 1));
   // segment length L: one accumulate task handles <= L entries.  A task is a serial chain of L mixed adds
   // (~23 us each with 4 waves per SIMD), so L also bounds the tail of the launch; ~1.25 x the mean bucket size
   // keeps most buckets in one segment, the rest get 1-2 short extra segments that msm_reduce1 absorbs.
@@ -196,9 +238,14 @@ inline MsmTailPlan msm_tail_plan(const MsmParams& P, bool is_g1, bool narrow_tai
   // whose length grows with the chunks per thread, so the slices are as small as the 64 lanes of msm_fold_merged
   // allow: 512 chunks (2^13 buckets) per slice at c = 20 -> 64 workgroups, one chunk per thread (G1) / two (G2).
   // G16_RED_SLICE = log2(chunks per slice) overrides it (experiments).
+  // A lean set (MsmParams::tstride >= 2) is reduced like a plain MSM of tstride windows: its bucket sets are the
+  // residues r of the windows modulo the stride, and the fold applies 2^(c r) by Horner.
+  const bool lean = P.tables && P.tstride >= 2;
   T.nsets = P.nwin;
   T.log2ks = 0;
-  if (P.tables && P.mtab == 2) {   // class bucket set: 43 slices of 2^(c-7) buckets (msm_class_bucket)
+  if (lean) {
+    T.nsets = P.tstride;
+  } else if (P.tables && P.mtab == 2) {   // class bucket set: 43 slices of 2^(c-7) buckets (msm_class_bucket)
     T.nsets = MSM_CLASS_SLICES;
     T.log2ks = P.c - 7;
   } else if (P.tables) {
@@ -234,7 +281,9 @@ inline MsmTailPlan msm_tail_plan(const MsmParams& P, bool is_g1, bool narrow_tai
     T.r2_threads = T.r2 == MsmR2::WIDE ? wide : T.r2 == MsmR2::WAVE ? 64u : wide / 4;
     T.r2_lds = T.r2_threads;
   }
-  if (P.tables && P.mtab == 2)
+  if (lean)
+    T.fold = MsmFold::PLAIN;   // msm_fold over nsets = tstride sums, c doublings between them
+  else if (P.tables && P.mtab == 2)
     T.fold = quad ? MsmFold::CLASSES_QUAD : MsmFold::CLASSES;
   else
     T.fold = P.tables ? MsmFold::MERGED : MsmFold::PLAIN;

@@ -26,21 +26,35 @@ int32_t g16_msm_sort(g16_ctx* ctx, hipStream_t st, const void* d_scalars, uint32
   if (!L.use_part) HIPCHK(ctx, hipMemsetAsync(S.count, 0, (char*)S.offset - (char*)S.count, st));  // count + cursor are adjacent
   HIPCHK(ctx, hipMemsetAsync(S.info, 0, 64, st));
   HIPCHK(ctx, hipMemsetAsync(S.ghist, 0, PERM_BINS * 4, st));
+  // a lean set (tables at a stride >= 2) runs the instantiations that map a window to its (table, bucket set) pair; every
+  // other MSM the ones without that division
+  const bool lean = P.tstride >= 2;
   if (L.use_part) {
-    KLAUNCH_ON(ctx, st, "msm_part_count", part_pass<false>, L.ptiles, PART_BLOCK, 0, scalars, d_live, P, L.lo_bits, L.nparts,
-               L.ptiles, S.tile_hist, S.tmp);
+    if (lean)
+      KLAUNCH_ON(ctx, st, "msm_part_count", (part_pass<false, true>), L.ptiles, PART_BLOCK, 0, scalars, d_live, P, L.lo_bits,
+                 L.nparts, L.ptiles, S.tile_hist, S.tmp);
+    else
+      KLAUNCH_ON(ctx, st, "msm_part_count", (part_pass<false, false>), L.ptiles, PART_BLOCK, 0, scalars, d_live, P, L.lo_bits,
+                 L.nparts, L.ptiles, S.tile_hist, S.tmp);
     KLAUNCH_ON(ctx, st, "msm_scan", scan1_tile_sums, L.nt2, SCAN_BLOCK, 0, S.tile_hist, (uint32_t)L.nth, S.tiles2);
     KLAUNCH_ON(ctx, st, "msm_scan", scan_tiles, 1, SCAN_BLOCK, 0, S.tiles2, L.nt2, S.info + 8);  // total -> info[8]
     KLAUNCH_ON(ctx, st, "msm_scan", scan1_apply, L.nt2, SCAN_BLOCK, 0, S.tile_hist, (uint32_t)L.nth, S.tiles2);
-    KLAUNCH_ON(ctx, st, "msm_part_scatter", part_pass<true>, L.ptiles, PART_BLOCK, 0, scalars, d_live, P, L.lo_bits, L.nparts,
-               L.ptiles, S.tile_hist, S.tmp);
+    if (lean)
+      KLAUNCH_ON(ctx, st, "msm_part_scatter", (part_pass<true, true>), L.ptiles, PART_BLOCK, 0, scalars, d_live, P, L.lo_bits,
+                 L.nparts, L.ptiles, S.tile_hist, S.tmp);
+    else
+      KLAUNCH_ON(ctx, st, "msm_part_scatter", (part_pass<true, false>), L.ptiles, PART_BLOCK, 0, scalars, d_live, P, L.lo_bits,
+                 L.nparts, L.ptiles, S.tile_hist, S.tmp);
     KLAUNCH_ON(ctx, st, "msm_bucket_sort", bucket_hist, L.nparts * BS_SPLIT, BS_LOW, 0, S.tmp, S.tile_hist, L.ptiles,
                L.nparts, S.info + 8, S.slice_hist);
     KLAUNCH_ON(ctx, st, "msm_bucket_sort", bucket_place, L.nparts * BS_SPLIT, BS_LOW, 0, S.tmp, S.tile_hist, L.ptiles,
                L.nparts, S.info + 8, S.slice_hist, P, L.lo_bits, S.count, S.offset, S.entries, L.fused ? 1u : 0u, S.xoff,
                S.heavy, S.info, S.ghist, S.blk_base);
   } else {
-    KLAUNCH_ON(ctx, st, "msm_count", msm_count, L.nblk, MSM_BLOCK, 0, scalars, d_live, P, S.count);
+    if (lean)
+      KLAUNCH_ON(ctx, st, "msm_count", msm_count<true>, L.nblk, MSM_BLOCK, 0, scalars, d_live, P, S.count);
+    else
+      KLAUNCH_ON(ctx, st, "msm_count", msm_count<false>, L.nblk, MSM_BLOCK, 0, scalars, d_live, P, S.count);
   }
   if (!L.fused) {
     KLAUNCH_ON(ctx, st, "msm_scan", scan_tile_sums, L.ntiles, SCAN_BLOCK, 0, S.count, P.nbuckets, P.seg, S.tiles);
@@ -51,8 +65,14 @@ int32_t g16_msm_sort(g16_ctx* ctx, hipStream_t st, const void* d_scalars, uint32
   }
   KLAUNCH_ON(ctx, st, "msm_perm", perm_scatter, L.pblk, PERM_BLOCK, 0, S.count, P.nbuckets, S.ghist, S.blk_base,
              S.perm);
-  if (!L.use_part)
-    KLAUNCH_ON(ctx, st, "msm_scatter", msm_scatter, L.nblk, MSM_BLOCK, 0, scalars, d_live, P, S.offset, S.cursor, S.entries);
+  if (!L.use_part) {
+    if (lean)
+      KLAUNCH_ON(ctx, st, "msm_scatter", msm_scatter<true>, L.nblk, MSM_BLOCK, 0, scalars, d_live, P, S.offset, S.cursor,
+                 S.entries);
+    else
+      KLAUNCH_ON(ctx, st, "msm_scatter", msm_scatter<false>, L.nblk, MSM_BLOCK, 0, scalars, d_live, P, S.offset, S.cursor,
+                 S.entries);
+  }
   KLAUNCH_ON(ctx, st, "msm_make_extra", msm_make_extra, 512, MSM_BLOCK, 0, S.heavy, S.info, S.offset, S.xoff, P.seg,
              P.max_extra, S.xseg);
   HIPCHK(ctx, hipGetLastError());
@@ -82,7 +102,7 @@ static int32_t msm_batch(g16_ctx* ctx, hipStream_t st, const g16_msm_run* runs, 
     const g16_ctx::MsmSort& S = *runs[j].sort;
     const MsmParams& Q = S.P;
     if (Q.n != P.n || Q.c != P.c || Q.nwin != P.nwin || Q.nbuckets != P.nbuckets || Q.seg != P.seg ||
-        Q.tables != P.tables || Q.mtab != P.mtab || Q.max_extra != P.max_extra) {
+        Q.tables != P.tables || Q.mtab != P.mtab || Q.tstride != P.tstride || Q.max_extra != P.max_extra) {
       ctx->err = "MSM batch: the jobs do not share their launch parameters";
       return G16_EINVAL;
     }

@@ -105,12 +105,13 @@ int32_t sum_partials_device(g16_ctx* ctx, const void* d_parts, uint32_t count, v
   return G16_OK;
 }
 
+// stride: tables for every stride-th window (1: every window; >= 2: a lean set, mtab == 1)
 template <class C>
-int32_t precompute_device(g16_ctx* ctx, const void* d_points, size_t n, uint32_t c, uint32_t mtab,
-                                 void* d_tables) {
-  const uint32_t nwin = FR_BITS / c + 1;
+int32_t precompute_device(g16_ctx* ctx, const void* d_points, size_t n, uint32_t c, uint32_t mtab, uint32_t stride,
+                          void* d_tables) {
+  const uint32_t nwin = FR_BITS / c + 1, ntab = (nwin + stride - 1) / stride;
   KLAUNCH(ctx, "msm_precompute", msm_precompute<C>, (uint32_t)((n + MSM_BLOCK - 1) / MSM_BLOCK), MSM_BLOCK, 0,
-          (const typename C::Aff*)d_points, (uint32_t)n, c, nwin, mtab, (typename Ec29<C>::Tab*)d_tables);
+          (const typename C::Aff*)d_points, (uint32_t)n, c * stride, ntab, mtab, (typename Ec29<C>::Tab*)d_tables);
   HIPCHK(ctx, hipGetLastError());
   return G16_OK;
 }

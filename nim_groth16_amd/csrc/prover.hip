@@ -90,7 +90,9 @@ static inline uint32_t rd32(const unsigned char* p) {
   return v;
 }
 
-static int32_t pkey_create(g16_ctx* ctx, const g16_pkey_desc* d, const CoeffSource& cs, g16_pkey** out) {
+// table_stride: the stride of all five point sets (g16_points_register_*_lean; 0 / 1: a table per window)
+static int32_t pkey_create(g16_ctx* ctx, const g16_pkey_desc* d, const CoeffSource& cs, uint32_t table_stride,
+                           g16_pkey** out) {
   const size_t n = size_t(1) << d->log2_domain;
   // shape rules of generateProofWithMask (prover.nim:236, 270-276)
   if (d->log2_domain > 27 || d->nvars == 0 || d->npubs + 1 > d->nvars || d->flavour > 1 || !d->pointsA1 ||
@@ -132,11 +134,12 @@ static int32_t pkey_create(g16_ctx* ctx, const g16_pkey_desc* d, const CoeffSour
   std::vector<unsigned char> c1pad((k->w_hi - k->w_lo) * 64, 0);
   for (size_t wI = k->w_lo; wI < k->w_hi; ++wI)
     if (wI > d->npubs) memcpy(&c1pad[(wI - k->w_lo) * 64], (const char*)d->pointsC1 + 64 * (wI - d->npubs - 1), 64);
-  if ((rc = g16_points_register_g1(ctx, (const char*)d->pointsA1 + 64 * k->w_lo, k->w_hi - k->w_lo, &k->A1))) return rc;
-  if ((rc = g16_points_register_g1(ctx, (const char*)d->pointsB1 + 64 * k->w_lo, k->w_hi - k->w_lo, &k->B1))) return rc;
-  if ((rc = g16_points_register_g2(ctx, (const char*)d->pointsB2 + 128 * k->w_lo, k->w_hi - k->w_lo, &k->B2))) return rc;
-  if ((rc = g16_points_register_g1(ctx, c1pad.data(), k->w_hi - k->w_lo, &k->C1))) return rc;
-  if ((rc = g16_points_register_g1(ctx, (const char*)d->pointsH1 + 64 * k->h_lo, k->h_hi - k->h_lo, &k->H1))) return rc;
+  const uint32_t ts = table_stride;
+  if ((rc = g16_points_register_g1_lean(ctx, (const char*)d->pointsA1 + 64 * k->w_lo, k->w_hi - k->w_lo, ts, &k->A1))) return rc;
+  if ((rc = g16_points_register_g1_lean(ctx, (const char*)d->pointsB1 + 64 * k->w_lo, k->w_hi - k->w_lo, ts, &k->B1))) return rc;
+  if ((rc = g16_points_register_g2_lean(ctx, (const char*)d->pointsB2 + 128 * k->w_lo, k->w_hi - k->w_lo, ts, &k->B2))) return rc;
+  if ((rc = g16_points_register_g1_lean(ctx, c1pad.data(), k->w_hi - k->w_lo, ts, &k->C1))) return rc;
+  if ((rc = g16_points_register_g1_lean(ctx, (const char*)d->pointsH1 + 64 * k->h_lo, k->h_hi - k->h_lo, ts, &k->H1))) return rc;
   {   // sparse sets get their own entry lists (see g16_pkey)
     const size_t nw = k->w_hi - k->w_lo;
     k->liveA = g16_points_live_if_sparse(k->A1);
@@ -179,7 +182,7 @@ static int32_t pkey_create(g16_ctx* ctx, const g16_pkey_desc* d, const CoeffSour
   return G16_OK;
 }
 
-extern "C" int32_t g16_pkey_create(g16_ctx* ctx, const g16_pkey_desc* d, g16_pkey** out) {
+extern "C" int32_t g16_pkey_create_lean(g16_ctx* ctx, const g16_pkey_desc* d, uint32_t table_stride, g16_pkey** out) {
   if (!ctx) return G16_EINVAL;
   if (!d || !out || (d->ncoeffs && !d->coeffs)) {
     ctx->err = "null argument";
@@ -189,14 +192,17 @@ extern "C" int32_t g16_pkey_create(g16_ctx* ctx, const g16_pkey_desc* d, g16_pke
   static_assert(sizeof(g16_coeff) == 48 && offsetof(g16_coeff, value) == 16, "g16_coeff layout");
   CoeffSource cs;
   cs.base = (const unsigned char*)d->coeffs, cs.count = d->ncoeffs, cs.stride = sizeof(g16_coeff), cs.value_off = 16;
-  return pkey_create(ctx, d, cs, out);
+  return pkey_create(ctx, d, cs, table_stride, out);
+}
+extern "C" int32_t g16_pkey_create(g16_ctx* ctx, const g16_pkey_desc* d, g16_pkey** out) {
+  return g16_pkey_create_lean(ctx, d, 0, out);
 }
 
 // the key's coefficients straight from the .zkey file: section 4 as it lies on disk -- u32 count, then count entries of
 // { u32 matrix, u32 row, u32 col, 32-byte value in DOUBLE Montgomery form } (files/zkey.nim:169-192; io.nim:134-139
 // unmarshalFrWTF).  No host arithmetic: the values go to the device as they are.
-extern "C" int32_t g16_pkey_create_zkey(g16_ctx* ctx, const g16_pkey_desc* d, const void* section4, size_t section4_bytes,
-                                        g16_pkey** out) {
+extern "C" int32_t g16_pkey_create_zkey_lean(g16_ctx* ctx, const g16_pkey_desc* d, const void* section4,
+                                             size_t section4_bytes, uint32_t table_stride, g16_pkey** out) {
   if (!ctx) return G16_EINVAL;
   if (!d || !out || !section4 || section4_bytes < 4 || d->coeffs || d->ncoeffs) {
     ctx->err = "bad argument (section 4 of the .zkey in, desc.coeffs = NULL, desc.ncoeffs = 0)";
@@ -211,7 +217,11 @@ extern "C" int32_t g16_pkey_create_zkey(g16_ctx* ctx, const g16_pkey_desc* d, co
   }
   CoeffSource cs;
   cs.base = p + 4, cs.count = count, cs.stride = 44, cs.value_off = 12, cs.values_r2 = true;
-  return pkey_create(ctx, d, cs, out);
+  return pkey_create(ctx, d, cs, table_stride, out);
+}
+extern "C" int32_t g16_pkey_create_zkey(g16_ctx* ctx, const g16_pkey_desc* d, const void* section4, size_t section4_bytes,
+                                        g16_pkey** out) {
+  return g16_pkey_create_zkey_lean(ctx, d, section4, section4_bytes, 0, out);
 }
 
 // Az | Bz | Cz for a witness (device buffers); exposed for tests of the buildABC kernel

@@ -4,7 +4,10 @@
 // (g16_ctx_create, g16_pkey_create, g16_prove, g16_pkey_destroy, g16_ctx_destroy).
 //
 //   g++ -O2 -std=c++17 -Iinclude tools/ab_prove.cpp -ldl -lpthread -o ab_prove
-//   ./ab_prove -l path/to/libg16hip.so -z circuit.zkey -w witness.wtns [-k steps] [-f inflight] [-K] [-r reps]
+//   ./ab_prove -l path/to/libg16hip.so -z circuit.zkey -w witness.wtns [-k steps] [-f inflight] [-K] [-r reps] [-s S]
+//
+// -s S: the key as a lean key at table stride S (g16_pkey_create_lean; builds without it are refused), its table bytes
+// printed beside the batches.
 //
 // Protocol = bench.py's replica mode: `inflight` host threads, one context each, prove `steps` proofs in total from
 // the (host, .wtns-layout) witness; wall time over the whole batch; `reps` batches, each printed.  -K: one key per
@@ -107,7 +110,7 @@ int main(int argc, char** argv) {
   int steps = 96, inflight = 3, reps = 3;
   if (const char* v = getenv("AB_INFLIGHT")) inflight = atoi(v);   // (tools/ab_rounds.sh: per-entry "@AB_INFLIGHT=4")
   bool key_per_ctx = false;
-  int pool_depth = 0;
+  int pool_depth = 0, table_stride = 0;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() -> const char* {
@@ -122,11 +125,13 @@ int main(int argc, char** argv) {
     else if (a == "-r") reps = atoi(next());
     else if (a == "-K") key_per_ctx = true;
     else if (a == "-P") pool_depth = atoi(next());
+    else if (a == "-s") table_stride = atoi(next());
     else die("unknown option " + a);
   }
-  if (!lpath || !zpath || !wpath || steps < 1 || inflight < 1 || inflight > 16 || pool_depth < 0 || pool_depth > 8)
+  if (!lpath || !zpath || !wpath || steps < 1 || inflight < 1 || inflight > 16 || pool_depth < 0 || pool_depth > 8 ||
+      table_stride < 0 || table_stride > 255 || (table_stride && pool_depth))
     die("usage: ab_prove -l libg16hip.so -z circuit.zkey -w witness.wtns [-k steps] [-f inflight | -P depth] [-K] "
-        "[-r reps]");
+        "[-r reps] [-s table_stride]");
   void* lib = dlopen(lpath, RTLD_NOW | RTLD_LOCAL);
   if (!lib) die(std::string("dlopen: ") + dlerror());
   auto sym = [&](const char* name) {
@@ -141,16 +146,35 @@ int main(int argc, char** argv) {
   auto pkey_destroy = (void (*)(g16_pkey*))sym("g16_pkey_destroy");
   auto prove = (int32_t(*)(g16_ctx*, const g16_pkey*, const void*, uint32_t, const void*, const void*, g16_proof*))sym("g16_prove");
 
+  // -s: the lean entry points, which only builds with table strides have
+  int32_t (*pkey_create_lean)(g16_ctx*, const g16_pkey_desc*, uint32_t, g16_pkey**) = nullptr;
+  int32_t (*points_plan)(int, size_t, uint32_t, uint32_t*, uint32_t*, size_t*) = nullptr;
+  if (table_stride) {
+    pkey_create_lean = (decltype(pkey_create_lean))sym("g16_pkey_create_lean");
+    points_plan = (decltype(points_plan))sym("g16_points_plan");
+  }
+
   ZkeyFile zf(zpath);
   WtnsFile wf(wpath, zf.nvars);
   const g16_pkey_desc d = zf.desc();
+  if (points_plan) {   // bytes of the five point sets' tables at this stride (A1, B1, C1 padded to nvars; B2; H1)
+    size_t g1w = 0, g2w = 0, g1h = 0;
+    uint32_t c = 0, nt = 0;
+    points_plan(1, zf.nvars, (uint32_t)table_stride, &c, &nt, &g1w);
+    points_plan(2, zf.nvars, (uint32_t)table_stride, nullptr, nullptr, &g2w);
+    points_plan(1, size_t(1) << d.log2_domain, (uint32_t)table_stride, nullptr, nullptr, &g1h);
+    printf("%s table_stride %d window_bits %u tables %u table_bytes %zu\n", lpath, table_stride, c, nt,
+           3 * g1w + g2w + g1h);
+  }
   if (pool_depth) return run_pool(lib, lpath, zf, wf, d, pool_depth, steps, reps);
   std::vector<g16_ctx*> ctx(inflight, nullptr);
   std::vector<g16_pkey*> key(inflight, nullptr);
   for (int j = 0; j < inflight; ++j) {
     if (ctx_create(0, &ctx[j]) != G16_OK) die("no usable GPU");
     if (j == 0 || key_per_ctx) {
-      if (pkey_create(ctx[j], &d, &key[j]) != G16_OK) die(std::string("g16_pkey_create: ") + last_error(ctx[j]));
+      const int32_t rc = pkey_create_lean ? pkey_create_lean(ctx[j], &d, (uint32_t)table_stride, &key[j])
+                                          : pkey_create(ctx[j], &d, &key[j]);
+      if (rc != G16_OK) die(std::string("g16_pkey_create: ") + last_error(ctx[j]));
     } else {
       key[j] = key[0];
     }

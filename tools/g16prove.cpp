@@ -5,6 +5,10 @@
 //   g++ -O2 -std=c++17 -Iinclude tools/g16prove.cpp -Lnim_groth16_amd/csrc -lg16hip
 //       -Wl,-rpath,$PWD/nim_groth16_amd/csrc -o g16prove
 //   ./g16prove -z circuit.zkey -w witness.wtns -o proof.json -i public.json [-n] [-y] [-t] [--gpus 0,1,2,3]
+//             [--table-stride S]
+//
+// --table-stride S: a lean key -- window tables for every S-th window only (g16_pkey_create_zkey_lean: about 1 / S of
+// the HBM, more bucket reduction per proof, the same proof).
 //
 // --gpus d0,d1,...: the proof sharded over those devices through the device group of the C ABI (g16_group_*: one host
 // thread per device inside the library; the reference's Taskpool shape, msm.nim:96-122).  A device may repeat.
@@ -17,6 +21,7 @@ int main(int argc, char** argv) {
   const char *zpath = nullptr, *wpath = nullptr, *opath = "proof.json", *ipath = "public.json";
   bool nomask = false, verify = false, timing = false;
   std::vector<int32_t> gpus;
+  uint32_t table_stride = 0;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() -> const char* {
@@ -39,7 +44,14 @@ int main(int argc, char** argv) {
         q = *end == ',' ? end + 1 : end;
       }
     }
-    else die("unknown option " + a + "\nusage: g16prove -z circuit.zkey -w witness.wtns [-o proof.json] [-i public.json] [-n] [-y] [-t] [--gpus 0,1,...]");
+    else if (a == "--table-stride") {
+      char* end = nullptr;
+      const char* q = next();
+      const long s = strtol(q, &end, 10);
+      if (end == q || *end || s < 0 || s > 255) die("--table-stride takes a number from 0 to 255");
+      table_stride = (uint32_t)s;
+    }
+    else die("unknown option " + a + "\nusage: g16prove -z circuit.zkey -w witness.wtns [-o proof.json] [-i public.json] [-n] [-y] [-t] [--gpus 0,1,...] [--table-stride S]");
   }
   if (!zpath || !wpath) die("usage: g16prove -z circuit.zkey -w witness.wtns [-o proof.json] [-i public.json] [-n] [-y] [-t]");
 
@@ -61,10 +73,10 @@ int main(int argc, char** argv) {
   g16_group* grp = nullptr;
   g16_group_pkey* gkey = nullptr;
   if (gpus.empty()) {
-    chk(g16_pkey_create_zkey(ctx, &d, zf.section4, zf.section4_len, &key), "g16_pkey_create_zkey");
+    chk(g16_pkey_create_zkey_lean(ctx, &d, zf.section4, zf.section4_len, table_stride, &key), "g16_pkey_create_zkey");
   } else {
     if (g16_group_create(gpus.data(), (int32_t)gpus.size(), &grp) != G16_OK) die("g16_group_create failed");
-    if (g16_group_pkey_create(grp, &d, &gkey) != G16_OK)
+    if (g16_group_pkey_create_lean(grp, &d, table_stride, &gkey) != G16_OK)
       die(std::string("g16_group_pkey_create failed: ") + g16_group_last_error(grp));
   }
   const double t2 = now();

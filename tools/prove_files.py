@@ -34,6 +34,8 @@ def main():
     ap.add_argument("-i", "--io", default="public.json")
     ap.add_argument("-n", "--nomask", action="store_true", help="trivial mask r = s = 0 (cli_main.nim -n)")
     ap.add_argument("-t", "--time", action="store_true")
+    ap.add_argument("--table-stride", type=int, default=0,
+                    help="a lean key: window tables for every S-th window only (about 1 / S of the HBM, same proof)")
     ap.add_argument("-k", "--vkey", default=None, help="also write the verification key as snarkjs verification_key.json")
     ap.add_argument("-c", "--check", action="store_true",
                     help="check every key point against its curve equation on the GPU while parsing")
@@ -46,7 +48,7 @@ def main():
     zkey, wtns = parseZKey(args.zkey, check=args.check, ctx=ctx, rawCoeffs=True), parseWitness(args.wtns)
     assert wtns.nvars == zkey.header.nvars, "wrong witness length"        # prover.nim:236
     t1 = time.time()
-    pkey = loadProvingKey(zkey, ctx)
+    pkey = loadProvingKey(zkey, ctx, table_stride=args.table_stride)
     t2 = time.time()
     mask = Mask(0, 0) if args.nomask else Mask(secrets.randbelow(F.primeR), secrets.randbelow(F.primeR))
     proof = generateProofWithMask(0, args.time, zkey, wtns, mask, ctx, pkey=pkey)
