@@ -14,6 +14,7 @@ import groth16/math/domain
 import groth16/zkey_types
 import groth16/files/witness
 import std/tables
+import std/sysrand
 
 {.passL: "-lg16hip".}
 type
@@ -254,3 +255,36 @@ proc verifyProof*(vkey: VKey, prf: Proof): bool =
   assert st != -1, "pi_a is not in G1"; assert st != -2, "pi_b is not in G2"; assert st != -3, "pi_c is not in G1"   # verifier.nim:35-37
   assert st != -5 and st != -6, "non-canonical field element in the proof / public input"
   result = st == 1
+
+proc g16_verify_batch(ctx: ptr G16Ctx, key: ptr G16VKey, proofs: ptr G16Proof, publicIO: pointer, flags: uint32,
+                      count: csize_t, multipliers: pointer, res: ptr int32, status: ptr int32): int32 {.importc, header: "g16hip.h".}
+
+proc verifyProofsBatch*(vkey: VKey, prfs: openArray[Proof]): bool =
+  ## "do they all verify?": ONE pairing product for the batch (count + 3 Miller loops, one final exponentiation).
+  ## False if any proof is malformed, has pi_b outside the order-r subgroup (always checked) or fails; a batch with a
+  ## bad proof passes with probability <= 1/(2^128 - 1) over the multipliers, which are drawn HERE, after the proofs
+  ## are fixed, from the OS CSPRNG (std/sysrand) -- the library draws none.  verifyProof tells which proof failed.
+  if prfs.len == 0: return true
+  var d = G16VKeyDesc(npubs: uint32(vkey.vpoints.pointsIC.len - 1), alpha1: unsafeAddr vkey.spec.alpha1,
+    beta2: unsafeAddr vkey.spec.beta2, gamma2: unsafeAddr vkey.spec.gamma2, delta2: unsafeAddr vkey.spec.delta2,
+    pointsIC: unsafeAddr vkey.vpoints.pointsIC[0])
+  var k: ptr G16VKey
+  check g16_vkey_create(gctx, addr d, addr k)
+  defer: g16_vkey_destroy(k)
+  let nio = vkey.vpoints.pointsIC.len
+  var ps = newSeq[G16Proof](prfs.len)
+  var io = newSeq[Fr](prfs.len * nio)
+  for j, prf in prfs:
+    assert prf.curve == "bn128" and prf.publicIO.len == nio
+    copyMem(addr ps[j].pi_a, unsafeAddr prf.pi_a, 64); copyMem(addr ps[j].pi_b, unsafeAddr prf.pi_b, 128); copyMem(addr ps[j].pi_c, unsafeAddr prf.pi_c, 64)
+    copyMem(addr io[j * nio], unsafeAddr prf.publicIO[0], 32 * nio)
+  var zs = newSeq[array[16, byte]](prfs.len)                 # 128-bit little-endian multipliers, none zero
+  for z in zs.mitems:
+    while true:
+      doAssert urandom(z)
+      var any = false
+      for b in z: any = any or b != 0
+      if any: break
+  var res: int32
+  check g16_verify_batch(gctx, k, addr ps[0], addr io[0], G16_SCALARS_MONT, csize_t(prfs.len), addr zs[0], addr res, nil)
+  result = res == 1

@@ -391,6 +391,26 @@ void g16_vkey_destroy(g16_vkey* key);
 int32_t g16_verify(g16_ctx* ctx, const g16_vkey* key, const g16_proof* proofs, const void* public_io, uint32_t flags,
                    size_t count, int32_t* status);
 int32_t g16_pairing(g16_ctx* ctx, const void* g1_points, const void* g2_points, size_t n, void* out_gt);
+/* One pairing-product check for the whole batch ("do they all verify?"), the random-linear-combination check:
+ *   prod_j e(-z_j A_j, B_j) * e(sum_j z_j C_j, delta2) * e(sum_i s_i IC_i, gamma2) * e((sum_j z_j) alpha1, beta2) == 1,
+ *   s_i = sum_j z_j pub_{j,i} (mod r):  count + 3 Miller loops and ONE final exponentiation per batch.
+ * proofs, public_io, key, count (< 2^22) and G16_SCALARS_MONT / G16_SCALARS_STD: as for g16_verify.
+ * multipliers: count x 16 bytes, little-endian 128-bit integers z_j, host memory, every one non-zero, drawn by the
+ * CALLER from a CSPRNG after the proofs are fixed.  The library draws no randomness itself.
+ * *result = 1: no proof has a structural defect (the negative codes of g16_verify) and the combined equation holds;
+ * 0 otherwise.  count == 0 gives 1.
+ * The order-r check on pi_b is ALWAYS applied (G16_VERIFY_SUBGROUP is implied: the combination is only sound on G2).
+ * Soundness: if at least one proof would not get status 1 from g16_verify with G16_VERIFY_SUBGROUP, then
+ * *result == 1 with probability at most 1/(2^128 - 1), for multipliers uniform over the non-zero 128-bit values and
+ * independent of the proofs: the proofs' defects form a non-zero linear form in the z_j over Fr, and r > 2^128.
+ * Multipliers that the prover can predict (or equal ones) void the bound.
+ * status: NULL, or count entries.  result 1 -> all 1.  result 0 -> exactly what
+ * g16_verify(ctx, key, proofs, public_io, flags | G16_VERIFY_SUBGROUP, count, status) writes (the per-proof kernels
+ * run on the data already uploaded; NULL skips them).
+ * G16_EINVAL: NULL result, NULL multipliers with count > 0, any z_j == 0 (checked on the host before anything is
+ * queued; g16_last_error names the index). */
+int32_t g16_verify_batch(g16_ctx* ctx, const g16_vkey* key, const g16_proof* proofs, const void* public_io,
+                         uint32_t flags, size_t count, const void* multipliers, int32_t* result, int32_t* status);
 
 /* ---- profiling ---------------------------------------------------------------------------------- */
 /* on = 1: every kernel launch is bracketed by HIP events on the stream it is launched on; on = 2: only the

@@ -13,5 +13,6 @@ from .ntt import (Domain, createDomain, forwardNTT, inverseNTT, extendAndForward
 from .prover import (ABC, Proof, Mask, Witness, buildABC, computeQuotientPointwise,  # noqa: F401
                      computeSnarkjsScalarCoeffs, generateProof, generateProofWithMask,
                      generateProofWithTrivialMask, loadGroupKey, loadProvingKey)
-from .verifier import VKey, extractVKey, loadVerifyingKey, verifyProof, verifyProofs  # noqa: F401
+from .verifier import (VKey, extractVKey, loadVerifyingKey, verifyProof, verifyProofs,  # noqa: F401
+                       verifyProofsBatch)
 from .zkey_types import ZKey, GrothHeader, SpecPoints, ProverPoints, JensGroth, Snarkjs  # noqa: F401

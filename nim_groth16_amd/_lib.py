@@ -23,7 +23,7 @@ SYMBOLS = [
     "g16_pkey_create_zkey", "g16_pkey_destroy", "g16_pkey_inf_counts", "g16_prove", "g16_build_abc", "g16_pkey_abc_info", "g16_spmv_fr", "g16_prove_partials", "g16_prove_combine",
     "g16_prove_partials_begin", "g16_prove_partials_end",
     "g16_ntt_fr", "g16_ntt_fr_dev", "g16_profile_enable", "g16_profile_reset", "g16_profile_report", "g16_profile_clock",
-    "g16_vkey_create", "g16_vkey_destroy", "g16_verify", "g16_pairing",
+    "g16_vkey_create", "g16_vkey_destroy", "g16_verify", "g16_verify_batch", "g16_pairing",
     "g16_ctx_cancel", "g16_group_create", "g16_group_destroy", "g16_group_size", "g16_group_last_error",
     "g16_group_pkey_create", "g16_group_pkey_destroy", "g16_group_prove",
     "g16_prover_create", "g16_prover_destroy", "g16_prover_last_error", "g16_prover_submit", "g16_prover_poll",
@@ -170,6 +170,7 @@ def load_library():
     lib.g16_vkey_destroy.argtypes = [vp]
     lib.g16_vkey_destroy.restype = None
     lib.g16_verify.argtypes = [vp, vp, vp, vp, u32, sz, ctypes.POINTER(i32)]
+    lib.g16_verify_batch.argtypes = [vp, vp, vp, vp, u32, sz, vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     lib.g16_pairing.argtypes = [vp, vp, vp, sz, vp]
     lib.g16_ctx_cancel.argtypes = [vp]
     lib.g16_group_create.argtypes = [ctypes.POINTER(i32), i32, ctypes.POINTER(vp)]
@@ -716,6 +717,29 @@ class VerifyingKey:
         self.ctx._check(self.ctx._lib.g16_verify(self.ctx._h, self._h, _buf(raw) if n else None,
                                                  _buf(public_io) if n else None, flags, n, st))
         return list(st)[:n]
+
+    def verify_batch(self, proofs, public_io: bytes, mont: bool = True, multipliers=None, want_status: bool = False):
+        """One pairing-product check for the whole batch (g16_verify_batch): True iff no proof has a structural defect
+        and the combination of all pairing equations under the multipliers holds.  The order-r check of pi_b always
+        runs.  multipliers: one int in [1, 2^128) per proof, unpredictable to whoever made the proofs; None draws
+        them with `secrets`.  want_status: -> (bool, statuses); the statuses of a rejected batch are those of
+        verify(..., subgroup=True), of an accepted one all 1."""
+        n = len(proofs)
+        assert len(public_io) == 32 * n * (self.npubs + 1)
+        raw = b"".join(a + b + c for a, b, c in proofs)
+        assert len(raw) == 256 * n
+        if multipliers is None:
+            import secrets
+            multipliers = [secrets.randbelow((1 << 128) - 1) + 1 for _ in range(n)]
+        assert len(multipliers) == n, "one multiplier per proof"
+        zs = b"".join(int(z).to_bytes(16, "little") for z in multipliers)
+        res = ctypes.c_int32(-1)
+        st = (ctypes.c_int32 * max(n, 1))() if want_status else None
+        flags = SCALARS_MONT if mont else 0
+        self.ctx._check(self.ctx._lib.g16_verify_batch(self.ctx._h, self._h, _buf(raw) if n else None,
+                                                       _buf(public_io) if n else None, flags, n,
+                                                       _buf(zs) if n else None, ctypes.byref(res), st))
+        return (res.value == 1, list(st)[:n]) if want_status else res.value == 1
 
     def _free(self):
         if self._h:

@@ -2,6 +2,7 @@
 
     verifyProof(vkey, prf)   -- verifier.nim:31-52:  e(-A,B) e(alpha,beta) e(C,delta) e(sum pub_i IC_i, gamma) == 1
     extractVKey(zkey)        -- zkey_types.nim:69-73
+    verifyProofsBatch(vkey, prfs) -- "do they all verify?": one pairing product for the batch (g16_verify_batch)
 
 The pairing product runs on the GPU (csrc/pairing.cuh, one lane per pairing, batched over proofs with
 verifyProofs); like the reference, malformed points raise AssertionError ("pi_a is not in G1", ...).
@@ -61,3 +62,17 @@ def verifyProofs(vkey, proofs: Sequence[Proof], ctx: Context = None, subgroup: b
 def verifyProof(vkey, prf: Proof, ctx: Context = None, subgroup: bool = False) -> bool:
     """verifier.nim:31-52"""
     return verifyProofs(vkey, [prf], ctx, subgroup)[0]
+
+
+def verifyProofsBatch(vkey, proofs: Sequence[Proof], ctx: Context = None, multipliers=None) -> bool:
+    """True iff every proof verifies, by ONE random-linear-combination pairing check: count + 3 Miller loops and one
+    final exponentiation instead of 3 count and count.  A batch with a bad proof passes with probability at most
+    1/(2^128 - 1) over the multipliers (ints in [1, 2^128), drawn with `secrets` when None; they must be unpredictable
+    to the provers).  The order-r check of pi_b always runs.  A malformed proof makes the answer False; verifyProofs
+    says which proof and why."""
+    dev = vkey if isinstance(vkey, VerifyingKey) else loadVerifyingKey(vkey, ctx)
+    for prf in proofs:
+        assert prf.curve == "bn128"                                   # verifier.nim:33
+        assert len(prf.publicIO) == 32 * (dev.npubs + 1), "publicIO must hold npubs + 1 values (incl. the leading 1)"
+    return dev.verify_batch([(p.pi_a, p.pi_b, p.pi_c) for p in proofs], b"".join(p.publicIO for p in proofs),
+                            mont=True, multipliers=multipliers)
