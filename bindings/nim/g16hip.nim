@@ -288,3 +288,57 @@ proc verifyProofsBatch*(vkey: VKey, prfs: openArray[Proof]): bool =
   var res: int32
   check g16_verify_batch(gctx, k, addr ps[0], addr io[0], G16_SCALARS_MONT, csize_t(prfs.len), addr zs[0], addr res, nil)
   result = res == 1
+
+# --- drop-in for fakeCircuitSetup (groth16/fake_setup.nim:201-326): one g16_fake_setup call ----------------------------
+# The Lagrange values, the column sums, the combinations and the H scalars are formed on the device and stay in HBM; the
+# points come back into the seqs of the ZKey.  ZKey.coeffs is the reference's own r1csToCoeffs (fake_setup.nim:46-65).
+# Needs `import groth16/files/r1cs` and `import groth16/fake_setup` (ToxicWaste, r1csToCoeffs) beside the imports above.
+type
+  G16SetupDesc {.importc: "g16_setup_desc", header: "g16hip.h".} = object
+    nvars, npubs, nconstraints, flavour: uint32
+    row, col: array[3, ptr uint32]
+    val: array[3, pointer]
+    nnz: array[3, csize_t]
+    flags: uint32
+    alpha, beta, gamma, delta, tau: pointer
+  G16SetupPoints {.importc: "g16_setup_points", header: "g16hip.h".} = object
+    alpha1, beta1, delta1, beta2, gamma2, delta2: pointer
+    pointsIC, pointsA1, pointsB1, pointsB2, pointsC1, pointsH1: pointer
+proc g16_setup_log2_domain(desc: ptr G16SetupDesc, log2Domain: ptr uint32): int32 {.importc, header: "g16hip.h".}
+proc g16_fake_setup(ctx: ptr G16Ctx, desc: ptr G16SetupDesc, res: ptr G16SetupPoints): int32 {.importc, header: "g16hip.h".}
+
+proc fakeCircuitSetup*(r1cs: R1CS, toxic: ToxicWaste, flavour = Snarkjs): ZKey =
+  let nvars = r1cs.cfg.nWires
+  let npubs = r1cs.cfg.nPubOut + r1cs.cfg.nPubIn
+  var rows, cols: array[3, seq[uint32]]
+  var vals: array[3, seq[Fr]]
+  for i, ct in r1cs.constraints:                            # files/r1cs.nim:62-80 -> triplets per matrix
+    for k, lc in [ct.A, ct.B, ct.C]:
+      for term in lc:
+        rows[k].add(uint32(i)); cols[k].add(uint32(term.wireIdx)); vals[k].add(term.value)
+  var d = G16SetupDesc(nvars: uint32(nvars), npubs: uint32(npubs), nconstraints: uint32(r1cs.constraints.len),
+    flavour: uint32(ord(flavour)), flags: G16_SCALARS_MONT,
+    alpha: unsafeAddr toxic.alpha, beta: unsafeAddr toxic.beta, gamma: unsafeAddr toxic.gamma,
+    delta: unsafeAddr toxic.delta, tau: unsafeAddr toxic.tau)
+  for k in 0..2:
+    d.nnz[k] = csize_t(rows[k].len)
+    if rows[k].len > 0:
+      d.row[k] = addr rows[k][0]; d.col[k] = addr cols[k][0]; d.val[k] = addr vals[k][0]
+  var logDom: uint32
+  check g16_setup_log2_domain(addr d, addr logDom)
+  let domSize = 1 shl int(logDom)
+  var spec: SpecPoints
+  var ic = newSeq[G1](npubs + 1)
+  var pts = ProverPoints(pointsA1: newSeq[G1](nvars), pointsB1: newSeq[G1](nvars), pointsB2: newSeq[G2](nvars),
+                         pointsC1: newSeq[G1](max(nvars - npubs - 1, 1)), pointsH1: newSeq[G1](domSize))
+  var o = G16SetupPoints(alpha1: addr spec.alpha1, beta1: addr spec.beta1, delta1: addr spec.delta1,
+    beta2: addr spec.beta2, gamma2: addr spec.gamma2, delta2: addr spec.delta2, pointsIC: addr ic[0],
+    pointsA1: addr pts.pointsA1[0], pointsB1: addr pts.pointsB1[0], pointsB2: addr pts.pointsB2[0],
+    pointsC1: addr pts.pointsC1[0], pointsH1: addr pts.pointsH1[0])
+  check g16_fake_setup(gctx, addr d, addr o)                # tau inside the domain: the reference's assert, poly.nim:245
+  pts.pointsC1.setLen(nvars - npubs - 1)
+  spec.alphaBeta = pairing(spec.alpha1, spec.beta2)         # fake_setup.nim: the verifier-only pairing value
+  let header = GrothHeader(curve: "bn128", flavour: flavour, p: primeP, r: primeR, nvars: nvars, npubs: npubs,
+                           domainSize: domSize, logDomainSize: int(logDom))
+  return ZKey(header: header, specPoints: spec, vPoints: VerifierPoints(pointsIC: ic), pPoints: pts,
+              coeffs: r1csToCoeffs(r1cs))

@@ -161,6 +161,55 @@ int32_t g16_points_check_g2(g16_ctx* ctx, const void* points, size_t n, size_t* 
 int32_t g16_fixed_base_g1(g16_ctx* ctx, const void* scalars, uint32_t scalar_flags, size_t n, void* out_points);
 int32_t g16_fixed_base_g2(g16_ctx* ctx, const void* scalars, uint32_t scalar_flags, size_t n, void* out_points);
 
+/* ---- fake trusted setup: replaces fakeCircuitSetup (groth16/fake_setup.nim:201-326; `-u/--setup -r circuit.r1cs`,
+ *      cli/cli_main.nim:184-193) ----------------------------------------------------------------------------------
+ * One call from an R1CS and explicit toxic waste to every point of a ZKey.  The scalar side -- the Lagrange values at
+ * tau (math/poly.nim:242-250), the sparse column sums (fake_setup.nim:159-187, 254-256), the combinations
+ * beta*A + alpha*B + C over gamma / delta (:273-280) and the H scalars of the flavour (:290-304) -- is formed on the
+ * device and stays in HBM between the stages; the points come from the fixed-base kernel of g16_fixed_base_g1/g2.
+ * Field arithmetic is exact: the points are the bytes the reference computes.
+ * ZKey.coeffs is a rearrangement of the input and stays with the caller (r1csToCoeffs, fake_setup.nim:46-65). */
+typedef struct {
+  uint32_t nvars, npubs, nconstraints; /* R1CS (files/r1cs.nim:62-80): nWires, nPubOut + nPubIn, constraints.len */
+  uint32_t flavour;                    /* G16_FLAVOUR_* (below) */
+  /* the R1CS as it is, as triplets; matrix k = 0, 1, 2 = A, B, C: entry i of matrix k is (constraint row[k][i], wire
+   * col[k][i], value = 32 bytes at val[k] + 32 i); entries of one (constraint, wire) add up.  The library adds snarkjs's
+   * dummy A entries (nconstraints + i, wire i, 1) for i <= npubs itself (fake_setup.nim:59-63, 182-185). */
+  const uint32_t* row[3];
+  const uint32_t* col[3];
+  const void* val[3];
+  size_t nnz[3];
+  uint32_t flags;                                 /* G16_SCALARS_MONT or G16_SCALARS_STD: the values AND the toxic waste */
+  const void *alpha, *beta, *gamma, *delta, *tau; /* ToxicWaste (fake_setup.nim:23-29), 32 bytes each */
+} g16_setup_desc;
+typedef struct {                                   /* host buffers the caller owns; sizes as in g16_pkey_desc */
+  void *alpha1, *beta1, *delta1;                   /* SpecPoints G1 (zkey_types.nim:24-31), 64 B each */
+  void *beta2, *gamma2, *delta2;                   /* SpecPoints G2, 128 B each */
+  void* pointsIC;                                  /* npubs + 1 G1 points           (VKey, zkey_types.nim:62-73) */
+  void *pointsA1, *pointsB1;                       /* nvars G1 points each          (zkey_types.nim:37-38) */
+  void* pointsB2;                                  /* nvars G2 points               (:39) */
+  void* pointsC1;                                  /* nvars - npubs - 1 G1 points   (:40) */
+  void* pointsH1;                                  /* 2^log2_domain G1 points       (:41) */
+} g16_setup_points;
+/* logDomainSize of the key g16_fake_setup builds: ceilingLog2(nconstraints + npubs + 1) (fake_setup.nim:203-206).
+ * A pure function -- no device, no context; only the three counts of desc are read. */
+int32_t g16_setup_log2_domain(const g16_setup_desc* desc, uint32_t* log2_domain);
+/* The whole setup on the context's stream, one wait at the end.  G16_EINVAL, checked on the host before anything is
+ * queued: a null pointer, a matrix entry out of range, a value or toxic scalar that is not canonical (>= r), gamma or
+ * delta zero, nvars <= npubs, a domain (doubled for the snarkjs flavour) above 2^28.  tau inside the domain that is
+ * evaluated -- the reference's assert "point should be outside the domain" (poly.nim:245) -- is found by the kernel and
+ * reported after the run: G16_EINVAL, g16_last_error names the index.  No output is promised after an error. */
+int32_t g16_fake_setup(g16_ctx* ctx, const g16_setup_desc* desc, g16_setup_points* out);
+/* The two scalar building blocks on their own; host pointers, Montgomery in and out; scale NULL = one.
+ * g16_lagrange_fr: out[i] = scale * L_{first + step i}(tau), i < count, on the 2^log2n domain: replaces
+ *   evalLagrangePolyAt (math/poly.nim:242-250) over a range of indices -- first 0, step 1 for fake_setup.nim:254-256,
+ *   first 1, step 2 on the doubled domain for :301-304.  log2n <= 28; first + step (count - 1) < 2^log2n.
+ *   tau = omega^j for a requested j: G16_EINVAL naming j.  tau elsewhere in the domain is legal: every value is zero.
+ * g16_powers_fr: out[i] = scale * base^i, i < count <= 2^29: replaces the running product of fake_setup.nim:290-294. */
+int32_t g16_lagrange_fr(g16_ctx* ctx, uint32_t log2n, uint32_t first, uint32_t step, size_t count, const void* tau,
+                        const void* scale, void* out);
+int32_t g16_powers_fr(g16_ctx* ctx, const void* base, const void* scale, size_t count, void* out);
+
 /* ---- NTT: replaces forwardNTT / inverseNTT (groth16/math/ntt.nim:55-77, 139-161) ------------------- */
 /* natural order in and out; forward unscaled, inverse includes 1/n; omega = gen28^(2^(28-log2n))
  * (math/domain.nim:26-33).  src/dst: n = 2^log2n Fr elements (Montgomery), host memory. 0 <= log2n <= 28 */

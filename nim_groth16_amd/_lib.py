@@ -31,6 +31,7 @@ SYMBOLS = [
     "g16_points_register_g1_lean", "g16_points_register_g2_lean", "g16_points_register_g1_lean_dev",
     "g16_points_register_g2_lean_dev", "g16_points_table_bytes", "g16_points_plan", "g16_pkey_create_lean",
     "g16_pkey_create_zkey_lean", "g16_group_pkey_create_lean",
+    "g16_setup_log2_domain", "g16_fake_setup", "g16_lagrange_fr", "g16_powers_fr",
 ]
 VERIFY_SUBGROUP = 16
 GT_BYTES = 384
@@ -52,6 +53,25 @@ class VkeyDesc(ctypes.Structure):
     """g16_vkey_desc (include/g16hip.h)"""
     _fields_ = [("npubs", ctypes.c_uint32), ("alpha1", ctypes.c_void_p), ("beta2", ctypes.c_void_p),
                 ("gamma2", ctypes.c_void_p), ("delta2", ctypes.c_void_p), ("pointsIC", ctypes.c_void_p)]
+
+
+class SetupDesc(ctypes.Structure):
+    """g16_setup_desc (include/g16hip.h)"""
+    _fields_ = [("nvars", ctypes.c_uint32), ("npubs", ctypes.c_uint32), ("nconstraints", ctypes.c_uint32),
+                ("flavour", ctypes.c_uint32),
+                ("row", ctypes.c_void_p * 3), ("col", ctypes.c_void_p * 3), ("val", ctypes.c_void_p * 3),
+                ("nnz", ctypes.c_size_t * 3), ("flags", ctypes.c_uint32),
+                ("alpha", ctypes.c_void_p), ("beta", ctypes.c_void_p), ("gamma", ctypes.c_void_p),
+                ("delta", ctypes.c_void_p), ("tau", ctypes.c_void_p)]
+
+
+SETUP_POINTS = ("alpha1", "beta1", "delta1", "beta2", "gamma2", "delta2", "pointsIC", "pointsA1", "pointsB1", "pointsB2",
+                "pointsC1", "pointsH1")
+
+
+class SetupPoints(ctypes.Structure):
+    """g16_setup_points (include/g16hip.h)"""
+    _fields_ = [(name, ctypes.c_void_p) for name in SETUP_POINTS]
 
 
 class G16Error(RuntimeError):
@@ -198,6 +218,10 @@ def load_library():
     lib.g16_profile_reset.argtypes = [vp]
     lib.g16_profile_report.argtypes = [vp, ctypes.c_char_p, sz]
     lib.g16_profile_clock.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
+    lib.g16_setup_log2_domain.argtypes = [ctypes.POINTER(SetupDesc), ctypes.POINTER(u32)]
+    lib.g16_fake_setup.argtypes = [vp, ctypes.POINTER(SetupDesc), ctypes.POINTER(SetupPoints)]
+    lib.g16_lagrange_fr.argtypes = [vp, u32, u32, u32, sz, vp, vp, vp]
+    lib.g16_powers_fr.argtypes = [vp, vp, vp, sz, vp]
     for name in SYMBOLS:
         if name not in ("g16_ctx_destroy", "g16_last_error", "g16_points_release", "g16_points_count",
                         "g16_points_inf_count",
@@ -338,6 +362,62 @@ class Context:
                                           _buf(val) if nnz else None, nnz, _buf(x) if len(x) else None, len(x) // 32,
                                           nrows, out))
         return out.raw[: 32 * nrows]
+
+    def lagrange(self, log2n: int, tau: bytes, first: int = 0, step: int = 1, count: int = None,
+                 scale: bytes = None) -> bytes:
+        """scale * L_{first + step i}(tau) for i < count on the 2^log2n domain (math/poly.nim:242-250), Montgomery Fr
+        bytes in and out; count None = every index from `first` at `step` that the domain holds"""
+        if count is None:
+            count = ((1 << log2n) - first + step - 1) // step if step else 1
+        out = ctypes.create_string_buffer(max(1, 32 * count))
+        self._check(self._lib.g16_lagrange_fr(self._h, log2n, first, step, count, _buf(tau),
+                                              _buf(scale) if scale is not None else None, out))
+        return out.raw[: 32 * count]
+
+    def powers(self, base: bytes, count: int, scale: bytes = None) -> bytes:
+        """scale * base^i for i < count (fake_setup.nim:290-294), Montgomery Fr bytes in and out"""
+        out = ctypes.create_string_buffer(max(1, 32 * count))
+        self._check(self._lib.g16_powers_fr(self._h, _buf(base), _buf(scale) if scale is not None else None, count, out))
+        return out.raw[: 32 * count]
+
+    def fake_setup(self, nvars: int, npubs: int, nconstraints: int, flavour: int, matrices, toxic, mont: bool = True):
+        """g16_fake_setup: matrices = three (constraint, wire, values) triplet sets for A, B, C -- uint32 numpy arrays
+        and nnz x 32 value bytes (numpy uint8 array or bytes); toxic = (alpha, beta, gamma, delta, tau) as 32-byte
+        strings in the form `mont` names.  -> (log2 of the domain, {name: bytes} for every member of g16_setup_points)"""
+        import numpy as np
+        d = SetupDesc()
+        d.nvars, d.npubs, d.nconstraints, d.flavour = nvars, npubs, nconstraints, flavour
+        d.flags = SCALARS_MONT if mont else SCALARS_STD
+        keep = []
+        for k, (rows, wires, vals) in enumerate(matrices):
+            rows = np.ascontiguousarray(rows, dtype=np.uint32)
+            wires = np.ascontiguousarray(wires, dtype=np.uint32)
+            if not isinstance(vals, (bytes, bytearray)):
+                vals = np.ascontiguousarray(vals, dtype=np.uint8)
+            nnz = len(rows)
+            assert len(wires) == nnz and (len(vals) if isinstance(vals, (bytes, bytearray)) else vals.size) == 32 * nnz
+            keep += [rows, wires, vals]
+            d.nnz[k] = nnz
+            if nnz:
+                d.row[k], d.col[k], d.val[k] = (_buf(x).value for x in (rows, wires, vals))
+        toxic = [bytes(t) for t in toxic]
+        d.alpha, d.beta, d.gamma, d.delta, d.tau = (_buf(t).value for t in toxic)
+        log2 = ctypes.c_uint32()
+        rc = self._lib.g16_setup_log2_domain(ctypes.byref(d), ctypes.byref(log2))
+        if rc != G16_OK:
+            raise G16Error(rc, "g16_setup_log2_domain failed")
+        sizes = dict(alpha1=64, beta1=64, delta1=64, beta2=128, gamma2=128, delta2=128, pointsIC=64 * (npubs + 1),
+                     pointsA1=64 * nvars, pointsB1=64 * nvars, pointsB2=128 * nvars,
+                     pointsC1=64 * max(0, nvars - npubs - 1), pointsH1=64 << min(log2.value, 40))
+        if log2.value + (1 if flavour == 1 else 0) > 28:     # the call rejects the domain before it writes anything
+            sizes = dict.fromkeys(sizes, 0)
+        o = SetupPoints()
+        bufs = {}
+        for name, nbytes in sizes.items():
+            bufs[name] = ctypes.create_string_buffer(max(1, nbytes))
+            setattr(o, name, ctypes.cast(bufs[name], ctypes.c_void_p).value)
+        self._check(self._lib.g16_fake_setup(self._h, ctypes.byref(d), ctypes.byref(o)))
+        return log2.value, {name: bufs[name].raw[: sizes[name]] for name in SETUP_POINTS}
 
     def quotient(self, Az, Bz, Cz, log2n: int, flavour: int, out=None, device: bool = False):
         if device:

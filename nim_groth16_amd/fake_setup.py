@@ -1,15 +1,18 @@
 """Host mirror of groth16/fake_setup.nim: a "fake" circuit-specific trusted setup from explicit toxic
-waste.  The O(n) scalar bookkeeping (Lagrange values at tau, the combinations of fake_setup.nim:263-277) is host
-code as in the reference; every `y ** gen1` / `y ** gen2` (fake_setup.nim:258-261, 273-277, 290-302) -- the
-expensive part: ~4N+n G1 and N G2 scalar multiplications -- runs on the GPU (g16_fixed_base_g1/g2), and so do the
-sparse column dot products (fake_setup.nim:159-187, 254-256: ~10^7 multiplications for a Poseidon-shaped circuit of
-2^20 constraints) through the transposed matrices (g16_spmv_fr)."""
+waste.  Two paths to the same key bytes (fakeCircuitSetup, `scalarSide`):
+  "device"  (the default with a _lib.Context) one g16_fake_setup call (include/g16hip.h): Lagrange values at tau, column sums, the combinations of
+            fake_setup.nim:263-277, the H scalars and every `y ** gen` on the GPU, nothing returning in between;
+  "host"    the O(n) scalar bookkeeping in Python integers as in the reference; every `y ** gen1` / `y ** gen2`
+            (fake_setup.nim:258-261, 273-277, 290-302: ~4N+n G1 and N G2 scalar multiplications) on the GPU
+            (g16_fixed_base_g1/g2), and so the sparse column dot products (fake_setup.nim:159-187, 254-256: ~10^7
+            multiplications for a Poseidon-shaped circuit of 2^20 constraints) through the transposed matrices
+            (g16_spmv_fr)."""
 from __future__ import annotations
 
 from dataclasses import dataclass
 
 from . import bn128 as F
-from ._lib import default_context
+from ._lib import G16Error, default_context
 from .zkey_types import (GrothHeader, JensGroth, MatrixA, MatrixB, ProverPoints, Snarkjs, SpecPoints, ZKey)
 
 R = F.primeR
@@ -143,9 +146,43 @@ def _lagrangeTaus(logDom: int, tau: int):
     return [omegas[k] * c % R * dinv[k] % R for k in range(dom)]
 
 
-def fakeCircuitSetup(r1cs: R1CS, toxic: ToxicWaste, flavour=Snarkjs, ctx=None) -> ZKey:
-    """fake_setup.nim:201-326"""
+def _deviceSetup(r1cs, toxic: ToxicWaste, flavour, ctx) -> ZKey:
+    """fakeCircuitSetup with the scalar side on the device: one g16_fake_setup call (include/g16hip.h)"""
+    import numpy as np
+    values, A, B, C = _triplets(r1cs)
+    neqs = r1cs.nConstraints if hasattr(r1cs, "nConstraints") else len(r1cs.constraints)
+    npub = r1cs.nPubIn + r1cs.nPubOut
+    table = np.frombuffer(F.frSeqToMontBytes(list(values) + [0]), dtype=np.uint8).reshape(-1, 32)
+    mats = [(rows, wires, table[np.asarray(vi, dtype=np.int64)]) for (rows, wires, vi) in (A, B, C)]
+    tox = [F.frToMontBytes(x % R) for x in (toxic.alpha, toxic.beta, toxic.gamma, toxic.delta, toxic.tau)]
+    try:
+        logDom, pts = ctx.fake_setup(r1cs.nWires, npub, neqs, flavour, mats, tox, mont=True)
+    except G16Error as e:
+        if "tau lies in the domain" in str(e):
+            raise AssertionError("point should be outside the domain") from e     # math/poly.nim:245
+        raise
+    zkey = ZKey()
+    zkey.header = GrothHeader("bn128", flavour, r1cs.nWires, npub, 1 << logDom, logDom)
+    zkey.specPoints = SpecPoints(**{k: pts[k] for k in ("alpha1", "beta1", "delta1", "beta2", "gamma2", "delta2")})
+    zkey.pointsIC = pts["pointsIC"]
+    zkey.pPoints = ProverPoints(**{k: pts[k] for k in ("pointsA1", "pointsB1", "pointsB2", "pointsC1", "pointsH1")})
+    zkey.coeffs = r1csToCoeffArray(r1cs) if hasattr(r1cs, "values") else r1csToCoeffs(r1cs)
+    return zkey
+
+
+def fakeCircuitSetup(r1cs: R1CS, toxic: ToxicWaste, flavour=Snarkjs, ctx=None, scalarSide=None) -> ZKey:
+    """fake_setup.nim:201-326.  scalarSide "device": one g16_fake_setup call with every intermediate in HBM; "host": the
+    Lagrange values, the combinations and the H scalars in Python integers, the results crossing to the GPU and back
+    between the stages.  The keys are the same bytes (tests/test_gpu_setup.py; profiles/fake_setup_ab.txt has the
+    times).  None, the default: "device" for a context that offers g16_fake_setup -- every _lib.Context -- and "host"
+    for a stand-in that implements only the two calls the host path makes (spmv, fixed_base)."""
     ctx = ctx or default_context()
+    if scalarSide is None:
+        scalarSide = "device" if hasattr(ctx, "fake_setup") else "host"
+    if scalarSide == "device":
+        return _deviceSetup(r1cs, toxic, flavour, ctx)
+    if scalarSide != "host":
+        raise ValueError(f"scalarSide must be 'host' or 'device', not {scalarSide!r}")
     neqs = r1cs.nConstraints if hasattr(r1cs, "nConstraints") else len(r1cs.constraints)
     npub = r1cs.nPubIn + r1cs.nPubOut
     logDom = F.ceilingLog2(neqs + npub + 1)

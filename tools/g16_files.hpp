@@ -1,5 +1,6 @@
-// .zkey / .wtns readers over read-only memory maps, shared by the native tools (g16prove.cpp, ab_prove.cpp).
-// File formats restated from the reference (groth16/files/container.nim:6-20, zkey.nim:6-91, witness.nim:5-15):
+// .zkey / .wtns / .r1cs readers over read-only memory maps, shared by the native tools (g16prove.cpp, ab_prove.cpp).
+// File formats restated from the reference (groth16/files/container.nim:6-20, zkey.nim:6-91, witness.nim:5-15,
+// r1cs.nim:6-58):
 // the point sections of a .zkey are little-endian Montgomery with R = 2^256 -- byte for byte the layout the
 // library takes -- so they go from the memory map to the GPU unparsed; .wtns values are canonical little-endian
 // and are passed with G16_SCALARS_STD.  The section-4 coefficients (doubly Montgomery-encoded, bn128/io.nim:134-139) go
@@ -81,6 +82,37 @@ U256 mont_reduce(const U256& x, const U256& m, uint64_t ninv) {
   if (t[8] || geq(r, m)) r = sub(r, m);
   return r;
 }
+// a * b * 2^-256 mod m (CIOS Montgomery product; a, b < m)
+[[maybe_unused]] U256 mont_mul(const U256& a, const U256& b, const U256& m, uint64_t ninv) {
+  uint64_t t[6] = {0, 0, 0, 0, 0, 0};
+  for (int i = 0; i < 4; ++i) {
+    u128 c = 0;
+    for (int j = 0; j < 4; ++j) {
+      c += (u128)a.v[j] * b.v[i] + t[j];
+      t[j] = (uint64_t)c;
+      c >>= 64;
+    }
+    c += t[4];
+    t[4] = (uint64_t)c;
+    t[5] = (uint64_t)(c >> 64);
+    const uint64_t q = t[0] * ninv;
+    c = ((u128)q * m.v[0] + t[0]) >> 64;
+    for (int j = 1; j < 4; ++j) {
+      c += (u128)q * m.v[j] + t[j];
+      t[j - 1] = (uint64_t)c;
+      c >>= 64;
+    }
+    c += t[4];
+    t[3] = (uint64_t)c;
+    t[4] = t[5] + (uint64_t)(c >> 64);
+  }
+  U256 r = {{t[0], t[1], t[2], t[3]}};
+  if (t[4] || geq(r, m)) r = sub(r, m);
+  return r;
+}
+// R mod r and R^2 mod r, R = 2^256 (frMontR, io.nim:91): c -> c R is mont_mul(c, FR_R2)
+[[maybe_unused]] const U256 FR_ONE = {{0xac96341c4ffffffbull, 0x36fc76959f60cd29ull, 0x666ea36f7879462eull, 0x0e0a77c19a07df2full}};
+[[maybe_unused]] const U256 FR_R2 = {{0x1bb8e645ae216da7ull, 0x53fe3ab1e35c59e3ull, 0x8c49833d53bb8085ull, 0x0216d0b17f4e44a5ull}};
 U256 load(const uint8_t* p) {
   U256 r;
   memcpy(r.v, p, 32);
@@ -250,6 +282,45 @@ struct WtnsFile {   // witness.nim:36-60
     if (w2.len != (size_t)nvars * 32) die("unexpected witness section length");
     values = w2.p;
   }
+};
+
+// ---- parsed .r1cs (files/r1cs.nim:84-155): header, then the constraints as triplets per matrix -- the form
+// g16_setup_desc takes.  Values stay in standard form, as they lie in the file (G16_SCALARS_STD).  Every count and
+// section size is held to the length of the file before anything is indexed by it.
+struct R1csFile {
+  Container rc;
+  uint32_t nwires = 0, npubout = 0, npubin = 0, nprivin = 0, nconstraints = 0;
+  std::vector<uint32_t> row[3], col[3];   // matrix k = 0, 1, 2 = A, B, C: constraint, wire
+  std::vector<uint8_t> val[3];            // 32 bytes per entry
+  explicit R1csFile(const char* path) : rc(path, "r1cs", 1) {
+    Section s1 = rc.get(1);   // r1cs.nim:84-108
+    if (s1.len != 4 + 32 + 16 + 8 + 4) die("unexpected r1cs header length");
+    const uint8_t* p = s1.p;
+    expect_prime(p, PRIME_R, "r1cs field");
+    nwires = u32(p), npubout = u32(p + 4), npubin = u32(p + 8), nprivin = u32(p + 12);
+    nconstraints = u32(p + 24);   // (after the 64-bit label count)
+    if ((uint64_t)npubout + npubin + nprivin + 1 > nwires) die("r1cs header: more inputs and outputs than wires");
+    Section s2 = rc.get(2);   // r1cs.nim:112-142
+    if ((uint64_t)nconstraints * 12 > s2.len) die("constraint count exceeds the constraint section");
+    size_t pos = 0;
+    for (uint32_t i = 0; i < nconstraints; ++i)
+      for (int k = 0; k < 3; ++k) {
+        if (s2.len - pos < 4) die("truncated constraint section");
+        const uint32_t nterms = u32(s2.p + pos);
+        pos += 4;
+        if ((uint64_t)nterms * 36 > s2.len - pos) die("term count exceeds the constraint section");
+        for (uint32_t t = 0; t < nterms; ++t, pos += 36) {
+          const uint32_t wire = u32(s2.p + pos);
+          if (wire >= nwires) die("wire index out of range");
+          row[k].push_back(i);
+          col[k].push_back(wire);
+          val[k].insert(val[k].end(), s2.p + pos + 4, s2.p + pos + 36);
+        }
+      }
+    if (pos != s2.len) die("unexpected constraint section length");
+    if (rc.sec.count(3) && rc.get(3).len != (size_t)nwires * 8) die("unexpected label section length");   // r1cs.nim:146-152
+  }
+  uint32_t npubs() const { return npubout + npubin; }
 };
 
 }  // namespace

@@ -6,6 +6,14 @@
 //       -Wl,-rpath,$PWD/nim_groth16_amd/csrc -o g16prove
 //   ./g16prove -z circuit.zkey -w witness.wtns -o proof.json -i public.json [-n] [-y] [-t] [--gpus 0,1,2,3]
 //             [--table-stride S]
+//   ./g16prove -u -r circuit.r1cs [--toxic-seed N] -w witness.wtns -o proof.json -i public.json [-y] ...
+//
+// -u/--setup -r/--r1cs circuit.r1cs: the reference's fake circuit-specific trusted setup (cli/cli_main.nim:184-193,
+// groth16/fake_setup.nim:201-326) in place of a .zkey: g16_fake_setup builds the key's points on the GPU from the R1CS and
+// toxic waste, the coefficients are the R1CS's A and B entries (r1csToCoeffs, fake_setup.nim:46-65), and the proof is made
+// and verified against that key.  --toxic-seed N (default 0): the five toxic scalars alpha, beta, gamma, delta, tau are
+// 256-bit draws of SplitMix64(N), four words each in that order, least significant word first, with the top three bits
+// cleared -- below r without any host arithmetic.  Toxic waste that anyone can derive: for tests and benchmarks only.
 //
 // --table-stride S: a lean key -- window tables for every S-th window only (g16_pkey_create_zkey_lean: about 1 / S of
 // the HBM, more bucket reduction per proof, the same proof).
@@ -17,9 +25,82 @@
 #define G16_TOOL_NAME "g16prove"
 #include "g16_files.hpp"
 
+#include <memory>
+
+namespace {
+
+// A key from g16_fake_setup: the points in host buffers, ZKey.coeffs from the R1CS (Montgomery values)
+struct SetupKey {
+  R1csFile rf;
+  uint32_t log2n = 0;
+  std::vector<uint8_t> spec, ic, a1, b1, b2, c1, h1;   // spec = alpha1 | beta1 | delta1 | beta2 | gamma2 | delta2
+  std::vector<g16_coeff> coeffs;
+  SetupKey(const char* path, uint64_t seed, g16_ctx* ctx) : rf(path) {
+    uint64_t state = seed;
+    auto splitmix = [&]() {
+      uint64_t z = (state += 0x9E3779B97F4A7C15ull);
+      z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+      z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+      return z ^ (z >> 31);
+    };
+    U256 toxic[5];
+    for (U256& t : toxic) {
+      for (int i = 0; i < 4; ++i) t.v[i] = splitmix();
+      t.v[3] &= 0x1fffffffffffffffull;   // < 2^253 < r
+    }
+    const uint32_t nvars = rf.nwires, npubs = rf.npubs();
+    g16_setup_desc d;
+    memset(&d, 0, sizeof d);
+    d.nvars = nvars, d.npubs = npubs, d.nconstraints = rf.nconstraints, d.flavour = G16_FLAVOUR_SNARKJS;
+    for (int k = 0; k < 3; ++k)
+      d.row[k] = rf.row[k].data(), d.col[k] = rf.col[k].data(), d.val[k] = rf.val[k].data(), d.nnz[k] = rf.row[k].size();
+    d.flags = G16_SCALARS_STD;
+    d.alpha = toxic[0].v, d.beta = toxic[1].v, d.gamma = toxic[2].v, d.delta = toxic[3].v, d.tau = toxic[4].v;
+    if (nvars <= npubs) die("r1cs header: no more wires than public inputs and outputs");
+    if (g16_setup_log2_domain(&d, &log2n) != G16_OK || log2n > 27) die("circuit too large");
+    spec.resize(3 * 64 + 3 * 128), ic.resize(64 * ((size_t)npubs + 1)), a1.resize(64 * (size_t)nvars);
+    b1.resize(64 * (size_t)nvars), b2.resize(128 * (size_t)nvars), c1.resize(64 * ((size_t)nvars - npubs - 1) + 1);
+    h1.resize((size_t)64 << log2n);
+    g16_setup_points o;
+    o.alpha1 = &spec[0], o.beta1 = &spec[64], o.delta1 = &spec[128];
+    o.beta2 = &spec[192], o.gamma2 = &spec[320], o.delta2 = &spec[448];
+    o.pointsIC = ic.data(), o.pointsA1 = a1.data(), o.pointsB1 = b1.data(), o.pointsB2 = b2.data();
+    o.pointsC1 = c1.data(), o.pointsH1 = h1.data();
+    if (g16_fake_setup(ctx, &d, &o) != G16_OK) die(std::string("g16_fake_setup failed: ") + g16_last_error(ctx));
+    // ZKey.coeffs (fake_setup.nim:46-65): the A and B entries with Montgomery values, then the dummy A rows
+    for (uint32_t m = 0; m < 2; ++m)
+      for (size_t i = 0; i < rf.row[m].size(); ++i) {
+        g16_coeff c;
+        c.matrix = m, c.row = rf.row[m][i], c.col = rf.col[m][i], c.reserved = 0;
+        const U256 v = mont_mul(load(&rf.val[m][32 * i]), FR_R2, PRIME_R, R_NINV);
+        memcpy(c.value, v.v, 32);
+        coeffs.push_back(c);
+      }
+    for (uint32_t i = 0; i <= npubs; ++i) {
+      g16_coeff c;
+      c.matrix = 0, c.row = rf.nconstraints + i, c.col = i, c.reserved = 0;
+      memcpy(c.value, FR_ONE.v, 32);
+      coeffs.push_back(c);
+    }
+  }
+  g16_pkey_desc desc() const {
+    g16_pkey_desc d;
+    memset(&d, 0, sizeof d);
+    d.nvars = rf.nwires, d.npubs = rf.npubs(), d.log2_domain = log2n, d.flavour = G16_FLAVOUR_SNARKJS;
+    d.pointsA1 = a1.data(), d.pointsB1 = b1.data(), d.pointsB2 = b2.data(), d.pointsC1 = c1.data(), d.pointsH1 = h1.data();
+    d.coeffs = coeffs.data(), d.ncoeffs = coeffs.size();
+    d.alpha1 = &spec[0], d.beta1 = &spec[64], d.delta1 = &spec[128], d.beta2 = &spec[192], d.delta2 = &spec[448];
+    d.shard_index = 0, d.shard_count = 1;
+    return d;
+  }
+};
+
+}  // namespace
+
 int main(int argc, char** argv) {
-  const char *zpath = nullptr, *wpath = nullptr, *opath = "proof.json", *ipath = "public.json";
-  bool nomask = false, verify = false, timing = false;
+  const char *zpath = nullptr, *wpath = nullptr, *rpath = nullptr, *opath = "proof.json", *ipath = "public.json";
+  bool nomask = false, verify = false, timing = false, setup = false;
+  uint64_t toxic_seed = 0;
   std::vector<int32_t> gpus;
   uint32_t table_stride = 0;
   for (int i = 1; i < argc; ++i) {
@@ -32,6 +113,14 @@ int main(int argc, char** argv) {
     else if (a == "-w" || a == "--wtns") wpath = next();
     else if (a == "-o" || a == "--output") opath = next();
     else if (a == "-i" || a == "--io") ipath = next();
+    else if (a == "-r" || a == "--r1cs") rpath = next();    // cli_main.nim -r
+    else if (a == "-u" || a == "--setup") setup = true;     // cli_main.nim -u
+    else if (a == "--toxic-seed") {
+      char* end = nullptr;
+      const char* q = next();
+      toxic_seed = strtoull(q, &end, 10);
+      if (end == q || *end) die("--toxic-seed takes an unsigned 64-bit number");
+    }
     else if (a == "-n" || a == "--nomask") nomask = true;   // cli_main.nim -n
     else if (a == "-y" || a == "--verify") verify = true;   // cli_main.nim -y
     else if (a == "-t" || a == "--time") timing = true;     // cli_main.nim -t
@@ -51,29 +140,38 @@ int main(int argc, char** argv) {
       if (end == q || *end || s < 0 || s > 255) die("--table-stride takes a number from 0 to 255");
       table_stride = (uint32_t)s;
     }
-    else die("unknown option " + a + "\nusage: g16prove -z circuit.zkey -w witness.wtns [-o proof.json] [-i public.json] [-n] [-y] [-t] [--gpus 0,1,...] [--table-stride S]");
+    else die("unknown option " + a + "\nusage: g16prove -z circuit.zkey -w witness.wtns [-o proof.json] [-i public.json] [-n] [-y] [-t] [--gpus 0,1,...] [--table-stride S]\n       g16prove -u -r circuit.r1cs [--toxic-seed N] -w witness.wtns ...");
   }
-  if (!zpath || !wpath) die("usage: g16prove -z circuit.zkey -w witness.wtns [-o proof.json] [-i public.json] [-n] [-y] [-t]");
+  if (setup ? (!rpath || zpath || !wpath) : (!zpath || rpath || !wpath))
+    die("usage: g16prove -z circuit.zkey -w witness.wtns [-o proof.json] [-i public.json] [-n] [-y] [-t]\n"
+        "       g16prove -u -r circuit.r1cs [--toxic-seed N] -w witness.wtns [-o proof.json] [-i public.json] [-n] [-y] [-t]");
 
   const double t0 = now();
-  ZkeyFile zf(zpath);
-  WtnsFile wf(wpath, zf.nvars);
-  const uint32_t npubs = zf.npubs;
-  const uint8_t* wvals = wf.values;
-  const double t1 = now();
-
   g16_ctx* ctx = nullptr;
   if (g16_ctx_create(gpus.empty() ? 0 : gpus[0], &ctx) != G16_OK) die("no usable GPU (there is no CPU fallback)");
   auto chk = [&](int32_t rc, const char* what) {
     if (rc != G16_OK) die(std::string(what) + " failed: " + g16_last_error(ctx));
   };
   chk(g16_selftest(ctx), "g16_selftest");
-  g16_pkey_desc d = zf.desc(gpus.empty());   // one GPU: the coefficient section goes to the library as it lies in the file
+  std::unique_ptr<ZkeyFile> zfp;
+  std::unique_ptr<SetupKey> skp;
+  if (setup) skp.reset(new SetupKey(rpath, toxic_seed, ctx));
+  else zfp.reset(new ZkeyFile(zpath));
+  const uint32_t nvars = setup ? skp->rf.nwires : zfp->nvars;
+  const uint32_t npubs = setup ? skp->rf.npubs() : zfp->npubs;
+  WtnsFile wf(wpath, nvars);
+  const uint8_t* wvals = wf.values;
+  const double t1 = now();
+
+  // one GPU and a .zkey: the coefficient section goes to the library as it lies in the file
+  g16_pkey_desc d = setup ? skp->desc() : zfp->desc(gpus.empty());
   g16_pkey* key = nullptr;
   g16_group* grp = nullptr;
   g16_group_pkey* gkey = nullptr;
-  if (gpus.empty()) {
-    chk(g16_pkey_create_zkey_lean(ctx, &d, zf.section4, zf.section4_len, table_stride, &key), "g16_pkey_create_zkey");
+  if (gpus.empty() && setup) {
+    chk(g16_pkey_create_lean(ctx, &d, table_stride, &key), "g16_pkey_create");
+  } else if (gpus.empty()) {
+    chk(g16_pkey_create_zkey_lean(ctx, &d, zfp->section4, zfp->section4_len, table_stride, &key), "g16_pkey_create_zkey");
   } else {
     if (g16_group_create(gpus.data(), (int32_t)gpus.size(), &grp) != G16_OK) die("g16_group_create failed");
     if (g16_group_pkey_create_lean(grp, &d, table_stride, &gkey) != G16_OK)
@@ -125,7 +223,13 @@ int main(int argc, char** argv) {
 
   if (verify) {  // verifier.nim:31-52 on the GPU
     g16_vkey_desc vd;
-    vd.npubs = npubs, vd.alpha1 = zf.alpha1, vd.beta2 = zf.beta2, vd.gamma2 = zf.gamma2, vd.delta2 = zf.delta2, vd.pointsIC = zf.ic;
+    vd.npubs = npubs;
+    if (setup) {
+      vd.alpha1 = &skp->spec[0], vd.beta2 = &skp->spec[192], vd.gamma2 = &skp->spec[320], vd.delta2 = &skp->spec[448];
+      vd.pointsIC = skp->ic.data();
+    } else {
+      vd.alpha1 = zfp->alpha1, vd.beta2 = zfp->beta2, vd.gamma2 = zfp->gamma2, vd.delta2 = zfp->delta2, vd.pointsIC = zfp->ic;
+    }
     g16_vkey* vk = nullptr;
     chk(g16_vkey_create(ctx, &vd, &vk), "g16_vkey_create");
     int32_t st = 0;
@@ -135,7 +239,8 @@ int main(int argc, char** argv) {
     if (st != 1) return 1;
   }
   if (timing)
-    printf("parsing %.3fs | key upload + tables %.3fs | proof %.3fs\n", t1 - t0, t2 - t1, t3 - t2);
+    printf("%s %.3fs | key upload + tables %.3fs | proof %.3fs\n", setup ? "parsing + setup" : "parsing", t1 - t0, t2 - t1,
+           t3 - t2);
   g16_pkey_destroy(key);
   g16_group_pkey_destroy(gkey);
   g16_group_destroy(grp);
