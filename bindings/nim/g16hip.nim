@@ -289,6 +289,77 @@ proc verifyProofsBatch*(vkey: VKey, prfs: openArray[Proof]): bool =
   check g16_verify_batch(gctx, k, addr ps[0], addr io[0], G16_SCALARS_MONT, csize_t(prfs.len), addr zs[0], addr res, nil)
   result = res == 1
 
+# --- key audit (include/g16hip.h "key audit"): is a ZKey from a third party fit to prove with? -------------------------
+# The reference asserts the curve equations while it loads a .zkey (mkG1 / mkG2, curves.nim:95-107).  auditKey is for the
+# host that is handed keys: canonical encodings, curve membership, the order-r subgroup of every G2 point, coefficient
+# values < r, and pointsB1 ~ pointsB2, beta1 ~ beta2, delta1 ~ delta2 -- before loadKeyGpu, and without touching any state.
+# It cannot tell whether the key belongs to a circuit: nothing ties A1 / C1 / H1 / IC to an R1CS without the transcript.
+const
+  G16_AUDIT_SECTIONS* = 13
+  auditSectionNames* = ["alpha1", "beta1", "delta1", "beta2", "gamma2", "delta2", "pointsIC", "pointsA1", "pointsB1",
+                        "pointsB2", "pointsC1", "pointsH1", "coeffs"]
+  auditCheckNames* = ["is not a canonical encoding", "is not on the curve", "is not in the order-r subgroup"]
+  auditRelationNames* = ["pointsB1~pointsB2", "beta1~beta2", "delta1~delta2"]
+type
+  KeyReport* {.importc: "g16_key_report", header: "g16hip.h".} = object
+    failed*: uint32                 ## OR of G16_AUDIT_*: 0 = fit to prove with
+    spec_infinity*: uint32          ## bit s: spec point s is (0,0)
+    relation*: array[3, int32]      ## 1 holds, 0 fails, -1 not run
+    reserved: uint32
+    first_bad*: array[G16_AUDIT_SECTIONS, array[3, csize_t]]   ## high(csize_t) = none
+    bad_count*: array[G16_AUDIT_SECTIONS, array[3, csize_t]]
+
+proc g16_points_audit_g1(ctx: ptr G16Ctx, points: pointer, n: csize_t, firstBad, badCount: ptr csize_t): int32 {.importc, header: "g16hip.h".}
+proc g16_points_audit_g2(ctx: ptr G16Ctx, points: pointer, n: csize_t, firstBad, badCount: ptr csize_t): int32 {.importc, header: "g16hip.h".}
+proc g16_points_pairs_check(ctx: ptr G16Ctx, g1Points, g2Points: pointer, n: csize_t, multipliers: pointer,
+                            res: ptr int32): int32 {.importc, header: "g16hip.h".}
+proc g16_key_audit(ctx: ptr G16Ctx, desc: ptr G16PKeyDesc, vk: ptr G16VKeyDesc, section4: pointer, section4Bytes: csize_t,
+                   multipliers: pointer, res: ptr KeyReport): int32 {.importc, header: "g16hip.h".}
+
+proc ok*(r: KeyReport): bool = r.failed == 0
+
+proc `$`*(r: KeyReport): string =
+  ## the section, index and check of every first finding
+  if r.ok: return "key audit: ok"
+  result = "key audit: FAILED"
+  for s in 0 ..< G16_AUDIT_SECTIONS:
+    for k in 0 ..< 3:
+      if r.bad_count[s][k] > 0:
+        result.add "\n  " & auditSectionNames[s] & "[" & $r.first_bad[s][k] & "] " & auditCheckNames[k]
+        if r.bad_count[s][k] > 1: result.add " (and " & $(r.bad_count[s][k] - 1) & " more)"
+  for k in 0 ..< 3:
+    if r.relation[k] == 0: result.add "\n  " & auditRelationNames[k] & ": not the same multiples of the two generators"
+  for s in 0 ..< 6:
+    if ((r.spec_infinity shr s) and 1) != 0: result.add "\n  " & auditSectionNames[s] & " is the point at infinity"
+
+proc auditKey*(zkey: ZKey): KeyReport =
+  ## g16_key_audit over the whole ZKey (its verifier half included); the multipliers of the batched B1 ~ B2 relation
+  ## are drawn HERE from the OS CSPRNG (std/sysrand), as verifyProofsBatch draws its own.
+  var cs = newSeq[G16Coeff](max(zkey.coeffs.len, 1))
+  for i, c in zkey.coeffs:
+    cs[i] = G16Coeff(matrix: uint32(ord(c.matrix)), row: uint32(c.row), col: uint32(c.col))
+    copyMem(addr cs[i].value, unsafeAddr c.coeff, 32)
+  var d = G16PKeyDesc(nvars: uint32(zkey.header.nvars), npubs: uint32(zkey.header.npubs),
+    log2_domain: uint32(zkey.header.logDomainSize), flavour: uint32(ord(zkey.header.flavour)),
+    pointsA1: unsafeAddr zkey.pPoints.pointsA1[0], pointsB1: unsafeAddr zkey.pPoints.pointsB1[0],
+    pointsB2: unsafeAddr zkey.pPoints.pointsB2[0],
+    pointsC1: (if zkey.pPoints.pointsC1.len > 0: unsafeAddr zkey.pPoints.pointsC1[0] else: nil),
+    pointsH1: unsafeAddr zkey.pPoints.pointsH1[0], coeffs: addr cs[0], ncoeffs: csize_t(zkey.coeffs.len),
+    alpha1: unsafeAddr zkey.specPoints.alpha1, beta1: unsafeAddr zkey.specPoints.beta1,
+    delta1: unsafeAddr zkey.specPoints.delta1, beta2: unsafeAddr zkey.specPoints.beta2,
+    delta2: unsafeAddr zkey.specPoints.delta2, shard_index: 0, shard_count: 1)
+  var v = G16VKeyDesc(npubs: uint32(zkey.header.npubs), alpha1: unsafeAddr zkey.specPoints.alpha1,
+    beta2: unsafeAddr zkey.specPoints.beta2, gamma2: unsafeAddr zkey.specPoints.gamma2,
+    delta2: unsafeAddr zkey.specPoints.delta2, pointsIC: unsafeAddr zkey.vPoints.pointsIC[0])
+  var zs = newSeq[array[16, byte]](zkey.header.nvars)         # 128-bit little-endian multipliers, none zero
+  for z in zs.mitems:
+    while true:
+      doAssert urandom(z)
+      var any = false
+      for b in z: any = any or b != 0
+      if any: break
+  check g16_key_audit(gctx, addr d, addr v, nil, 0, addr zs[0], addr result)
+
 # --- drop-in for fakeCircuitSetup (groth16/fake_setup.nim:201-326): one g16_fake_setup call ----------------------------
 # The Lagrange values, the column sums, the combinations and the H scalars are formed on the device and stay in HBM; the
 # points come back into the seqs of the ZKey.  ZKey.coeffs is the reference's own r1csToCoeffs (fake_setup.nim:46-65).

@@ -461,6 +461,75 @@ int32_t g16_pairing(g16_ctx* ctx, const void* g1_points, const void* g2_points, 
 int32_t g16_verify_batch(g16_ctx* ctx, const g16_vkey* key, const g16_proof* proofs, const void* public_io,
                          uint32_t flags, size_t count, const void* multipliers, int32_t* result, int32_t* status);
 
+/* ---- key audit: is an UNTRUSTED proving key fit to prove with? ------------------------------------------------------
+ * g16_pkey_create* take a key as it is, and g16_points_check_* are the reference's curve asserts only (mkG1 / mkG2,
+ * curves.nim:95-107).  The calls below are for a service that is handed .zkey files by third parties.  None of them
+ * changes any state: a context proves the same bytes before and after.  Host pointers throughout.
+ *
+ * g16_points_audit_g1/g2: three checks per element, in this precedence:
+ *   [0] canonical: every Fp limb pattern is < p
+ *   [1] on the curve y^2 = x^3 + b; (0,0) is infinity and passes
+ *   [2] in the order-r subgroup, [r]Q == infinity by the definition (G2 only: G1 has cofactor 1, its [2] is always
+ *       "none")
+ * An element that fails a check is counted under that check ONLY and is not examined by the later ones: the field
+ * arithmetic would silently reduce a non-canonical pattern, so an alias of a valid point would pass [1] and [2].
+ * first_bad[k] = index of the first element failing check k, (size_t)-1 when none does; bad_count[k] = how many.
+ * n < 2^31. */
+int32_t g16_points_audit_g1(g16_ctx* ctx, const void* points, size_t n, size_t first_bad[3], size_t bad_count[3]);
+int32_t g16_points_audit_g2(g16_ctx* ctx, const void* points, size_t n, size_t first_bad[3], size_t bad_count[3]);
+/* Do P_i (G1) and Q_i (G2) have the same logarithm, P_i = k_i gen1 and Q_i = k_i gen2, for every i?  One
+ * random-linear-combination pairing equation:
+ *   *result = 1 exactly when  e(sum_i z_i P_i, gen2) * e(-gen1, sum_i z_i Q_i) == 1,  0 otherwise  (n == 0 gives 1):
+ * two one-shot MSMs, two Miller loops, one final exponentiation.
+ * PRECONDITION: both arrays pass g16_points_audit_* (no element fails any check).  The call does not repeat those
+ * checks, and its arithmetic is only defined on canonical points of the curve and subgroup.
+ * multipliers: n x 16 bytes, little-endian 128-bit z_i, every one non-zero, drawn by the CALLER from a CSPRNG after the
+ * arrays are fixed, exactly as for g16_verify_batch; the library draws no randomness.  A zero multiplier: G16_EINVAL,
+ * g16_last_error names the index.  n < 2^27.
+ * Soundness, as for g16_verify_batch: with P_i = a_i gen1 and Q_i = b_i gen2 the equation says sum_i z_i (a_i - b_i) = 0
+ * (mod r); if any a_i != b_i that is a non-zero linear form in the z_i over Fr, so *result == 1 with probability at most
+ * 1/(2^128 - 1) over multipliers uniform in the non-zero 128-bit values and independent of the arrays. */
+int32_t g16_points_pairs_check(g16_ctx* ctx, const void* g1_points, const void* g2_points, size_t n,
+                               const void* multipliers, int32_t* result);
+/* The whole key.  Sections, in the order of the report: */
+#define G16_AUDIT_SECTIONS 13
+enum {
+  G16_SEC_ALPHA1 = 0, G16_SEC_BETA1, G16_SEC_DELTA1, G16_SEC_BETA2, G16_SEC_GAMMA2, G16_SEC_DELTA2, G16_SEC_POINTS_IC,
+  G16_SEC_POINTS_A1, G16_SEC_POINTS_B1, G16_SEC_POINTS_B2, G16_SEC_POINTS_C1, G16_SEC_POINTS_H1, G16_SEC_COEFFS
+};
+#define G16_AUDIT_CANONICAL 1u     /* some element fails check [0] */
+#define G16_AUDIT_CURVE 2u         /* ... check [1] */
+#define G16_AUDIT_SUBGROUP 4u      /* ... check [2] */
+#define G16_AUDIT_RELATION 8u      /* a relation that was run does not hold */
+#define G16_AUDIT_SPEC_INFINITY 16u /* a spec point is (0,0): on the curve, but no key of a real setup holds one */
+typedef struct {
+  uint32_t failed;        /* OR of G16_AUDIT_*; 0 = fit to prove with */
+  uint32_t spec_infinity; /* bit s set: spec point s (G16_SEC_ALPHA1 .. G16_SEC_DELTA2) is (0,0) */
+  /* [0] pointsB1 ~ pointsB2 (g16_points_pairs_check with the multipliers), [1] beta1 ~ beta2, [2] delta1 ~ delta2 (the
+   * last two exact: two Miller loops each, no multipliers).  1 = holds, 0 = fails, -1 = not run: a section it reads
+   * failed an element check, or (for [0]) multipliers == NULL */
+  int32_t relation[3];
+  uint32_t reserved;
+  size_t first_bad[G16_AUDIT_SECTIONS][3]; /* per section and check, as g16_points_audit_* */
+  size_t bad_count[G16_AUDIT_SECTIONS][3];
+} g16_key_report;
+/* desc: the key as for g16_pkey_create* (a sharded one, shard_count > 1, is G16_EINVAL: audit the whole key).
+ * vk: NULL, or the key's verification half -- only gamma2 and pointsIC (npubs + 1 points; vk->npubs == desc->npubs) are
+ *   read from it; with NULL those two sections are reported as empty.
+ * coefficients: desc->coeffs / ncoeffs, or section 4 of the .zkey as for g16_pkey_create_zkey (then desc->coeffs = NULL,
+ *   desc->ncoeffs = 0); section4 == NULL and no desc->coeffs: none.  Only check [0] applies to them: the value is < r
+ *   (the Montgomery limbs of a g16_coeff; for section 4 the 32-byte integer on file) -- buildABC's products are only
+ *   correct for operands < r.  A matrix selector, row or column out of range is G16_EINVAL, as for g16_pkey_create*.
+ * multipliers: desc->nvars x 16 bytes as for g16_points_pairs_check, or NULL to skip the pointsB1 ~ pointsB2 relation.
+ * Every array is uploaded whole, one at a time, into the context's staging buffer; all work runs on the context's
+ * stream with one wait after the element passes (the relations run only on sections whose every element passed)
+ * and one at the end.
+ * What the audit CANNOT establish: that the key belongs to any circuit.  Nothing ties pointsA1 / pointsC1 / pointsH1 /
+ * pointsIC (or the values of alpha, beta, gamma, delta) to an R1CS without the ceremony transcript; a key can pass
+ * every check here and still prove nothing about the statement its user has in mind. */
+int32_t g16_key_audit(g16_ctx* ctx, const g16_pkey_desc* desc, const g16_vkey_desc* vk, const void* section4,
+                      size_t section4_bytes, const void* multipliers, g16_key_report* out);
+
 /* ---- profiling ---------------------------------------------------------------------------------- */
 /* on = 1: every kernel launch is bracketed by HIP events on the stream it is launched on; on = 2: only the
  * bucket-accumulation kernels (cheap enough to leave on inside a timed region); on = 0: off */

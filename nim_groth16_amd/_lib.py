@@ -32,6 +32,7 @@ SYMBOLS = [
     "g16_points_register_g2_lean_dev", "g16_points_table_bytes", "g16_points_plan", "g16_pkey_create_lean",
     "g16_pkey_create_zkey_lean", "g16_group_pkey_create_lean",
     "g16_setup_log2_domain", "g16_fake_setup", "g16_lagrange_fr", "g16_powers_fr",
+    "g16_points_audit_g1", "g16_points_audit_g2", "g16_points_pairs_check", "g16_key_audit",
 ]
 VERIFY_SUBGROUP = 16
 GT_BYTES = 384
@@ -72,6 +73,64 @@ SETUP_POINTS = ("alpha1", "beta1", "delta1", "beta2", "gamma2", "delta2", "point
 class SetupPoints(ctypes.Structure):
     """g16_setup_points (include/g16hip.h)"""
     _fields_ = [(name, ctypes.c_void_p) for name in SETUP_POINTS]
+
+
+# key audit (include/g16hip.h): the sections of a report in order, the checks in precedence, the bits of `failed`
+AUDIT_SECTIONS = ("alpha1", "beta1", "delta1", "beta2", "gamma2", "delta2", "pointsIC", "pointsA1", "pointsB1", "pointsB2",
+                  "pointsC1", "pointsH1", "coeffs")
+AUDIT_CHECKS = ("canonical", "curve", "subgroup")
+AUDIT_RELATIONS = ("pointsB1~pointsB2", "beta1~beta2", "delta1~delta2")
+AUDIT_CANONICAL, AUDIT_CURVE, AUDIT_SUBGROUP, AUDIT_RELATION, AUDIT_SPEC_INFINITY = 1, 2, 4, 8, 16
+
+
+class KeyReportC(ctypes.Structure):
+    """g16_key_report (include/g16hip.h)"""
+    _fields_ = [("failed", ctypes.c_uint32), ("spec_infinity", ctypes.c_uint32), ("relation", ctypes.c_int32 * 3),
+                ("reserved", ctypes.c_uint32),
+                ("first_bad", (ctypes.c_size_t * 3) * len(AUDIT_SECTIONS)),
+                ("bad_count", (ctypes.c_size_t * 3) * len(AUDIT_SECTIONS))]
+
+
+class KeyReport:
+    """What g16_key_audit found.  first_bad[section][check] is an index or None, bad_count[section][check] a count;
+    relation[k] is 1 (holds), 0 (fails) or -1 (not run) for AUDIT_RELATIONS[k]."""
+
+    def __init__(self, failed, spec_infinity, relation, first_bad, bad_count):
+        self.failed, self.spec_infinity, self.relation = failed, spec_infinity, list(relation)
+        self.first_bad, self.bad_count = first_bad, bad_count
+
+    @property
+    def ok(self) -> bool:
+        """fit to prove with"""
+        return self.failed == 0
+
+    def as_dict(self) -> dict:
+        return {"failed": self.failed, "spec_infinity": self.spec_infinity, "relation": self.relation,
+                "first_bad": self.first_bad, "bad_count": self.bad_count}
+
+    def findings(self):
+        """one line per first finding: section, index and check; failed relations; spec points at infinity"""
+        out = []
+        for s, name in enumerate(AUDIT_SECTIONS):
+            for k, check in enumerate(AUDIT_CHECKS):
+                if self.bad_count[s][k]:
+                    what = {"canonical": "is not a canonical encoding", "curve": "is not on the curve",
+                            "subgroup": "is not in the order-r subgroup"}[check]
+                    more = self.bad_count[s][k] - 1
+                    out.append(f"{name}[{self.first_bad[s][k]}] {what}" + (f" (and {more} more)" if more else ""))
+        for k, name in enumerate(AUDIT_RELATIONS):
+            if self.relation[k] == 0:
+                out.append(f"{name}: not the same multiples of the two generators")
+        for s in range(6):
+            if self.spec_infinity >> s & 1:
+                out.append(f"{AUDIT_SECTIONS[s]} is the point at infinity")
+        return out
+
+    def __str__(self):
+        if self.ok:
+            skipped = [AUDIT_RELATIONS[k] for k in range(3) if self.relation[k] < 0]
+            return "key audit: ok" + (f" (not run: {', '.join(skipped)})" if skipped else "")
+        return "key audit: FAILED\n" + "\n".join("  " + f for f in self.findings())
 
 
 class G16Error(RuntimeError):
@@ -222,6 +281,11 @@ def load_library():
     lib.g16_fake_setup.argtypes = [vp, ctypes.POINTER(SetupDesc), ctypes.POINTER(SetupPoints)]
     lib.g16_lagrange_fr.argtypes = [vp, u32, u32, u32, sz, vp, vp, vp]
     lib.g16_powers_fr.argtypes = [vp, vp, vp, sz, vp]
+    lib.g16_points_audit_g1.argtypes = [vp, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(sz)]
+    lib.g16_points_audit_g2.argtypes = [vp, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(sz)]
+    lib.g16_points_pairs_check.argtypes = [vp, vp, vp, sz, vp, ctypes.POINTER(i32)]
+    lib.g16_key_audit.argtypes = [vp, ctypes.POINTER(PkeyDesc), ctypes.POINTER(VkeyDesc), vp, sz, vp,
+                                  ctypes.POINTER(KeyReportC)]
     for name in SYMBOLS:
         if name not in ("g16_ctx_destroy", "g16_last_error", "g16_points_release", "g16_points_count",
                         "g16_points_inf_count",
@@ -337,6 +401,51 @@ class Context:
         fn = self._lib.g16_points_check_g1 if group == 1 else self._lib.g16_points_check_g2
         self._check(fn(self._h, _buf(points) if n else None, n, ctypes.byref(bad)))
         return None if bad.value == ctypes.c_size_t(-1).value else bad.value
+
+    # ---- key audit ------------------------------------------------------------------------------
+    def points_audit(self, group: int, points: bytes):
+        """g16_points_audit_g1/g2 -> (first_bad, bad_count): per check (canonical, curve, subgroup) the index of the
+        first failing element (None: none) and how many fail; an element counts under the first check it fails"""
+        psz = 64 if group == 1 else 128
+        assert len(points) % psz == 0
+        n = len(points) // psz
+        first, count = (ctypes.c_size_t * 3)(), (ctypes.c_size_t * 3)()
+        fn = self._lib.g16_points_audit_g1 if group == 1 else self._lib.g16_points_audit_g2
+        self._check(fn(self._h, _buf(points) if n else None, n, first, count))
+        none = ctypes.c_size_t(-1).value
+        return [None if f == none else f for f in first], list(count)
+
+    def pairs_check(self, g1_points: bytes, g2_points: bytes, multipliers) -> bool:
+        """g16_points_pairs_check: are g1_points[i] and g2_points[i] the same multiple of gen1 and gen2 for every i?
+        Both arrays must pass points_audit.  multipliers: one int in [1, 2^128) per pair, drawn by the caller."""
+        n = len(g1_points) // 64
+        assert len(g1_points) == 64 * n and len(g2_points) == 128 * n and len(multipliers) == n
+        zs = b"".join(int(z).to_bytes(16, "little") for z in multipliers)
+        res = ctypes.c_int32(-1)
+        self._check(self._lib.g16_points_pairs_check(self._h, _buf(g1_points) if n else None,
+                                                     _buf(g2_points) if n else None, n, _buf(zs) if n else None,
+                                                     ctypes.byref(res)))
+        return res.value == 1
+
+    def key_audit(self, desc: PkeyDesc, vk: VkeyDesc = None, section4: bytes = None, multipliers=None) -> KeyReport:
+        """g16_key_audit.  desc / section4 as for ProvingKey; vk: a VkeyDesc (gamma2 and pointsIC are read) or None;
+        multipliers: desc.nvars ints in [1, 2^128) (or their 16-byte encodings, joined), or None to skip the pointsB1 ~ pointsB2 relation."""
+        zs = None
+        if isinstance(multipliers, (bytes, bytearray)):             # already 16 little-endian bytes each
+            assert len(multipliers) == 16 * desc.nvars, "one multiplier per wire"
+            zs = bytes(multipliers)
+        elif multipliers is not None:
+            assert len(multipliers) == desc.nvars, "one multiplier per wire"
+            zs = b"".join(int(z).to_bytes(16, "little") for z in multipliers)
+        rep = KeyReportC()
+        self._check(self._lib.g16_key_audit(self._h, ctypes.byref(desc), ctypes.byref(vk) if vk is not None else None,
+                                            _buf(section4) if section4 is not None else None,
+                                            len(section4) if section4 is not None else 0,
+                                            _buf(zs) if zs is not None else None, ctypes.byref(rep)))
+        none = ctypes.c_size_t(-1).value
+        return KeyReport(rep.failed, rep.spec_infinity, list(rep.relation),
+                         [[None if f == none else f for f in row] for row in rep.first_bad],
+                         [list(row) for row in rep.bad_count])
 
     def fixed_base(self, group: int, scalars: bytes, mont: bool = True) -> bytes:
         """scalars[i] * generator -> affine points (fake_setup.nim:258-261 `y ** gen1/gen2`)."""

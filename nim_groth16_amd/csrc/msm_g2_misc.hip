@@ -29,3 +29,11 @@ template int32_t precompute_device<G2>(g16_ctx*, const void*, size_t, uint32_t, 
 template int32_t fixed_base_device<G2>(g16_ctx*, void*, bool, const void*, uint32_t, size_t, void*);
 template int32_t on_curve_device<G2>(g16_ctx*, const void*, size_t, uint32_t*);
 template int32_t live_bitmap_device<G2>(g16_ctx*, const void*, size_t, uint32_t*, uint32_t*);
+
+// the two constants for translation units that do not see CurveConsts (audit.hip)
+void g16_curve_consts_g2(void* gen2, void* twist_b) {
+  const g2_aff g = CurveConsts<G2>::gen();
+  const fp2_t b = CurveConsts<G2>::b();
+  memcpy(gen2, &g, sizeof g);
+  memcpy(twist_b, &b, sizeof b);
+}

@@ -28,6 +28,31 @@ def checkZKeyPoints(zk: ZKey, ctx=None) -> None:
         assert bad is None, f"mkG{group}: {name}[{bad}] is not a G{group} curve point"
 
 
+def auditZKey(zk: ZKey, ctx=None, multipliers=None):
+    """Is an untrusted key fit to prove with?  One g16_key_audit over every section of the key (include/g16hip.h):
+    canonical encodings, curve membership, the order-r subgroup for the G2 points, coefficient values < r, and the
+    relations pointsB1 ~ pointsB2, beta1 ~ beta2, delta1 ~ delta2.  -> _lib.KeyReport: `.ok`, and str() names the
+    section, index and check of every first finding.  multipliers: one int in [1, 2^128) per wire for the batched
+    relation; None draws them with `secrets`, as verifyProofsBatch does.  A key parsed with rawCoeffs is audited on
+    its coefficient section as it lies in the file.  What no audit can tell: whether the key belongs to a circuit."""
+    import ctypes
+    import secrets
+
+    from .._lib import VkeyDesc, default_context
+    from ..prover import pkeyDesc
+    ctx = ctx or default_context()
+    desc, bufs, raw4 = pkeyDesc(zk)
+    sp = zk.specPoints
+    vbufs = [ctypes.create_string_buffer(x, len(x)) for x in (sp.alpha1, sp.beta2, sp.gamma2, sp.delta2, zk.pointsIC)]
+    va = [ctypes.cast(b, ctypes.c_void_p) for b in vbufs]
+    vk = VkeyDesc(zk.header.npubs, va[0], va[1], va[2], va[3], va[4])
+    if multipliers is None:
+        multipliers = [secrets.randbelow((1 << 128) - 1) + 1 for _ in range(zk.header.nvars)]
+    rep = ctx.key_audit(desc, vk, section4=raw4, multipliers=multipliers)
+    del bufs, vbufs
+    return rep
+
+
 def parseZKey(fname: str, check: bool = False, ctx=None, rawCoeffs: bool = False) -> ZKey:
     """zkey.nim:241-246.  rawCoeffs: keep the coefficient section as it lies in the file (ZKey.coeffsSection4, handed to
     the GPU unparsed by loadProvingKey -> g16_pkey_create_zkey) instead of un-Montgomerying every entry on the host

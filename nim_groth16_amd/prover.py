@@ -40,12 +40,8 @@ def _cbuf(b: bytes):
     return ctypes.create_string_buffer(b, len(b)) if b else ctypes.create_string_buffer(1)
 
 
-def loadProvingKey(zkey: ZKey, ctx=None, shard_index: int = 0, shard_count: int = 1, table_stride: int = 0) -> ProvingKey:
-    """Uploads the ZKey once (the reference parses it once per run, files/zkey.nim:241-245).  With
-    shard_count > 1 only this rank's contiguous index range of every point set is kept (msm.nim:105-115).
-    table_stride >= 2: a lean key -- every point set keeps window tables for every table_stride-th window only (about
-    1 / table_stride of the HBM, more bucket reduction per proof; the proofs are the same bytes)."""
-    ctx = ctx or default_context()
+def pkeyDesc(zkey: ZKey, shard_index: int = 0, shard_count: int = 1):
+    """The g16_pkey_desc of a ZKey -> (desc, the buffers it points into, the raw coefficient section or None)"""
     hdr, pts, spec = zkey.header, zkey.pPoints, zkey.specPoints
     # shape asserts of generateProofWithMask (prover.nim:270-276)
     assert len(pts.pointsA1) == 64 * hdr.nvars and len(pts.pointsB1) == 64 * hdr.nvars
@@ -60,6 +56,16 @@ def loadProvingKey(zkey: ZKey, ctx=None, shard_index: int = 0, shard_count: int 
     desc = PkeyDesc(hdr.nvars, hdr.npubs, hdr.logDomainSize, hdr.flavour, addr[0], addr[1], addr[2], addr[3],
                     addr[4], None if raw4 is not None else addr[5], 0 if raw4 is not None else len(zkey.coeffs),
                     addr[6], addr[7], addr[8], addr[9], addr[10], shard_index, shard_count)
+    return desc, bufs, raw4
+
+
+def loadProvingKey(zkey: ZKey, ctx=None, shard_index: int = 0, shard_count: int = 1, table_stride: int = 0) -> ProvingKey:
+    """Uploads the ZKey once (the reference parses it once per run, files/zkey.nim:241-245).  With
+    shard_count > 1 only this rank's contiguous index range of every point set is kept (msm.nim:105-115).
+    table_stride >= 2: a lean key -- every point set keeps window tables for every table_stride-th window only (about
+    1 / table_stride of the HBM, more bucket reduction per proof; the proofs are the same bytes)."""
+    ctx = ctx or default_context()
+    desc, bufs, raw4 = pkeyDesc(zkey, shard_index, shard_count)
     return ProvingKey(ctx, desc, bufs, section4=raw4, table_stride=table_stride)
 
 

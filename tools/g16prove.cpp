@@ -5,7 +5,7 @@
 //   g++ -O2 -std=c++17 -Iinclude tools/g16prove.cpp -Lnim_groth16_amd/csrc -lg16hip
 //       -Wl,-rpath,$PWD/nim_groth16_amd/csrc -o g16prove
 //   ./g16prove -z circuit.zkey -w witness.wtns -o proof.json -i public.json [-n] [-y] [-t] [--gpus 0,1,2,3]
-//             [--table-stride S]
+//             [--table-stride S] [--audit-key]
 //   ./g16prove -u -r circuit.r1cs [--toxic-seed N] -w witness.wtns -o proof.json -i public.json [-y] ...
 //
 // -u/--setup -r/--r1cs circuit.r1cs: the reference's fake circuit-specific trusted setup (cli/cli_main.nim:184-193,
@@ -17,6 +17,11 @@
 //
 // --table-stride S: a lean key -- window tables for every S-th window only (g16_pkey_create_zkey_lean: about 1 / S of
 // the HBM, more bucket reduction per proof, the same proof).
+//
+// --audit-key: for a key from a third party.  Before anything of the key is uploaded for proving, g16_key_audit checks
+// every section of it (canonical encodings, curve membership, the order-r subgroup for the G2 points, coefficient values
+// < r, and pointsB1 ~ pointsB2, beta1 ~ beta2, delta1 ~ delta2; the multipliers of the batched relation are drawn here from
+// std::random_device).  Findings are printed one per line; a key that fails gives exit code 2 and no proof.
 //
 // --gpus d0,d1,...: the proof sharded over those devices through the device group of the C ABI (g16_group_*: one host
 // thread per device inside the library; the reference's Taskpool shape, msm.nim:96-122).  A device may repeat.
@@ -95,11 +100,30 @@ struct SetupKey {
   }
 };
 
+// the first finding per section and check, the failed relations, the spec points at infinity
+void print_report(const g16_key_report& r) {
+  static const char* sec[G16_AUDIT_SECTIONS] = {"alpha1",   "beta1",    "delta1",   "beta2",    "gamma2",   "delta2", "pointsIC",
+                                                "pointsA1", "pointsB1", "pointsB2", "pointsC1", "pointsH1", "coeffs"};
+  static const char* what[3] = {"is not a canonical encoding", "is not on the curve", "is not in the order-r subgroup"};
+  static const char* rel[3] = {"pointsB1~pointsB2", "beta1~beta2", "delta1~delta2"};
+  for (int s = 0; s < G16_AUDIT_SECTIONS; ++s)
+    for (int k = 0; k < 3; ++k)
+      if (r.bad_count[s][k]) {
+        printf("  %s[%zu] %s", sec[s], r.first_bad[s][k], what[k]);
+        if (r.bad_count[s][k] > 1) printf(" (and %zu more)", r.bad_count[s][k] - 1);
+        printf("\n");
+      }
+  for (int k = 0; k < 3; ++k)
+    if (r.relation[k] == 0) printf("  %s: not the same multiples of the two generators\n", rel[k]);
+  for (int s = 0; s < 6; ++s)
+    if (r.spec_infinity >> s & 1) printf("  %s is the point at infinity\n", sec[s]);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
   const char *zpath = nullptr, *wpath = nullptr, *rpath = nullptr, *opath = "proof.json", *ipath = "public.json";
-  bool nomask = false, verify = false, timing = false, setup = false;
+  bool nomask = false, verify = false, timing = false, setup = false, audit = false;
   uint64_t toxic_seed = 0;
   std::vector<int32_t> gpus;
   uint32_t table_stride = 0;
@@ -124,6 +148,7 @@ int main(int argc, char** argv) {
     else if (a == "-n" || a == "--nomask") nomask = true;   // cli_main.nim -n
     else if (a == "-y" || a == "--verify") verify = true;   // cli_main.nim -y
     else if (a == "-t" || a == "--time") timing = true;     // cli_main.nim -t
+    else if (a == "--audit-key") audit = true;
     else if (a == "--gpus") {
       for (const char* q = next(); *q;) {
         char* end = nullptr;
@@ -140,7 +165,7 @@ int main(int argc, char** argv) {
       if (end == q || *end || s < 0 || s > 255) die("--table-stride takes a number from 0 to 255");
       table_stride = (uint32_t)s;
     }
-    else die("unknown option " + a + "\nusage: g16prove -z circuit.zkey -w witness.wtns [-o proof.json] [-i public.json] [-n] [-y] [-t] [--gpus 0,1,...] [--table-stride S]\n       g16prove -u -r circuit.r1cs [--toxic-seed N] -w witness.wtns ...");
+    else die("unknown option " + a + "\nusage: g16prove -z circuit.zkey -w witness.wtns [-o proof.json] [-i public.json] [-n] [-y] [-t] [--gpus 0,1,...] [--table-stride S] [--audit-key]\n       g16prove -u -r circuit.r1cs [--toxic-seed N] -w witness.wtns ...");
   }
   if (setup ? (!rpath || zpath || !wpath) : (!zpath || rpath || !wpath))
     die("usage: g16prove -z circuit.zkey -w witness.wtns [-o proof.json] [-i public.json] [-n] [-y] [-t]\n"
@@ -162,6 +187,36 @@ int main(int argc, char** argv) {
   WtnsFile wf(wpath, nvars);
   const uint8_t* wvals = wf.values;
   const double t1 = now();
+
+  if (audit) {   // before g16_pkey_create*: nothing of an unfit key is registered
+    g16_pkey_desc ad = setup ? skp->desc() : zfp->desc(true);
+    g16_vkey_desc vd;
+    vd.npubs = npubs;
+    if (setup) {
+      vd.alpha1 = &skp->spec[0], vd.beta2 = &skp->spec[192], vd.gamma2 = &skp->spec[320], vd.delta2 = &skp->spec[448];
+      vd.pointsIC = skp->ic.data();
+    } else {
+      vd.alpha1 = zfp->alpha1, vd.beta2 = zfp->beta2, vd.gamma2 = zfp->gamma2, vd.delta2 = zfp->delta2, vd.pointsIC = zfp->ic;
+    }
+    std::vector<uint64_t> zs(2 * (size_t)nvars);   // one non-zero 128-bit multiplier per wire
+    std::random_device rd;
+    for (size_t i = 0; i < zs.size(); i += 2)
+      do {
+        zs[i] = ((uint64_t)rd() << 32) | rd();
+        zs[i + 1] = ((uint64_t)rd() << 32) | rd();
+      } while (!(zs[i] | zs[i + 1]));
+    g16_key_report rep;
+    chk(g16_key_audit(ctx, &ad, &vd, setup ? nullptr : zfp->section4, setup ? 0 : zfp->section4_len, zs.data(), &rep),
+        "g16_key_audit");
+    if (rep.failed) {
+      printf("key audit: FAILED\n");
+      print_report(rep);
+      g16_ctx_destroy(ctx);
+      return 2;
+    }
+    printf("key audit: ok\n");
+  }
+  const double t1a = now();
 
   // one GPU and a .zkey: the coefficient section goes to the library as it lies in the file
   g16_pkey_desc d = setup ? skp->desc() : zfp->desc(gpus.empty());
@@ -239,8 +294,9 @@ int main(int argc, char** argv) {
     if (st != 1) return 1;
   }
   if (timing)
-    printf("%s %.3fs | key upload + tables %.3fs | proof %.3fs\n", setup ? "parsing + setup" : "parsing", t1 - t0, t2 - t1,
+    printf("%s %.3fs | key upload + tables %.3fs | proof %.3fs\n", setup ? "parsing + setup" : "parsing", t1 - t0, t2 - t1a,
            t3 - t2);
+  if (timing && audit) printf("key audit %.3fs\n", t1a - t1);
   g16_pkey_destroy(key);
   g16_group_pkey_destroy(gkey);
   g16_group_destroy(grp);

@@ -11,6 +11,9 @@ snarkjs, ptau or network).  Given external files the checked recipe is
       -y  the proof is verified on the GPU against the key's own verification key (verifier.nim:31-52)
       -t  phase timings, and the fraction of points at infinity per ProverPoints array together with whether the
           library put A1 / B1+B2 on compacted entry lists (g16_pkey_inf_counts)
+      --audit  for a key from a third party: before it is loaded, every section is audited on the GPU (auditZKey:
+          canonical encodings, curve, order-r subgroup, coefficient values, the B1/B2, beta and delta relations);
+          findings are printed, and a key that fails gives exit code 2 and no proof
     snarkjs groth16 verify verification_key.json public.json proof.json        # offline, wherever snarkjs exists
 (the reference's own recipe: groth16/example/prove.sh:52-59)."""
 import argparse
@@ -39,6 +42,8 @@ def main():
     ap.add_argument("-k", "--vkey", default=None, help="also write the verification key as snarkjs verification_key.json")
     ap.add_argument("-c", "--check", action="store_true",
                     help="check every key point against its curve equation on the GPU while parsing")
+    ap.add_argument("--audit", action="store_true",
+                    help="audit the key on the GPU before loading it; no proof from a key that fails")
     ap.add_argument("-y", "--verify", action="store_true",
                     help="also verify the proof against the zkey's verification key (cli_main.nim -y)")
     args = ap.parse_args()
@@ -47,6 +52,12 @@ def main():
     t0 = time.time()
     zkey, wtns = parseZKey(args.zkey, check=args.check, ctx=ctx, rawCoeffs=True), parseWitness(args.wtns)
     assert wtns.nvars == zkey.header.nvars, "wrong witness length"        # prover.nim:236
+    if args.audit:
+        from nim_groth16_amd.files import auditZKey
+        report = auditZKey(zkey, ctx)
+        print(report)
+        if not report.ok:
+            raise SystemExit(2)
     t1 = time.time()
     pkey = loadProvingKey(zkey, ctx, table_stride=args.table_stride)
     t2 = time.time()
