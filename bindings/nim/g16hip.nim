@@ -48,6 +48,7 @@ proc g16_prove(ctx: ptr G16Ctx, key: ptr G16PKey, witness: pointer, flags: uint3
 # points at infinity per ProverPoints array (A1, B1, B2, C1, H1, B1-and-B2) and whether A1 / B1+B2 run on compacted
 # entry lists: snarkjs keys hold (0,0) for every wire absent from a matrix (curves.nim:95-107 accepts them)
 proc g16_pkey_inf_counts(key: ptr G16PKey, res: ptr array[8, csize_t]): int32 {.importc, header: "g16hip.h".}
+proc g16_pkey_b1_fold(key: ptr G16PKey, res: ptr array[3, csize_t]): int32 {.importc, header: "g16hip.h".}
 
 var gctx: ptr G16Ctx
 

@@ -279,6 +279,17 @@ void g16_pkey_destroy(g16_pkey* key);
  * whose B1 AND B2 points are both (0,0); out[6] / out[7] = 1 if A1 / B1+B2 run on compacted entry lists (their own
  * arrangement of the witness without those wires; sets below the G16_INF_COMPACT threshold share one arrangement). */
 int32_t g16_pkey_inf_counts(const g16_pkey* key, size_t out[8]);
+/* pointsB1 folded into pointsA1.  Both sets meet the same scalars, so MSM(w, B1) = MSM(w, A1) + MSM(w, B1 - A1), and the
+ * difference is the point at infinity for every wire whose columns of A and B coincide (squarings, boolean checks).  At
+ * key creation the library counts, over the key's WHOLE wire range, live_b1 = pointsB1 entries that are not (0,0) and
+ * live_delta = wires whose two points differ, and keeps in place of pointsB1
+ *   1: nothing, if live_delta = 0;
+ *   2: the differences, if live_delta * 100 <= live_b1 * (100 - G16_INF_COMPACT) -- and, where pointsB1 holds enough
+ *      (0,0) entries to run on a compacted entry list, only if live_delta * 64 <= live_b1: the differences ride the entry
+ *      list of all wires, where 64 neighbours at infinity are skipped together;
+ *   0: pointsB1 as it is, otherwise and always under G16_B1_FOLD=0.
+ * out[0] = that form, out[1] = live_b1, out[2] = live_delta.  Proofs are the same bytes in every form. */
+int32_t g16_pkey_b1_fold(const g16_pkey* key, size_t out[3]);
 /* witness: nvars Fr values (flags: G16_SCALARS_MONT for Nim seq[Fr], G16_SCALARS_STD for raw .wtns,
  * | G16_SCALARS_DEVICE); mask_r / mask_s: Fr Montgomery (Mask, prover.nim:210-213), NULL = zero
  * (generateProofWithTrivialMask, prover.nim:308-310). */
@@ -289,7 +300,8 @@ int32_t g16_prove(g16_ctx* ctx, const g16_pkey* key, const void* witness, uint32
  *      writes G16_PARTIALS_BYTES = 768 bytes: XYZZ accumulators A1 | B1 | B2 (256 B) | H1 | C1.  The record is
  *      opaque: accumulators are not canonical (the addition order inside a bucket is not fixed), and when the C1 and
  *      H1 sets share their bucket set the H1 slot holds H1 + C1 and the C1 slot infinity (pi_c needs only the sum,
- *      prover.nim:301-302).  Only g16_prove_combine gives records a meaning; it accepts any mix of them.
+ *      prover.nim:301-302); for a key with pointsB1 folded into pointsA1 (g16_pkey_b1_fold) the B1 slot holds the
+ *      MSM over the differences B1 - A1 and g16_prove_combine adds the A1 slots to it.  Only g16_prove_combine gives records a meaning; it accepts any mix of them.
  *      flags: G16_SCALARS_MONT/STD | G16_SCALARS_DEVICE (witness in HBM) | G16_OUT_DEVICE (output in HBM).
  *  g16_prove_combine: `count` gathered records (rank order; e.g. from an RCCL all-gather) are summed per MSM
  *      -- the `res += sync pending[k]` of msm.nim:117-119 across GPUs -- and the mask algebra of

@@ -33,6 +33,7 @@ SYMBOLS = [
     "g16_pkey_create_zkey_lean", "g16_group_pkey_create_lean",
     "g16_setup_log2_domain", "g16_fake_setup", "g16_lagrange_fr", "g16_powers_fr",
     "g16_points_audit_g1", "g16_points_audit_g2", "g16_points_pairs_check", "g16_key_audit",
+    "g16_pkey_b1_fold",
 ]
 VERIFY_SUBGROUP = 16
 GT_BYTES = 384
@@ -223,6 +224,7 @@ def load_library():
     lib.g16_points_inf_count.argtypes = [vp]
     lib.g16_points_inf_count.restype = sz
     lib.g16_pkey_inf_counts.argtypes = [vp, ctypes.POINTER(sz)]
+    lib.g16_pkey_b1_fold.argtypes = [vp, ctypes.POINTER(sz)]
     lib.g16_points_info.argtypes = [vp, ctypes.POINTER(u32), ctypes.POINTER(u32)]
     lib.g16_msm_points.argtypes = [vp, vp, vp, u32, vp]
     lib.g16_points_check_g1.argtypes = [vp, vp, sz, ctypes.POINTER(sz)]
@@ -677,6 +679,14 @@ class ProvingKey:
         v = list(out)
         return {"A1": v[0], "B1": v[1], "B2": v[2], "C1": v[3], "H1": v[4], "B1_and_B2": v[5],
                 "compact_A": bool(v[6]), "compact_B": bool(v[7])}
+
+    def b1_fold(self) -> dict:
+        """what the key keeps in place of pointsB1 (g16_pkey_b1_fold): form "PLAIN" (pointsB1), "EMPTY" (nothing: every
+        wire's B1 point equals its A1 point) or "DELTA" (the differences B1 - A1), and the two counts over the whole
+        wire range it was decided from"""
+        out = (ctypes.c_size_t * 3)()
+        self.ctx._check(self.ctx._lib.g16_pkey_b1_fold(self._h, out))
+        return {"form": ("PLAIN", "EMPTY", "DELTA")[out[0]], "live_b1": out[1], "live_delta": out[2]}
 
     def abc_info(self) -> dict:
         """shape of the A / B matrices as buildABC runs them (g16_pkey_abc_info)"""

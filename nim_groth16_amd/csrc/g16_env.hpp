@@ -38,4 +38,5 @@ struct G16Env {
                                   // come from a small set (spmv.hip: value dictionary)
   int g2_first = -1;              // G16_G2_FIRST = 0 | 1 | 2: A1 and B1 (2: C1 too) accumulate after B2 (unset: 1 for small shards,
                                   // proof_plan.hpp)
+  int b1_fold = 1;                // G16_B1_FOLD=0: every key keeps pointsB1 as it is (b1_fold_form, proof_plan.hpp: always PLAIN)
 };

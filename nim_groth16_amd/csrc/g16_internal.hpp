@@ -223,7 +223,10 @@ int32_t g16_msm_sort(g16_ctx* ctx, hipStream_t stream, const void* d_scalars, ui
 struct g16_msm_run {
   const g16_ctx::MsmSort* sort;
   g16_ctx::Buf* acc;            // workspace of this job (bucket sums first: see g16_msm_partial_ptr)
-  const void* d_points;         // the tables of a registered set, or reduced-radix entries (to29_device)
+  const void* d_points;         // the tables of a registered set, or reduced-radix entries (to29_device); null = a set
+                                // that is infinity throughout: msm_accum (msm.cuh) then writes infinity to every bucket
+                                // sum and reads no entry.  It does NOT carry `init_partial` over in that case, so a run
+                                // with a null table must have a null init_partial (g16_msm_batch refuses the pair)
   void* d_out_aff;              // either may be null
   void* d_out_acc;
   const void* init_partial;

@@ -31,6 +31,7 @@ static G16Env read_env() {
   if (const char* v = getenv("G16_RED_CHUNK")) e.red_chunk = atoi(v) == 2 || atoi(v) == 4 || atoi(v) == 8 || atoi(v) == 16 ? atoi(v) : 0;
   if (const char* v = getenv("G16_TAIL_QUAD")) e.tail_quad = v[0] != '0';
   if (const char* v = getenv("G16_G2_FIRST")) e.g2_first = v[0] == '2' ? 2 : v[0] != '0';
+  if (const char* v = getenv("G16_B1_FOLD")) e.b1_fold = v[0] != '0';
   if (const char* v = getenv("G16_MTAB")) e.mtab = v[0] == '1' ? 1 : 2;
   if (const char* v = getenv("G16_NTT_TILE")) e.ntt_tile = atoi(v) == 1024 ? 1024 : atoi(v) == 4096 ? 4096 : 2048;
   if (const char* v = getenv("G16_MSM_SORT")) e.msm_sort = v[0];

@@ -606,6 +606,11 @@ msm_accum(const MsmBatch<C> B, MsmParams P, unsigned long long* __restrict__ clk
     s = 0;
     slot = b;
   }
+  // no table at all (a key whose pointsB1 equals pointsA1 wire for wire, b1_fold_form): every bucket sum is infinity
+  if (points == nullptr) {
+    J.partial[slot] = E::acc_inf();
+    return;
+  }
   uint32_t beg = offset[b], end = offset[b + 1];
   beg += s * P.seg;
   if (end > beg + P.seg) end = beg + P.seg;

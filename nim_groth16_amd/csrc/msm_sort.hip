@@ -132,6 +132,12 @@ static int32_t msm_batch(g16_ctx* ctx, hipStream_t st, const g16_msm_run* runs, 
 }
 int32_t g16_msm_batch(g16_ctx* ctx, hipStream_t stream, int group, const g16_msm_run* runs, int n_accum, int n_tail,
                       hipEvent_t after_heavy) {
+  // a null table stands for a set at infinity throughout, and msm_accum then drops the sums it was given to continue
+  for (int i = 0; i < n_accum; ++i)
+    if (!runs[i].d_points && runs[i].init_partial) {
+      ctx->err = "an MSM run without a table cannot continue another run's bucket sums";
+      return G16_EINVAL;
+    }
   return group == 1 ? msm_batch<G1>(ctx, stream, runs, n_accum, n_tail, after_heavy)
                     : msm_batch<G2>(ctx, stream, runs, n_accum, n_tail, after_heavy);
 }

@@ -11,6 +11,7 @@
 #include <new>
 
 #include "g16_internal.hpp"
+#include "b1_fold.cuh"
 #include "host_curve.hpp"   // the host-side O(1) curve algebra of the combine step (ec.cuh, host_ff64.hpp)
 
 using namespace g16;
@@ -39,6 +40,12 @@ struct g16_pkey {
   const uint32_t* liveA = nullptr;   // not owned: A1's own bitmap
   DevMem<uint32_t> liveB;            // owned (the union), or empty
   size_t deadB = 0;               // wires whose B1 AND B2 points are both (0,0)
+  // pointsB1 folded into pointsA1 (b1_fold_form, proof_plan.hpp).  B1_DELTA: `B1` holds the differences B1_i - A1_i
+  // in place of pointsB1; B1_EMPTY: there is no live difference and the B1 accumulation runs against no table.  In both
+  // the record's B1 slot holds MSM(w, difference) and the combine kernel adds the A1 slots to it.
+  int b1_form = B1_PLAIN;
+  size_t b1_inf = 0;              // (0,0) points of pointsB1 itself in this key's wire range
+  size_t live_b1 = 0, live_delta = 0;   // over the WHOLE wire range: what the form was decided from
 };
 
 extern "C" void g16_pkey_destroy(g16_pkey* k) {
@@ -65,8 +72,17 @@ extern "C" int32_t g16_pkey_inf_counts(const g16_pkey* k, size_t out[8]) {
   // public wires 0 .. npubs of this shard's wire range: their C1 slots are this library's padding, not key points
   const size_t pub_end = std::min<size_t>(k->w_hi, (size_t)k->npubs + 1);
   const size_t pad = pub_end > k->w_lo ? pub_end - k->w_lo : 0;
-  out[0] = k->A1->n_inf, out[1] = k->B1->n_inf, out[2] = k->B2->n_inf, out[3] = k->C1->n_inf - pad, out[4] = k->H1->n_inf;
+  out[0] = k->A1->n_inf, out[1] = k->b1_inf, out[2] = k->B2->n_inf, out[3] = k->C1->n_inf - pad, out[4] = k->H1->n_inf;
   out[5] = k->deadB, out[6] = k->liveA ? 1 : 0, out[7] = k->liveB ? 1 : 0;
+  return G16_OK;
+}
+
+// out[0] = the key's B1Form (0: pointsB1 as it is, 1: no live difference, 2: the differences in its place), out[1] =
+// pointsB1 entries that are not (0,0), out[2] = wires whose pointsB1 and pointsA1 entries differ -- both counted over the
+// whole wire range of the key, whichever shard this is
+extern "C" int32_t g16_pkey_b1_fold(const g16_pkey* k, size_t out[3]) {
+  if (!k || !out) return G16_EINVAL;
+  out[0] = (size_t)k->b1_form, out[1] = k->live_b1, out[2] = k->live_delta;
   return G16_OK;
 }
 
@@ -88,6 +104,38 @@ static inline uint32_t rd32(const unsigned char* p) {
   uint32_t v;
   memcpy(&v, p, 4);   // section 4 is not 4-byte aligned past its first entry
   return v;
+}
+
+// ---- pointsB1 against pointsA1 (key creation; b1_fold_form, proof_plan.hpp) --------------------------------------------
+// cnt[0] += #{B1_i != (0,0)}, cnt[1] += #{B1_i != A1_i}: equality of the 64 bytes, which for the canonical encodings a key
+// holds is equality of the points
+static __global__ void __launch_bounds__(256) b1_compare_kernel(const uint4* __restrict__ a1, const uint4* __restrict__ b1,
+                                                                uint32_t n, uint32_t* __restrict__ cnt) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  bool live = false, differs = false;
+  if (i < n) {
+    uint32_t any = 0, diff = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const uint4 a = a1[(size_t)i * 4 + q], b = b1[(size_t)i * 4 + q];
+      any |= b.x | b.y | b.z | b.w;
+      diff |= (a.x ^ b.x) | (a.y ^ b.y) | (a.z ^ b.z) | (a.w ^ b.w);
+    }
+    live = any != 0, differs = diff != 0;
+  }
+  const uint32_t nl = (uint32_t)__popcll(__ballot(live)), nd = (uint32_t)__popcll(__ballot(differs));
+  if ((threadIdx.x & 63) == 0) {
+    if (nl) atomicAdd(&cnt[0], nl);
+    if (nd) atomicAdd(&cnt[1], nd);
+  }
+}
+// b1[i] <- b1[i] - a1[i], exact and in the canonical affine form (b1_fold.cuh).  One thread per wire with an inversion of
+// its own: this runs once per key.
+static __global__ void __launch_bounds__(256) b1_delta_kernel(const g1_aff* __restrict__ a1, g1_aff* __restrict__ b1,
+                                                              uint32_t n) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  b1[i] = point_difference<G1>(b1[i], a1[i]);
 }
 
 // table_stride: the stride of all five point sets (g16_points_register_*_lean; 0 / 1: a table per window)
@@ -136,14 +184,83 @@ static int32_t pkey_create(g16_ctx* ctx, const g16_pkey_desc* d, const CoeffSour
     if (wI > d->npubs) memcpy(&c1pad[(wI - k->w_lo) * 64], (const char*)d->pointsC1 + 64 * (wI - d->npubs - 1), 64);
   const uint32_t ts = table_stride;
   if ((rc = g16_points_register_g1_lean(ctx, (const char*)d->pointsA1 + 64 * k->w_lo, k->w_hi - k->w_lo, ts, &k->A1))) return rc;
-  if ((rc = g16_points_register_g1_lean(ctx, (const char*)d->pointsB1 + 64 * k->w_lo, k->w_hi - k->w_lo, ts, &k->B1))) return rc;
+  {   // pointsB1, or what stands in for it (b1_fold_form)
+    const size_t nv = d->nvars, nw = k->w_hi - k->w_lo;
+    SyncOnExit sync{ctx->stream};
+    uint32_t cnt[2] = {0, 0};
+    if (g16_env().b1_fold) {
+      // the form is decided over every wire, whichever shard this is: the two whole arrays pass through a pair of small
+      // buffers, a chunk at a time, so that the comparison costs a key no device memory worth speaking of
+      constexpr size_t CHUNK = size_t(1) << 16;
+      const size_t step = std::min(nv, CHUNK);
+      DevMem<g1_aff> c_a1, c_b1;
+      SyncOnExit sync_chunks{ctx->stream};
+      if ((rc = ensure(ctx, ctx->stage_o, 2048))) return rc;
+      uint32_t* d_cnt = (uint32_t*)ctx->stage_o.p();
+      HIPCHK(ctx, dev_alloc(c_a1, step * sizeof(g1_aff)));
+      HIPCHK(ctx, dev_alloc(c_b1, step * sizeof(g1_aff)));
+      HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, 8, ctx->stream));
+      for (size_t lo = 0; lo < nv; lo += step) {
+        const size_t m = std::min(step, nv - lo);
+        HIPCHK(ctx, hipMemcpyAsync(c_a1.get(), (const char*)d->pointsA1 + 64 * lo, m * 64, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(c_b1.get(), (const char*)d->pointsB1 + 64 * lo, m * 64, hipMemcpyHostToDevice, ctx->stream));
+        // (key creation: not a kernel of a proof, and not in the profile report)
+        hipLaunchKernelGGL(b1_compare_kernel, dim3((uint32_t)((m + 255) / 256)), dim3(256), 0, ctx->stream,
+                           (const uint4*)c_a1.get(), (const uint4*)c_b1.get(), (uint32_t)m, d_cnt);
+        HIPCHK(ctx, hipGetLastError());
+      }
+      HIPCHK(ctx, hipMemcpyAsync(cnt, d_cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    k->live_b1 = cnt[0], k->live_delta = cnt[1];
+    k->b1_form = b1_fold_form(cnt[0], cnt[1], nv, g16_env());
+    if (k->b1_form == B1_DELTA && nw) {
+      // this shard's range of the two arrays: the differences are built in place of the B1 points and registered from
+      // the device (both arrays are gone before B2's tables are allocated)
+      DevMem<g1_aff> d_a1, d_b1;
+      SyncOnExit sync_arrays{ctx->stream};
+      HIPCHK(ctx, dev_alloc(d_a1, nw * sizeof(g1_aff)));
+      HIPCHK(ctx, dev_alloc(d_b1, nw * sizeof(g1_aff)));
+      HIPCHK(ctx, hipMemcpyAsync(d_a1.get(), (const char*)d->pointsA1 + 64 * k->w_lo, nw * 64, hipMemcpyHostToDevice, ctx->stream));
+      HIPCHK(ctx, hipMemcpyAsync(d_b1.get(), (const char*)d->pointsB1 + 64 * k->w_lo, nw * 64, hipMemcpyHostToDevice, ctx->stream));
+      // (0,0) points of pointsB1 itself in this range, before the differences replace them
+      uint32_t n_inf = 0;
+      DevMem<uint32_t> scratch_live;
+      uint32_t* d_cnt = (uint32_t*)ctx->stage_o.p();
+      HIPCHK(ctx, dev_alloc(scratch_live, ((nw + 31) / 32 + 1) * 4));
+      HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, 4, ctx->stream));
+      if ((rc = live_bitmap_device<G1>(ctx, d_b1.get(), nw, scratch_live.get(), d_cnt))) return rc;
+      HIPCHK(ctx, hipMemcpyAsync(&n_inf, d_cnt, 4, hipMemcpyDeviceToHost, ctx->stream));
+      hipLaunchKernelGGL(b1_delta_kernel, dim3((uint32_t)((nw + 255) / 256)), dim3(256), 0, ctx->stream,
+                         (const g1_aff*)d_a1.get(), d_b1.get(), (uint32_t)nw);
+      HIPCHK(ctx, hipGetLastError());
+      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+      k->b1_inf = n_inf;
+      if ((rc = g16_points_register_g1_lean_dev(ctx, d_b1.get(), nw, ts, &k->B1))) return rc;
+    } else {
+      // B1_EMPTY keeps pointsB1 registered in full although no proof reads its tables (run_plan hands the B1 run no
+      // table): the set still gives the key its B1 counts, bitmap and window configuration, and the reports of a key's
+      // table bytes stay what they were.  That is memory and key-creation time spent for nothing on such a key.
+      if ((rc = g16_points_register_g1_lean(ctx, (const char*)d->pointsB1 + 64 * k->w_lo, nw, ts, &k->B1))) return rc;
+      k->b1_inf = k->B1->n_inf;
+    }
+  }
   if ((rc = g16_points_register_g2_lean(ctx, (const char*)d->pointsB2 + 128 * k->w_lo, k->w_hi - k->w_lo, ts, &k->B2))) return rc;
   if ((rc = g16_points_register_g1_lean(ctx, c1pad.data(), k->w_hi - k->w_lo, ts, &k->C1))) return rc;
   if ((rc = g16_points_register_g1_lean(ctx, (const char*)d->pointsH1 + 64 * k->h_lo, k->h_hi - k->h_lo, ts, &k->H1))) return rc;
   {   // sparse sets get their own entry lists (see g16_pkey)
     const size_t nw = k->w_hi - k->w_lo;
     k->liveA = g16_points_live_if_sparse(k->A1);
-    if (nw && k->B1->d_live && k->B2->d_live) {
+    if (nw && k->b1_form == B1_DELTA && k->B2->d_live) {
+      // B1_i = (0,0) <=> B2_i = (0,0): the union of the two bitmaps is B2's own, and only B2 reads that arrangement
+      k->deadB = k->B2->n_inf;
+      if (points_sparse(k->deadB, nw, g16_env())) {
+        const size_t words = (nw + 31) / 32 + 1;
+        HIPCHK(ctx, dev_alloc(k->liveB, words * 4));
+        HIPCHK(ctx, hipMemcpyAsync(k->liveB.get(), k->B2->d_live.get(), words * 4, hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+      }
+    } else if (nw && k->B1->d_live && k->B2->d_live) {
       uint32_t dead = 0;
       if ((rc = ensure(ctx, ctx->stage_o, 2048))) return rc;
       uint32_t* d_cnt = (uint32_t*)ctx->stage_o.p();
@@ -257,7 +374,7 @@ static constexpr size_t PART_A = 0, PART_B1 = 128, PART_B2 = 256, PART_H = 512, 
 // ---- a proof's launch sequence: the plan (proof_plan.hpp) decides, run_plan issues ------------------------------
 static ProofShape proof_shape(const g16_pkey* k) {
   return ProofShape{k->w_hi - k->w_lo, k->h_hi - k->h_lo, k->log2n, k->liveA != nullptr, (bool)k->liveB,
-                    k->C1->cfg() == k->H1->cfg()};
+                    k->C1->cfg() == k->H1->cfg(), k->b1_form};
 }
 
 // what the steps of one entry point work on
@@ -293,7 +410,9 @@ static int32_t run_plan(g16_ctx* ctx, const g16_pkey* k, ProofEntry entry, uint3
   const g16_points* const sets[RUN_COUNT] = {k->A1, k->B1, k->C1, k->B2, k->H1};
   g16_msm_run runs[RUN_COUNT] = {
       {&ctx->sort[plan.sort_a], &L[0].acc, k->A1->d_tables.get(), nullptr, slots + PART_A, nullptr},
-      {&ctx->sort[plan.sort_b], &L[2].acc, k->B1->d_tables.get(), nullptr, slots + PART_B1, nullptr},
+      // (B1_EMPTY: no table -- msm_accum leaves infinity in every bucket and the tail kernels take their early-outs)
+      {&ctx->sort[plan.sort_b1], &L[2].acc, k->b1_form == B1_EMPTY ? nullptr : k->B1->d_tables.get(), nullptr,
+       slots + PART_B1, nullptr},
       {&ctx->sort[SORT_W], &L[3].acc, k->C1->d_tables.get(), nullptr, slots + PART_C, nullptr},
       {&ctx->sort[plan.sort_b], &L[1].acc, k->B2->d_tables.get(), nullptr, slots + PART_B2, nullptr},
       {&ctx->sort[SORT_H], &L[4].acc, k->H1->d_tables.get(), nullptr, slots + PART_H, nullptr}};
@@ -419,7 +538,8 @@ extern "C" int32_t g16_prove_partials_end(g16_ctx* ctx, const g16_pkey* k, const
 
 // one workgroup per MSM: res = sum over ranks of that MSM's partial, then canonical affine
 // (`res += sync pending[k]`, msm.nim:117-119, across GPUs instead of threads)
-static __global__ void prove_combine_kernel(const unsigned char* __restrict__ gathered, uint32_t count,
+// fold_b1: the B1 slots hold MSM(w, B1 - A1) (a key with pointsB1 folded into pointsA1): B1 = the A1 slots + the B1 slots
+static __global__ void prove_combine_kernel(const unsigned char* __restrict__ gathered, uint32_t count, uint32_t fold_b1,
                                             unsigned char* __restrict__ out) {
   if (threadIdx.x != 0) return;
   const uint32_t b = blockIdx.x;
@@ -432,6 +552,8 @@ static __global__ void prove_combine_kernel(const unsigned char* __restrict__ ga
     const size_t dst = b == 0 ? 0 : b == 1 ? 64 : b == 3 ? 256 : 320;
     g1_acc r = G1::acc_inf();
     for (uint32_t i = 0; i < count; ++i) G1::add(r, *(const g1_acc*)(gathered + (size_t)i * PART_BYTES + src));
+    if (b == 1 && fold_b1)
+      for (uint32_t i = 0; i < count; ++i) G1::add(r, *(const g1_acc*)(gathered + (size_t)i * PART_BYTES + PART_A));
     *(g1_aff*)(out + dst) = G1::to_affine(r);
   }
 }
@@ -454,7 +576,7 @@ int32_t g16_combine_enqueue(g16_ctx* ctx, const g16_pkey* k, const void* partial
                              ctx->stream));
   unsigned char* d_res = (unsigned char*)ctx->stage_o.p() + 1024;
   KLAUNCH(ctx, "prove_combine", prove_combine_kernel, 5, 64, 0, (const unsigned char*)ctx->stage_p.p(), (uint32_t)count,
-          d_res);
+          k->b1_form != B1_PLAIN ? 1u : 0u, d_res);
 
   // Everything that depends on the mask and the key alone is computed while the GPU works -- in g16_prove that is the
   // whole proof, which is enqueued without a host wait (host_curve.hpp: host_combine_pre)
