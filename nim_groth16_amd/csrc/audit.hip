@@ -74,7 +74,8 @@ int32_t points_audit(g16_ctx* ctx, const void* points, size_t n, size_t first_ba
   }
   CTX_ENTER(ctx);
   int32_t rc;
-  if ((rc = ensure(ctx, ctx->stage_o, 2048))) return rc;
+  static_assert(sizeof(AuditCounts) <= STAGE_O_RESULT_BYTES, "stage_o's result slot");
+  if ((rc = ensure_stage_o(ctx))) return rc;
   AuditCounts h;
   counts_reset(&h, 1);
   AuditCounts* d = (AuditCounts*)ctx->stage_o.p();

@@ -1,4 +1,4 @@
-// pointsB1 folded into pointsA1 (b1_fold_form, proof_plan.hpp): the one point operation of key creation that the fold
+// pointsB1 folded into pointsA1 (b1_fold_form, key_plan.hpp): the one point operation of key creation that the fold
 // needs, in a header of its own so that the CPU test shim runs the very code the device runs.
 #pragma once
 #include "ec.cuh"

@@ -1,5 +1,5 @@
 // The experiment knobs of the library as plain data: no HIP, so that the launch plans that take them as an argument
-// (msm_plan.hpp, proof_plan.hpp) also build with g++ for the CPU tests.
+// (msm_plan.hpp, key_plan.hpp, proof_plan.hpp) also build with g++ for the CPU tests.
 #pragma once
 
 // Experiment knobs (G16_* environment variables), read ONCE per process -- at the first g16_ctx_create -- and never
@@ -16,7 +16,7 @@ struct G16Env {
   char stream_prio[7] = "lhllln";   // G16_STREAM_PRIO  six characters from {h, n, l}
   int red_slice_log2 = 0;  // G16_RED_SLICE    log2 of the chunks per reduce2 slice of a merged bucket set (8..11)
   int inf_compact_pct = 10;   // G16_INF_COMPACT  point sets with at least this percentage of (0,0) points get their own
-                              // entry lists without them (0: always, 101: never); proof_plan.hpp
+                              // entry lists without them (0: always, 101: never); key_plan.hpp
   int r2_width = -1;       // G16_R2_WIDTH  0: reduce2 with 512 / 256-thread workgroups, 1: 128 / 64, 2: 64 / 64; unset:
                            // narrow inside proofs, wide for stand-alone MSMs (msm_stage.cuh)
   int ntt_tile = 2048;            // G16_NTT_TILE = 1024 | 2048 | 4096: NTT workgroup geometry (ntt.cuh)
@@ -38,5 +38,5 @@ struct G16Env {
                                   // come from a small set (spmv.hip: value dictionary)
   int g2_first = -1;              // G16_G2_FIRST = 0 | 1 | 2: A1 and B1 (2: C1 too) accumulate after B2 (unset: 1 for small shards,
                                   // proof_plan.hpp)
-  int b1_fold = 1;                // G16_B1_FOLD=0: every key keeps pointsB1 as it is (b1_fold_form, proof_plan.hpp: always PLAIN)
+  int b1_fold = 1;                // G16_B1_FOLD=0: every key keeps pointsB1 as it is (b1_fold_form, key_plan.hpp: always PLAIN)
 };

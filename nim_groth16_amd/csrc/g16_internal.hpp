@@ -63,7 +63,7 @@ struct g16_ctx {
   Buf stage_s;   // staged scalars (host-pointer API)
   Buf stage_p;   // staged points
   Buf stage_p29; // the same points as reduced-radix entries (one-shot MSMs; registered sets keep their own tables)
-  Buf stage_o;   // result slot
+  Buf stage_o;   // result slot (STAGE_O_*, below)
   Buf ntt_tw;    // twiddle table
   Buf ntt_tmp;   // ping-pong buffers
   Buf coset[2];  // eta^(+-i)/n tables (ntt_make_coset_table)
@@ -151,6 +151,36 @@ inline int32_t ensure(g16_ctx* ctx, g16_ctx::Buf& b, size_t bytes) {
   return G16_OK;
 }
 
+// ---- stage_o: the result slot of a context ------------------------------------------------------------------------------
+// One small buffer, laid out once.  [0, RESULT_BYTES): the result of the call in progress -- a proof's partials record
+// (G16_PARTIALS_BYTES), the sum of a one-shot MSM, the counts of an audit; then the counter words of counted_launch;
+// then the five affine sums the combine kernel writes, which a proof's next record must not overwrite before they
+// have been copied out.
+#define G16_COMBINE_RES_BYTES 384   // the five affine MSM sums A1 | B1 | B2 | H1 | C1 the combine kernel writes
+constexpr size_t STAGE_O_RESULT = 0, STAGE_O_RESULT_BYTES = G16_PARTIALS_BYTES;
+constexpr size_t STAGE_O_COUNTERS = STAGE_O_RESULT + STAGE_O_RESULT_BYTES, STAGE_O_COUNTER_WORDS = 2;
+constexpr size_t STAGE_O_COMBINE = 1024;
+constexpr size_t STAGE_O_BYTES = 2048;
+static_assert(STAGE_O_COUNTERS % 4 == 0 && STAGE_O_COUNTERS + 4 * STAGE_O_COUNTER_WORDS <= STAGE_O_COMBINE &&
+                  STAGE_O_COMBINE % 128 == 0 && STAGE_O_COMBINE + G16_COMBINE_RES_BYTES <= STAGE_O_BYTES,
+              "the pieces of stage_o overlap or do not fit");
+inline int32_t ensure_stage_o(g16_ctx* ctx) { return ensure(ctx, ctx->stage_o, STAGE_O_BYTES); }
+inline char* stage_o_at(g16_ctx* ctx, size_t offset) { return (char*)ctx->stage_o.p() + offset; }
+
+// The one way the host reads a count back from a kernel: `nwords` (<= STAGE_O_COUNTER_WORDS) device words are filled
+// with the byte `fill`, `launch(d_words)` queues on the main stream whatever updates them (an int32_t code: nonzero
+// ends the call), then the words are copied into `words` and the stream is drained.
+template <class Launch>
+inline int32_t counted_launch(g16_ctx* ctx, int fill, uint32_t* words, size_t nwords, Launch&& launch) {
+  if (int32_t rc = ensure_stage_o(ctx)) return rc;
+  uint32_t* d_words = (uint32_t*)stage_o_at(ctx, STAGE_O_COUNTERS);
+  HIPCHK(ctx, hipMemsetAsync(d_words, fill, 4 * nwords, ctx->stream));
+  if (int32_t rc = launch(d_words)) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(words, d_words, 4 * nwords, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return G16_OK;
+}
+
 // ---- profiling helpers ----------------------------------------------------------------------------
 struct ProfScope {
   g16_ctx* ctx;
@@ -207,7 +237,7 @@ struct g16_points {
   size_t n_inf = 0;             // points at infinity in the set
 };
 // the live bitmap of a registered set if it holds enough (0,0) points for its own entry lists to pay (points_sparse,
-// proof_plan.hpp; g16hip.hip)
+// key_plan.hpp; g16hip.hip)
 const uint32_t* g16_points_live_if_sparse(const g16_points* p);
 // the two halves of an MSM: (1) arrange one scalar vector into buckets, (2) accumulate + reduce a point set
 // against that arrangement.  Several point sets may share one sort (same scalars, same n, same c).
@@ -315,11 +345,9 @@ struct g16_combine_pre {
   unsigned char r_std[32], s_std[32];
   unsigned char a_pre[64], b_pre[128], c_pre[64];
 };
-#define G16_COMBINE_RES_BYTES 384   // the five affine MSM sums A1 | B1 | B2 | H1 | C1 the combine kernel writes
 // stage copy + combine kernel on ctx->stream, host algebra, then the 384-byte D2H into res_host (+ event `done`)
 int32_t g16_combine_enqueue(g16_ctx* ctx, const g16_pkey* k, const void* partials, size_t count, uint32_t flags,
                             const void* mask_r, const void* mask_s, void* res_host, hipEvent_t done,
                             g16_combine_pre* pre);
 // the additions and the one joint multiplication on the MSM sums; res_host must be complete
 void g16_combine_finish(const g16_combine_pre* pre, const void* res_host, g16_proof* out);
-void g16_pkey_shape(const g16_pkey* k, int* device, uint32_t* nvars, uint32_t* shard_count);

@@ -245,7 +245,7 @@ static int32_t msm_entry(g16_ctx* ctx, const void* scalars, uint32_t flags, cons
     d_s = ctx->stage_s.p();
     d_p = ctx->stage_p.p();
   }
-  if ((rc = ensure(ctx, ctx->stage_o, 512))) return rc;
+  if ((rc = ensure_stage_o(ctx))) return rc;
   auto* d_aff = partial ? nullptr : (typename C::Aff*)ctx->stage_o.p();
   auto* d_acc = partial ? (typename C::Acc*)ctx->stage_o.p() : nullptr;
   if ((rc = msm_device<C>(ctx, d_s, flags, d_p, n, d_aff, d_acc, 0))) return rc;
@@ -303,12 +303,10 @@ static int32_t points_register(g16_ctx* ctx, const void* points, size_t n, bool 
     // which points are (0,0): snarkjs keys hold the point at infinity for every wire absent from a matrix
     uint32_t n_inf = 0;
     HIPCHK(ctx, dev_alloc(h->d_live, ((n + 31) / 32 + 1) * 4));
-    if ((rc = ensure(ctx, ctx->stage_o, 2048))) return rc;
-    uint32_t* d_cnt = (uint32_t*)ctx->stage_o.p();
-    HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, 4, ctx->stream));
-    if ((rc = live_bitmap_device<C>(ctx, d_src, n, h->d_live.get(), d_cnt))) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(&n_inf, d_cnt, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    rc = counted_launch(ctx, 0, &n_inf, 1, [&](uint32_t* d_n_inf) {
+      return live_bitmap_device<C>(ctx, d_src, n, h->d_live.get(), d_n_inf);
+    });
+    if (rc) return rc;
     h->n_inf = n_inf;
   }
   *out = h.release();
@@ -396,14 +394,12 @@ static int32_t points_check(g16_ctx* ctx, const void* points, size_t n, size_t* 
   constexpr size_t psz = sizeof(typename C::Aff);
   int32_t rc;
   if ((rc = ensure(ctx, ctx->stage_p, n * psz + psz))) return rc;
-  if ((rc = ensure(ctx, ctx->stage_o, 2048))) return rc;
-  uint32_t* d_bad = (uint32_t*)ctx->stage_o.p();
-  HIPCHK(ctx, hipMemsetAsync(d_bad, 0xff, 4, ctx->stream));
-  if (n) HIPCHK(ctx, hipMemcpyAsync(ctx->stage_p.p(), points, n * psz, hipMemcpyHostToDevice, ctx->stream));
-  if ((rc = on_curve_device<C>(ctx, ctx->stage_p.p(), n, d_bad))) return rc;
   uint32_t bad = 0;
-  HIPCHK(ctx, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  rc = counted_launch(ctx, 0xff, &bad, 1, [&](uint32_t* d_bad) -> int32_t {
+    if (n) HIPCHK(ctx, hipMemcpyAsync(ctx->stage_p.p(), points, n * psz, hipMemcpyHostToDevice, ctx->stream));
+    return on_curve_device<C>(ctx, ctx->stage_p.p(), n, d_bad);
+  });
+  if (rc) return rc;
   *first_bad = bad == 0xffffffffu ? (size_t)-1 : (size_t)bad;
   return G16_OK;
 }
@@ -463,7 +459,7 @@ static int32_t msm_points(g16_ctx* ctx, const g16_points* pts, const void* scala
     HIPCHK(ctx, hipMemcpyAsync(ctx->stage_s.p(), scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
     d_s = ctx->stage_s.p();
   }
-  if ((rc = ensure(ctx, ctx->stage_o, 512))) return rc;
+  if ((rc = ensure_stage_o(ctx))) return rc;
   void* d_aff = partial ? nullptr : ctx->stage_o.p();
   void* d_acc = partial ? ctx->stage_o.p() : nullptr;
   const uint32_t* live = g16_points_live_if_sparse(pts);
@@ -515,7 +511,7 @@ static int32_t sum_partials(g16_ctx* ctx, const void* xyzz, size_t count, void* 
   int32_t rc;
   size_t bytes = count * sizeof(typename C::Acc);
   if ((rc = ensure(ctx, ctx->stage_p, bytes + 256))) return rc;
-  if ((rc = ensure(ctx, ctx->stage_o, 512))) return rc;
+  if ((rc = ensure_stage_o(ctx))) return rc;
   if (count) HIPCHK(ctx, hipMemcpyAsync(ctx->stage_p.p(), xyzz, bytes, hipMemcpyHostToDevice, ctx->stream));
   if ((rc = sum_partials_device<C>(ctx, ctx->stage_p.p(), (uint32_t)count, ctx->stage_o.p()))) return rc;
   HIPCHK(ctx, hipMemcpyAsync(out, ctx->stage_o.p(), sizeof(typename C::Aff), hipMemcpyDeviceToHost, ctx->stream));

@@ -14,7 +14,7 @@
 // The same device may appear several times in `devices` (tests: every "device" = 0 on a one-GPU box).
 #include <thread>
 
-#include "g16_internal.hpp"
+#include "pkey.hpp"
 
 namespace {
 struct Member {
@@ -37,7 +37,6 @@ struct g16_group_pkey {
   std::vector<g16_pkey*> key;        // shard g on member g
   std::vector<DevMem<>> task_out;    // member g: its owned coset vectors (owned x n Fr), HBM of devices[g]
   std::vector<DevMem<>> slices;      // member g: 3 x (h_hi - h_lo) Fr, HBM of devices[g]
-  std::vector<size_t> h_lo, h_hi;
 };
 
 extern "C" const char* g16_group_last_error(const g16_group* g) { return g ? g->err.c_str() : "null group"; }
@@ -140,8 +139,6 @@ extern "C" int32_t g16_group_pkey_create_lean(g16_group* g, const g16_pkey_desc*
   k->key.assign(G, nullptr);
   k->task_out.resize(G);
   k->slices.resize(G);
-  k->h_lo.assign(G, 0);
-  k->h_hi.assign(G, 0);
   const size_t n = size_t(1) << desc->log2_domain;
   // table precomputation of the shards runs concurrently, one thread per member
   int32_t rc = for_members(g, [&](size_t i) -> int32_t {
@@ -151,14 +148,12 @@ extern "C" int32_t g16_group_pkey_create_lean(g16_group* g, const g16_pkey_desc*
     g16_ctx* ctx = g->m[i].ctx;   // for_members reports this member's error text
     int32_t r = g16_pkey_create_lean(ctx, &d, table_stride, &k->key[i]);
     if (r != G16_OK) return r;
-    k->h_lo[i] = (n * i) / G;               // msm.nim:107-115: b = (N * (k + 1)) div ntasks
-    k->h_hi[i] = (n * (i + 1)) / G;
     if (desc->flavour != G16_FLAVOUR_SNARKJS) return G16_OK;
     size_t owned = 0;
     for (uint32_t v = 0; v < 3; ++v) owned += task_owner(v, (uint32_t)G) == i;
     HIPCHK(ctx, hipSetDevice(g->m[i].device));
     if (owned) HIPCHK(ctx, dev_alloc(k->task_out[i], owned * n * 32));
-    const size_t nh = k->h_hi[i] - k->h_lo[i];
+    const size_t nh = k->key[i]->h.size();   // the shard's range of domain indices (shard_range, key_plan.hpp)
     if (nh) HIPCHK(ctx, dev_alloc(k->slices[i], 3 * nh * 32));
     return G16_OK;
   });
@@ -204,14 +199,14 @@ extern "C" int32_t g16_group_prove(g16_group* g, const g16_group_pkey* k, const 
     if (rc == G16_OK)
       rc = for_members(g, [&](size_t i) -> int32_t {
         g16_ctx* ctx = g->m[i].ctx;
-        const size_t nh = k->h_hi[i] - k->h_lo[i];
+        const size_t nh = k->key[i]->h.size();
         char* sl = (char*)k->slices[i].get();
         HIPCHK(ctx, hipSetDevice(g->m[i].device));
         for (uint32_t v = 0; v < 3 && nh; ++v) {
           const size_t o = task_owner(v, (uint32_t)G);
           size_t idx = 0;                               // position of v among the owner's pipelines
           for (uint32_t u = 0; u < v; ++u) idx += task_owner(u, (uint32_t)G) == o;
-          const char* src = (const char*)k->task_out[o].get() + (idx * n + k->h_lo[i]) * 32;
+          const char* src = (const char*)k->task_out[o].get() + (idx * n + k->key[i]->h.lo) * 32;
           const hipError_t e = g->m[o].device == g->m[i].device
                                    ? hipMemcpyAsync(sl + v * nh * 32, src, nh * 32, hipMemcpyDeviceToDevice, ctx->stream)
                                    : hipMemcpyPeerAsync(sl + v * nh * 32, g->m[i].device, src, g->m[o].device, nh * 32,

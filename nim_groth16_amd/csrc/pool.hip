@@ -20,7 +20,7 @@
 #include <thread>
 #include <vector>
 
-#include "g16_internal.hpp"
+#include "pkey.hpp"
 
 namespace {
 enum RecState { REC_FREE, REC_PENDING, REC_RUNNING, REC_DONE };
@@ -142,10 +142,7 @@ extern "C" int32_t g16_prover_create(int32_t device, const g16_pkey* key, uint32
   if (!out) return G16_EINVAL;
   *out = nullptr;
   if (!key || depth < 1 || depth > 8) return G16_EINVAL;
-  int kdev = 0;
-  uint32_t nvars = 0, shards = 0;
-  g16_pkey_shape(key, &kdev, &nvars, &shards);
-  if (shards != 1 || kdev != device) return G16_EINVAL;
+  if (key->shard_count != 1 || key->device != device) return G16_EINVAL;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ENODEV;
   if (device < 0 || device >= ndev) return G16_EINVAL;
@@ -156,7 +153,7 @@ extern "C" int32_t g16_prover_create(int32_t device, const g16_pkey* key, uint32
     p->device = device;
     p->key = key;
     p->depth = depth;
-    p->wbytes = (size_t)nvars * 32;
+    p->wbytes = (size_t)key->nvars * 32;
     p->ctx.assign(depth, nullptr);
     p->slot_rec.assign(depth, -1);
     p->rec.resize(depth + 1);

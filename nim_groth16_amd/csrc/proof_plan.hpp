@@ -9,40 +9,11 @@
 #include <stdint.h>
 
 #include "g16_env.hpp"
+#include "key_plan.hpp"   // B1Form, b1_fold_form, points_sparse: what a key is, which a ProofShape restates
 
 namespace g16 {
 
 // ---- small decisions of the host layer that depend on the knobs alone ----------------------------------------------
-// a point set (or the B1 / B2 pair) with n_inf of its n points at (0,0) holds enough of them for entry lists of its
-// own to pay (G16_INF_COMPACT, g16_pkey)
-inline bool points_sparse(size_t n_inf, size_t n, const G16Env& env) {
-  return n_inf && n_inf * 100 >= (size_t)env.inf_compact_pct * n;
-}
-// pointsB1 folded into pointsA1 (g16_pkey, prover.hip).  A1 and B1 meet the same scalars, so with D_i = B1_i - A1_i
-//   MSM(w, B1) = MSM(w, A1) + MSM(w, D),
-// and D_i is the point at infinity for every wire whose columns of A and B coincide (squarings, boolean checks).  The
-// form a key takes, from counts over its WHOLE wire range of n wires (every shard of a key reaches the same answer):
-//   live_b1 = #{B1_i != inf},  live_delta = #{B1_i != A1_i}
-//   EMPTY  no live difference: the B1 accumulation runs against no table at all and leaves infinity
-//   DELTA  D in place of B1, where D holds few enough live points that dropping the others would pay against B1 as it
-//          stands by the rule of points_sparse: live_delta * 100 <= live_b1 * (100 - G16_INF_COMPACT) -- and where D's
-//          run costs no more than B1's did.  D has no arrangement of its own: its run reads the arrangement of all n
-//          pairs (ProofPlan::sort_b1), where an addition is skipped only if all 64 lanes of a wave meet infinity, so it
-//          costs up to min(n, 64 * live_delta) wave-level additions.  B1 as it stands costs n of them, or live_b1 where
-//          the key's B sets run on their compacted arrangement (points_sparse over the B1 points at infinity).  Against
-//          n, D never loses; against a compacted B1 it must have most waves empty: 64 * live_delta <= live_b1.
-//   PLAIN  everything else (and every key under G16_B1_FOLD=0): B1 as registered
-// In the first two forms the record's B1 slot holds MSM(w, D) and the combine kernel adds the A1 slots to it.
-enum B1Form : int { B1_PLAIN = 0, B1_EMPTY = 1, B1_DELTA = 2 };
-inline B1Form b1_fold_form(size_t live_b1, size_t live_delta, size_t n, const G16Env& env) {
-  if (!env.b1_fold) return B1_PLAIN;
-  if (live_delta == 0) return B1_EMPTY;
-  const long long keep = 100 - (long long)env.inf_compact_pct;   // (G16_INF_COMPACT=101, "never": negative)
-  if ((long long)live_delta * 100 > (long long)live_b1 * keep) return B1_PLAIN;
-  const bool b1_compacted = n >= live_b1 && points_sparse(n - live_b1, n, env);
-  if (b1_compacted && live_delta * 64 > live_b1) return B1_PLAIN;
-  return B1_DELTA;
-}
 // G16_CU_SPLIT=k: the CU mask of the main stream (`front`: k CUs of every XCD) or of an MSM lane (the other 32 - k).
 // CU-mask bit i is CU (i / 8) of XCD (i % 8): the mask is dealt round robin over the XCCs.
 inline void stream_cu_mask(const G16Env& env, bool front, uint32_t mask[8]) {

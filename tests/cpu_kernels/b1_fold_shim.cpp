@@ -1,4 +1,4 @@
-// Test-only: the rule that folds pointsB1 into pointsA1 (proof_plan.hpp), what it changes in a proof's launch plan, and
+// Test-only: the rule that folds pointsB1 into pointsA1 (key_plan.hpp), what it changes in a proof's launch plan, and
 // the device's point difference (b1_fold.cuh) compiled with g++.  Not part of the product library.
 #include "../../nim_groth16_amd/csrc/b1_fold.cuh"
 #include "../../nim_groth16_amd/csrc/proof_plan.hpp"

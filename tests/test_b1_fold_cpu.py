@@ -2,7 +2,7 @@
 
 A1 and B1 are multiplied by the same scalars, so with D_i = B1_i - A1_i the sum MSM(w, B1) equals MSM(w, A1) + MSM(w, D);
 a key keeps D (or nothing at all) in place of pointsB1 where few enough of the D_i are live.  Held here, without a GPU:
-  * the rule (b1_fold_form, nim_groth16_amd/csrc/proof_plan.hpp) against a restatement in Python integers, exhaustively
+  * the rule (b1_fold_form, nim_groth16_amd/csrc/key_plan.hpp) against a restatement in Python integers, exhaustively
     over small counts and at every boundary of its three forms, keys with 5 .. 50 % linear wires (whose B1 runs
     compacted, and which the fold must leave alone), the switch G16_B1_FOLD=0, and why the counts must be the whole
     key's and not a shard's;

@@ -1,5 +1,5 @@
 """pointsB1 folded into pointsA1 on the GPU: MSM(w, B1) = MSM(w, A1) + MSM(w, B1 - A1), and a key keeps the differences
-(or nothing) in place of pointsB1 where few enough of them are live (b1_fold_form, nim_groth16_amd/csrc/proof_plan.hpp;
+(or nothing) in place of pointsB1 where few enough of them are live (b1_fold_form, nim_groth16_amd/csrc/key_plan.hpp;
 tests/test_b1_fold_cpu.py holds the rule and the point difference on the CPU).
 
 Every proof here is compared with the C oracle's bit for bit, the key's form and its two counts with a recount of the
