@@ -10,9 +10,10 @@
 //          the global-atomic variant, used when the partition count exceeds the LDS histogram and by G16_MSM_SORT=a)
 //   accum  msm_accum      one thread per bucket *segment* (<= L entries): XYZZ += affine table point, 9x29 field
 //   heavy  msm_heavy      buckets that were split in >1 segment: one thread (few segments) / LDS tree (many)
-//   reduce msm_reduce1/2  sum_k k*B_k: 16-bucket chunk running sums, then per slice an LDS suffix scan + tree
-//   fold   msm_fold_classes / msm_fold_merged (registered sets: slices of the class / plain bucket set) or msm_fold
-//          (windows, Horner) -> one point; canonical affine on request
+//   reduce msm_reduce1/2  sum_k k*B_k: 16-bucket chunk running sums, then per slice an LDS suffix scan + tree; a slot
+//          of msm_reduce2 is one lane or a cooperating quad (Lane / Quad)
+//   fold   msm_fold_classes / msm_fold_classes_quad / msm_fold_merged (registered sets: slices of the class / plain
+//          bucket set) or msm_fold (windows, Horner) -> one point; canonical affine on request
 // Every stage from accum on takes up to MSM_BATCH_MAX jobs per launch (blockIdx.y).
 //
 // Load balance: work is cut by *entries*, not by buckets -- a circom witness puts ~30 % of all
@@ -30,34 +31,9 @@ constexpr int ACC_BLOCK = G16_ACC_BLOCK;   // workgroup size of the accumulate k
 #ifndef G16_G2_WAVES
 #define G16_G2_WAVES 2
 #endif
-
-// Wave priority of the latency-bound kernels (split-bucket combine, reduce, fold; the sort): their few waves share the
-// SIMDs with the register-filling accumulate waves of the other streams, and every instruction they wait for the
-// arbiter lengthens a dependency chain the proof's end waits for.  s_setprio 3 = issue before priority-0 waves.
-#ifndef G16_TAIL_PRIO
-#define G16_TAIL_PRIO 0
-#endif
-__device__ __forceinline__ void tail_prio() {
-#if G16_TAIL_PRIO
-  __builtin_amdgcn_s_setprio(G16_TAIL_PRIO);
-#endif
-}
 #ifndef G16_G1_WAVES
 #define G16_G1_WAVES 4
 #endif
-// Register budget of the latency-bound kernels, as waves per SIMD they must allow (1 = whatever the compiler takes).
-// A wave can only start on a SIMD with that many free registers: while the accumulate kernels of other streams keep
-// refilling the SIMDs with 117-register (G1) / 241-register (G2) waves, a 481-register reduce1<G2> wave finds room
-// only when a whole SIMD drains -- the tails of a proof then wait for the accumulate launches to END instead of
-// slotting in behind single exiting waves.
-#ifndef G16_TAIL_WAVES_G1
-#define G16_TAIL_WAVES_G1 1
-#endif
-#ifndef G16_TAIL_WAVES_G2
-#define G16_TAIL_WAVES_G2 1
-#endif
-template <class C>
-constexpr int tail_waves() { return sizeof(typename C::Aff) == 64 ? G16_TAIL_WAVES_G1 : G16_TAIL_WAVES_G2; }
 
 // ---- batched launches -------------------------------------------------------------------------------------------
 // Every stage kernel from the accumulation to the fold takes up to MSM_BATCH_MAX independent MSMs per launch
@@ -87,15 +63,16 @@ template <class C>
 struct MsmBatch {
   MsmJob<C> job[MSM_BATCH_MAX];
 };
+// how every fold ends, on one thread: the job's result as an accumulator and / or in canonical affine form
+// (MsmJob::out_acc, out_aff; either may be null)
+template <class C>
+__device__ __forceinline__ void job_finish(typename C::Acc* out_acc, typename C::Aff* out_aff,
+                                           const typename C::Acc& r) {
+  if (out_acc) *out_acc = r;
+  if (out_aff) *out_aff = C::to_affine(r);
+}
 
 
-// signed c-bit digits of a scalar, least significant window first.  The canonical scalar stays in its 8 registers
-// and is shifted right by c bits per window (8 funnel shifts with static register indices, c <= 22 < 32): no LDS
-// staging, no dynamic limb indexing, and any workgroup size.  (Rounds 1-2 staged the limbs in LDS and indexed them by
-// window: 36 KB of LDS per 1024 threads and two LDS reads per digit.)
-// `live` (optional): bitmap over the pairs; a cleared bit drops the pair before its scalar is even read -- the entry
-// lists of point sets with many points at infinity ((0,0) for every wire absent from a matrix, curves.nim:95-107)
-// then hold only the points that can contribute.
 // ---- class bucket set of a registered point set with multiplier tables {1, 2} (MsmParams::mtab == 2) ---------------
 // A signed digit of magnitude t in [1, H], H = 2^(c-1), is served from the table of 2^(c w) P or of 2 * 2^(c w) P:
 //   t = 2^s * b,  s = ctz(t) & 1,  so that b = 4^z * u with u odd (an even power of two times an odd number),
@@ -106,8 +83,16 @@ struct MsmBatch {
 // Classes z = 0, 1, 2 hold t with ctz(t) < 6; the rest (t = 64 x) go unmultiplied to class X, weight 64 x.  Sizes
 // H/2, H/8, H/32, H/64: 43 slices of 2^(c-7) buckets.  Every bucket receives one or two digit values (u > H/2 or an
 // odd-length chain end: one), so bucket loads are 1x or 2x the load of the plain set -- like its two rounds of tasks.
-// (msm_class_bucket itself lives in msm_params.hpp: host and device code, and a CPU test, share it)
+// (msm_class_bucket itself, and msm_class_slice -- the same layout seen from a slice, for the folds -- live in
+// msm_params.hpp: host and device code, and CPU tests, share them)
 
+// signed c-bit digits of a scalar, least significant window first.  The canonical scalar stays in its 8 registers
+// and is shifted right by c bits per window (8 funnel shifts with static register indices, c <= 22 < 32): no LDS
+// staging, no dynamic limb indexing, and any workgroup size.  (Rounds 1-2 staged the limbs in LDS and indexed them by
+// window: 36 KB of LDS per 1024 threads and two LDS reads per digit.)
+// `live` (optional): bitmap over the pairs; a cleared bit drops the pair before its scalar is even read -- the entry
+// lists of point sets with many points at infinity ((0,0) for every wire absent from a matrix, curves.nim:95-107)
+// then hold only the points that can contribute.
 template <class EMIT>
 __device__ __forceinline__ void msm_digits(const u256* __restrict__ scalars, const uint32_t* __restrict__ live, uint32_t i,
                                            const MsmParams& P, EMIT&& emit) {
@@ -369,7 +354,6 @@ static __global__ void __launch_bounds__(BS_LOW) bucket_place(const uint2* __res
   }
 }
 
-// plain exclusive scan of a u32 array in place (three launches, reuses the tile machinery below)
 // ---- three-phase exclusive scan over the bucket histogram ------------------------------------------
 // produces offset[b] = sum_{b'<b} count[b'], xoff[b] = sum_{b'<b} extra(b') with
 // extra(b) = max(ceil(count/L) - 1, 0), and appends buckets with extra(b) > 0 to the heavy list.
@@ -468,7 +452,7 @@ static __global__ void __launch_bounds__(SCAN_BLOCK) scan_apply(const uint32_t* 
   if (blockIdx.x == gridDim.x - 1 && threadIdx.x == SCAN_BLOCK - 1) offset[nb] = o;
 }
 
-// in-place exclusive scan of a plain u32 array (used for tile_hist): same three phases
+// plain exclusive scan of a u32 array in place (used for tile_hist): the same three phases, reusing scan_tiles
 static __global__ void __launch_bounds__(SCAN_BLOCK) scan1_tile_sums(const uint32_t* __restrict__ v, uint32_t n,
                                                                      uint2* __restrict__ tile_sum) {
   uint32_t base = blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
@@ -637,158 +621,16 @@ __global__ void __launch_bounds__(MSM_BLOCK) points_to29(const typename C::Aff* 
   if (i < n) out[i] = Ec29<C>::tab_from_std(points[i]);
 }
 
-// ---- K5: combine the segments of split buckets (one workgroup per heavy bucket) ---------------------
-template <class C, int BLOCK>
-__device__ __forceinline__ typename C::Acc block_sum(typename C::Acc v, typename C::Acc* sh) {
-  sh[threadIdx.x] = v;
-  __syncthreads();
-#pragma unroll 1
-  for (int stride = BLOCK / 2; stride > 0; stride >>= 1) {
-    if ((int)threadIdx.x < stride) {
-      typename C::Acc a = sh[threadIdx.x];
-      C::add(a, sh[threadIdx.x + stride]);
-      sh[threadIdx.x] = a;
-    }
-    __syncthreads();
-  }
-  typename C::Acc r = sh[0];
-  __syncthreads();
-  return r;
-}
-
-// the bucket partials between msm_accum and msm_reduce1 are reduced-radix XYZZ (Ec29<C>::Acc: 144 B G1, 288 B G2);
-// HEAVY_BLOCK threads x one partial each must fit the LDS budget of a workgroup
-template <class C>
-constexpr int heavy_block() { return sizeof(typename C::Aff) == 64 ? 256 : 128; }
-// One launch for every split bucket of the batch: buckets with only a few extra segments are summed by one thread
-// each (phase 1), buckets with >= HEAVY_MIN by a workgroup with an LDS tree (phase 2).  Both phases stride over the
-// same list and touch disjoint buckets.  (Rounds 1-3: two launches, msm_heavy + msm_heavy_small.)
-template <class C>
-__global__ void __launch_bounds__(heavy_block<C>(), tail_waves<C>()) msm_heavy(const MsmBatch<C> B, MsmParams P) {
-  tail_prio();
-  using E = Ec29<C>;
-  constexpr int HEAVY_BLOCK = heavy_block<C>();
-  extern __shared__ __align__(16) unsigned char smem[];
-  typename E::Acc* sh = reinterpret_cast<typename E::Acc*>(smem);
-  const MsmJob<C>& J = B.job[blockIdx.y];
-  const uint32_t* __restrict__ heavy = J.heavy;
-  const uint32_t* __restrict__ offset = J.offset;
-  const uint32_t* __restrict__ xoff = J.xoff;
-  typename E::Acc* __restrict__ partial = J.partial;
-  const uint32_t nheavy = J.info[2];
-  for (uint32_t h = blockIdx.x * HEAVY_BLOCK + threadIdx.x; h < nheavy; h += gridDim.x * HEAVY_BLOCK) {
-    const uint32_t b = heavy[h];
-    const uint32_t e = extra_segs(offset[b + 1] - offset[b], P.seg), x0 = xoff[b];
-    if (e >= HEAVY_MIN) continue;
-    typename E::Acc acc = partial[b];
-    for (uint32_t k = 0; k < e; ++k) E::add(acc, partial[P.nbuckets + x0 + k]);
-    partial[b] = acc;
-  }
-  for (uint32_t h = blockIdx.x; h < nheavy; h += gridDim.x) {
-    uint32_t b = heavy[h];
-    uint32_t e = extra_segs(offset[b + 1] - offset[b], P.seg), x0 = xoff[b];
-    if (e < HEAVY_MIN) continue;   // phase 1's (uniform per workgroup: no barrier is skipped unevenly)
-    typename E::Acc acc = E::acc_inf();
-    // segment 0 lives at partial[b]; segments 1..e at partial[nbuckets + x0 + s - 1]
-    for (uint32_t s = threadIdx.x; s <= e; s += HEAVY_BLOCK) {
-      uint32_t idx = s == 0 ? b : P.nbuckets + x0 + s - 1;
-      E::add(acc, partial[idx]);
-    }
-    typename E::Acc r = block_sum<E, HEAVY_BLOCK>(acc, sh);
-    if (threadIdx.x == 0) partial[b] = r;
-  }
-}
-
-// ---- K6: bucket reduction  S_w = sum_{k=1}^{K} k * B_{w,k},  K = 2^(c-1) -----------------------------
-// stage 1: thread per chunk of RC consecutive buckets: R_j = sum B_k, A_j = sum (k - j*RC) B_k
-// (RC = msm_red_chunk, msm_plan.hpp: 16, or 4 for small bucket sets)
-// A job that continues another MSM's bucket sums (MsmJob::init): a bucket without entries of its own still
-// holds the other MSM's sum, so every bucket is added (infinity is skipped inside the addition).
-template <class C>
-__global__ void __launch_bounds__(MSM_BLOCK, tail_waves<C>()) msm_reduce1(const MsmBatch<C> B, uint32_t nbuckets, uint32_t rc) {
-  tail_prio();
-  using E = Ec29<C>;   // running sums in the reduced-radix field; the chunk sums leave in the standard layout
-  const MsmJob<C>& J = B.job[blockIdx.y];
-  const typename E::Acc* __restrict__ partial = J.partial;
-  const uint32_t* __restrict__ offset = J.offset;
-  const bool always = J.init != nullptr;
-  uint32_t j = blockIdx.x * MSM_BLOCK + threadIdx.x;
-  uint32_t b0 = j * rc;
-  if (b0 >= nbuckets) return;
-  typename E::Acc run = E::acc_inf(), acc = E::acc_inf();
-#pragma unroll 1
-  for (int k = (int)rc - 1; k >= 0; --k) {
-    uint32_t b = b0 + k;
-    if (b < nbuckets && (always || offset[b + 1] != offset[b])) E::add(run, partial[b]);
-    E::add(acc, run);
-  }
-  J.chunkR[j] = E::to_std(run);
-  J.chunkA[j] = E::to_std(acc);
-}
-// stage 2: one workgroup per reduction set (a window, or a slice of the merged bucket set) over its M chunks
-// (chunk m holds buckets m*RC+1 .. (m+1)*RC of the set):
-//   S = sum_m A_m + RC * sum_m m * R_m ,      sum_m m R_m = sum_t [ wsum_t + lo_t * run_t ]
-// Thread t owns chunks [lo_t, lo_t + per): run_t = sum R, wsum_t = sum (m - lo_t) R_m, sumA_t = sum A_m by
-// running sums; sum_t lo_t run_t = per * sum_{t>=1} suffix(t) with suffix = inclusive suffix scan of run_t
-// (Hillis-Steele in LDS).  Each thread then forms  v_t = RC * (per * suffix_t[t>=1] + wsum_t) + sumA_t  with a
-// few doublings, and ONE LDS tree adds the v_t.  The whole kernel is a latency chain of ~40 group operations,
-// so the block is as wide as the register budget allows (BLOCK = 512 for G1, 256 for G2).
-template <class C, int BLOCK>
-__global__ void __launch_bounds__(BLOCK, tail_waves<C>()) msm_reduce2(const MsmBatch<C> B, uint32_t chunks_per_window,
-                                                                      uint32_t rc) {
-  tail_prio();
-  extern __shared__ __align__(16) unsigned char smem[];
-  typename C::Acc* sh = reinterpret_cast<typename C::Acc*>(smem);
-  const MsmJob<C>& J = B.job[blockIdx.y];
-  typename C::Acc* __restrict__ window_sum = J.wsum;        // [0, 64]: set sums
-  typename C::Acc* __restrict__ window_tot = J.wsum + 65;   // [65, 129]: sum of every bucket of the set
-  const uint32_t w = blockIdx.x, M = chunks_per_window;
-  const typename C::Acc* R = J.chunkR + (size_t)w * M;
-  const typename C::Acc* A = J.chunkA + (size_t)w * M;
-  const uint32_t per = (M + BLOCK - 1) / BLOCK;
-  const uint32_t lo = threadIdx.x * per, hi = (lo + per < M) ? lo + per : M;
-  typename C::Acc sumA = C::acc_inf(), run = C::acc_inf(), wsum = C::acc_inf();
-  if (lo < M) {
-    for (uint32_t m = hi; m-- > lo;) {
-      C::add(wsum, run);   // each R_m' ends up counted (m' - lo) times
-      C::add(run, R[m]);
-      C::add(sumA, A[m]);
-    }
-  }
-  // inclusive suffix scan of the slice totals
-  sh[threadIdx.x] = run;
-  __syncthreads();
-  typename C::Acc incl = run;
-#pragma unroll 1
-  for (int d = 1; d < BLOCK; d <<= 1) {
-    typename C::Acc other = C::acc_inf();
-    const bool has = (int)threadIdx.x + d < BLOCK;
-    if (has) other = sh[threadIdx.x + d];
-    __syncthreads();
-    if (has) C::add(incl, other);
-    sh[threadIdx.x] = incl;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) window_tot[w] = incl;   // sum of every bucket of this set
-  // v_t = RC * (per * suffix_t + wsum_t) + sumA_t
-  typename C::Acc v = (threadIdx.x >= 1 && lo < M) ? C::mul_small(incl, per) : C::acc_inf();
-  C::add(v, wsum);
-  v = C::mul_small(v, rc);
-  C::add(v, sumA);
-  __syncthreads();
-  typename C::Acc tot = block_sum<C, BLOCK>(v, sh);
-  if (threadIdx.x == 0) window_sum[w] = tot;
-}
-
-// ---- wave-cooperative doubling for the serial tails -----------------------------------------------------
+// ---- cooperative doubling for the serial tails ----------------------------------------------------------
 // A doubling chain on ONE lane is bound by the issue rate of its wave (~2800 instructions, ~7 us per doubling on
 // MI355X) while 63 lanes idle.  The 9 multiplications + 1 two-term product of dbl-2008-s-1 fall into three levels
 // of mutually independent products:
 //   level 1:  v = u^2          xx = x^2                        (u = 2y)
 //   level 2:  w = u v          s  = x v          mm = m^2      (m = 3 xx)
 //   level 3:  y3 = m (s - x3) - w y      zz3 = v zz      zzz3 = w zzz        (x3 = mm - 2s)
-// Lanes 0, 1, 2 of the wave take one product of a level each -- the SAME instruction stream on different operands,
-// so nothing diverges -- and the results travel between levels by ds_bpermute.  One doubling then costs 3 (+1/2)
+// Lanes 0, 1, 2 of a group take one product of a level each -- the SAME instruction stream on different operands,
+// so nothing diverges -- and the results travel between levels through the group's transport X: the whole wave by
+// ds_bpermute (WaveXfer), or a quad by quad-permute DPP moves (QuadXfer).  One doubling then costs 3 (+1/2)
 // multiplications of wave time instead of 10 1/2.  Every lane must hold the same COORDINATES (not merely the same
 // point: products computed by different lanes are combined) on entry, and does on exit; the formulas map the all-zero
 // infinity to itself, so no lane branches.
@@ -799,40 +641,6 @@ __device__ __forceinline__ u256 wave_get(const u256& v, int src) {
   return r;
 }
 __device__ __forceinline__ fp2_t wave_get(const fp2_t& v, int src) { return fp2_t{wave_get(v.c0, src), wave_get(v.c1, src)}; }
-template <class E>
-__device__ __forceinline__ E sel3(uint32_t role, const E& a, const E& b, const E& c) {
-  return role == 0 ? a : (role == 1 ? b : c);
-}
-template <class C>
-__device__ __forceinline__ typename C::Acc dbl_coop(const typename C::Acc& p) {
-  using F = typename C::Field;
-  using E = typename C::E;
-  const uint32_t lane = threadIdx.x & 63, role = lane < 2 ? lane : 2;
-  const E u = F::dbl(p.y);
-  const E l1 = F::sqr(role == 0 ? u : p.x);
-  const E v = wave_get(l1, 0), xx = wave_get(l1, 1);
-  const E m = F::add(F::dbl(xx), xx);
-  const E l2 = F::mul(sel3(role, u, p.x, m), role == 2 ? m : v);
-  const E w = wave_get(l2, 0), s = wave_get(l2, 1), mm = wave_get(l2, 2);
-  const E x3 = F::sub(mm, F::dbl(s));
-  // a b - c d on every lane (c = 0 on lanes 1, 2: the plain product through the same code path)
-  const E l3 = F::mulsub(sel3(role, m, v, w), sel3(role, F::sub(s, x3), p.zz, p.zzz), role == 0 ? w : F::zero(), p.y);
-  return typename C::Acc{x3, wave_get(l3, 0), wave_get(l3, 1), wave_get(l3, 2)};
-}
-
-// ---- quad-cooperative group operations for the latency chains ------------------------------------------------------
-// reduce2 and the folds are chains of DEPENDENT group operations run by a handful of waves: one addition on one lane
-// is bound by the issue rate of its wave (~4.5 us G1, ~20 us G2) while most of the GPU idles.  The 14 multiplications
-// of add-2008-s fall into four levels of mutually independent products:
-//   level 1:  u1 = x1 zz2     u2 = x2 zz1     s1 = y1 zzz2    s2 = y2 zzz1          (p = u2 - u1, r = s2 - s1)
-//   level 2:  pp = p^2        rr = r^2        z12 = zz1 zz2   z123 = zzz1 zzz2
-//   level 3:  ppp = p pp      q = u1 pp       zz3 = z12 pp                          (x3 = rr - ppp - 2 q)
-//   level 4:  r (q - x3)      s1 ppp          zzz3 = z123 ppp                       (y3 = the difference)
-// The four lanes of a quad hold the SAME operands (the same coordinates, not merely the same point), take one product
-// of a level each -- one instruction stream, different operands, nothing diverges inside a quad -- and exchange the
-// results by quad-permute DPP moves (no LDS, no barrier).  An addition then costs 4 multiplications of wave time
-// instead of 14, a doubling (dbl_coop's three levels) 3 instead of 10 1/2.  Every lane of the quad returns the same
-// coordinates.  Branches (infinity, P = +-Q) are uniform inside a quad by construction.
 template <int I>
 __device__ __forceinline__ uint32_t quad_word(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, I * 0x55, 0xf, 0xf, false);   // quad_perm:[I,I,I,I]
@@ -846,24 +654,57 @@ __device__ __forceinline__ u256 quad_get(const u256& v) {
 }
 template <int I>
 __device__ __forceinline__ fp2_t quad_get(const fp2_t& v) { return fp2_t{quad_get<I>(v.c0), quad_get<I>(v.c1)}; }
+struct WaveXfer {
+  static __device__ __forceinline__ uint32_t lane() { return threadIdx.x & 63; }
+  template <int I, class E>
+  static __device__ __forceinline__ E get(const E& v) { return wave_get(v, I); }
+};
+struct QuadXfer {
+  static __device__ __forceinline__ uint32_t lane() { return threadIdx.x & 3; }
+  template <int I, class E>
+  static __device__ __forceinline__ E get(const E& v) { return quad_get<I>(v); }
+};
+template <class E>
+__device__ __forceinline__ E sel3(uint32_t role, const E& a, const E& b, const E& c) {
+  return role == 0 ? a : (role == 1 ? b : c);
+}
+template <class C, class X>
+__device__ __forceinline__ typename C::Acc dbl_over(const typename C::Acc& p) {
+  using F = typename C::Field;
+  using E = typename C::E;
+  const uint32_t lane = X::lane(), role = lane < 2 ? lane : 2;   // every further lane repeats lane 2's product
+  const E u = F::dbl(p.y);
+  const E l1 = F::sqr(role == 0 ? u : p.x);
+  const E v = X::template get<0>(l1), xx = X::template get<1>(l1);
+  const E m = F::add(F::dbl(xx), xx);
+  const E l2 = F::mul(sel3(role, u, p.x, m), role == 2 ? m : v);
+  const E w = X::template get<0>(l2), s = X::template get<1>(l2), mm = X::template get<2>(l2);
+  const E x3 = F::sub(mm, F::dbl(s));
+  // a b - c d on every lane (c = 0 on lanes 1, 2: the plain product through the same code path)
+  const E l3 = F::mulsub(sel3(role, m, v, w), sel3(role, F::sub(s, x3), p.zz, p.zzz), role == 0 ? w : F::zero(), p.y);
+  return typename C::Acc{x3, X::template get<0>(l3), X::template get<1>(l3), X::template get<2>(l3)};
+}
+template <class C>
+__device__ __forceinline__ typename C::Acc dbl_coop(const typename C::Acc& p) { return dbl_over<C, WaveXfer>(p); }
+template <class C>
+__device__ __forceinline__ typename C::Acc dbl_quad(const typename C::Acc& p) { return dbl_over<C, QuadXfer>(p); }
+
+// ---- quad-cooperative group operations for the latency chains ------------------------------------------------------
+// reduce2 and the folds are chains of DEPENDENT group operations run by a handful of waves: one addition on one lane
+// is bound by the issue rate of its wave (~4.5 us G1, ~20 us G2) while most of the GPU idles.  The 14 multiplications
+// of add-2008-s fall into four levels of mutually independent products:
+//   level 1:  u1 = x1 zz2     u2 = x2 zz1     s1 = y1 zzz2    s2 = y2 zzz1          (p = u2 - u1, r = s2 - s1)
+//   level 2:  pp = p^2        rr = r^2        z12 = zz1 zz2   z123 = zzz1 zzz2
+//   level 3:  ppp = p pp      q = u1 pp       zz3 = z12 pp                          (x3 = rr - ppp - 2 q)
+//   level 4:  r (q - x3)      s1 ppp          zzz3 = z123 ppp                       (y3 = the difference)
+// The four lanes of a quad hold the SAME operands (the same coordinates, not merely the same point), take one product
+// of a level each -- one instruction stream, different operands, nothing diverges inside a quad -- and exchange the
+// results by quad-permute DPP moves (no LDS, no barrier).  An addition then costs 4 multiplications of wave time
+// instead of 14, a doubling (dbl_quad's three levels) 3 instead of 10 1/2.  Every lane of the quad returns the same
+// coordinates.  Branches (infinity, P = +-Q) are uniform inside a quad by construction.
 template <class E>
 __device__ __forceinline__ E sel4(uint32_t role, const E& a, const E& b, const E& c, const E& d) {
   return role == 0 ? a : (role == 1 ? b : (role == 2 ? c : d));
-}
-template <class C>
-__device__ __forceinline__ typename C::Acc dbl_quad(const typename C::Acc& p) {
-  using F = typename C::Field;
-  using E = typename C::E;
-  const uint32_t q = threadIdx.x & 3, role = q < 2 ? q : 2;   // lane 3 repeats lane 2's product
-  const E u = F::dbl(p.y);
-  const E l1 = F::sqr(role == 0 ? u : p.x);
-  const E v = quad_get<0>(l1), xx = quad_get<1>(l1);
-  const E m = F::add(F::dbl(xx), xx);
-  const E l2 = F::mul(sel3(role, u, p.x, m), role == 2 ? m : v);
-  const E w = quad_get<0>(l2), s = quad_get<1>(l2), mm = quad_get<2>(l2);
-  const E x3 = F::sub(mm, F::dbl(s));
-  const E l3 = F::mulsub(sel3(role, m, v, w), sel3(role, F::sub(s, x3), p.zz, p.zzz), role == 0 ? w : F::zero(), p.y);
-  return typename C::Acc{x3, quad_get<0>(l3), quad_get<1>(l3), quad_get<2>(l3)};   // infinity (all zero) maps to itself
 }
 template <class C>
 __device__ __forceinline__ typename C::Acc add_quad(const typename C::Acc& a, const typename C::Acc& b) {
@@ -895,69 +736,178 @@ __device__ __forceinline__ typename C::Acc mul_small_quad(const typename C::Acc&
   }
   return r;
 }
-// sum over the SLOTS quads of a workgroup (4 * SLOTS threads), returned on every thread
-template <class C, int SLOTS>
-__device__ __forceinline__ typename C::Acc block_sum_quad(const typename C::Acc& v, typename C::Acc* sh) {
-  const int slot = threadIdx.x >> 2;
-  __syncthreads();
-  if ((threadIdx.x & 3) == 0) sh[slot] = v;
+
+// ---- how many lanes share one group operation ---------------------------------------------------------------------
+// The kernels below that are written per SLOT take the cooperation as a policy: a slot is W consecutive threads that
+// hold the same coordinates, slot = threadIdx.x / W, and the lane with threadIdx.x % W == 0 writes the slot's LDS cell.
+// Lane: one thread per slot, the plain operations of the curve.  Quad: four, the operations above.
+// add accumulates in registers; sum adds two cells of memory (block_sum's tree, read straight from LDS): Lane copies
+// its first operand, Quad reads both in place -- each as its kernels always did, which keeps their compiled code.
+template <class C>
+struct Lane {
+  using Acc = typename C::Acc;
+  static constexpr int W = 1;
+  static __device__ __forceinline__ void add(Acc& a, const Acc& b) { C::add(a, b); }
+  static __device__ __forceinline__ Acc sum(Acc a, const Acc& b) {
+    C::add(a, b);
+    return a;
+  }
+  static __device__ __forceinline__ Acc dbl(const Acc& p) { return C::dbl(p); }
+  static __device__ __forceinline__ Acc mul_small(const Acc& p, uint32_t k) { return C::mul_small(p, k); }
+};
+template <class C>
+struct Quad {
+  using Acc = typename C::Acc;
+  static constexpr int W = 4;
+  static __device__ __forceinline__ void add(Acc& a, const Acc& b) { a = add_quad<C>(a, b); }
+  static __device__ __forceinline__ Acc sum(const Acc& a, const Acc& b) { return add_quad<C>(a, b); }
+  static __device__ __forceinline__ Acc dbl(const Acc& p) { return dbl_quad<C>(p); }
+  static __device__ __forceinline__ Acc mul_small(const Acc& p, uint32_t k) { return mul_small_quad<C>(p, k); }
+};
+// sum of v over the SLOTS slots whose cells are sh[0 .. SLOTS), returned on every thread of them.  The caller's last
+// read of sh lies behind a barrier.
+template <class Coop, int SLOTS>
+__device__ __forceinline__ typename Coop::Acc block_sum(int slot, const typename Coop::Acc& v, typename Coop::Acc* sh) {
+  const uint32_t q = threadIdx.x % Coop::W;
+  if (q == 0) sh[slot] = v;
   __syncthreads();
 #pragma unroll 1
   for (int stride = SLOTS / 2; stride > 0; stride >>= 1) {
     if (slot < stride) {
-      const typename C::Acc a = add_quad<C>(sh[slot], sh[slot + stride]);
-      if ((threadIdx.x & 3) == 0) sh[slot] = a;
+      const typename Coop::Acc a = Coop::sum(sh[slot], sh[slot + stride]);
+      if (q == 0) sh[slot] = a;
     }
     __syncthreads();
   }
-  const typename C::Acc r = sh[0];
+  typename Coop::Acc r = sh[0];
   __syncthreads();
   return r;
 }
 
-// stage 2 of the bucket reduction (msm_reduce2's algorithm and outputs) with a quad per slot: 4 * SLOTS threads
-template <class C, int SLOTS>
-__global__ void __launch_bounds__(4 * SLOTS, tail_waves<C>()) msm_reduce2_quad(const MsmBatch<C> B, uint32_t chunks_per_window,
-                                                                               uint32_t rc) {
-  tail_prio();
+// ---- K5: combine the segments of split buckets (one workgroup per heavy bucket) ---------------------
+// the bucket partials between msm_accum and msm_reduce1 are reduced-radix XYZZ (Ec29<C>::Acc: 144 B G1, 288 B G2);
+// HEAVY_BLOCK threads x one partial each must fit the LDS budget of a workgroup
+template <class C>
+constexpr int heavy_block() { return sizeof(typename C::Aff) == 64 ? 256 : 128; }
+// One launch for every split bucket of the batch: buckets with only a few extra segments are summed by one thread
+// each (phase 1), buckets with >= HEAVY_MIN by a workgroup with an LDS tree (phase 2).  Both phases stride over the
+// same list and touch disjoint buckets.  (Rounds 1-3: two launches, msm_heavy + msm_heavy_small.)
+template <class C>
+__global__ void __launch_bounds__(heavy_block<C>(), 1) msm_heavy(const MsmBatch<C> B, MsmParams P) {
+  using E = Ec29<C>;
+  constexpr int HEAVY_BLOCK = heavy_block<C>();
   extern __shared__ __align__(16) unsigned char smem[];
-  typename C::Acc* sh = reinterpret_cast<typename C::Acc*>(smem);
+  typename E::Acc* sh = reinterpret_cast<typename E::Acc*>(smem);
+  const MsmJob<C>& J = B.job[blockIdx.y];
+  const uint32_t* __restrict__ heavy = J.heavy;
+  const uint32_t* __restrict__ offset = J.offset;
+  const uint32_t* __restrict__ xoff = J.xoff;
+  typename E::Acc* __restrict__ partial = J.partial;
+  const uint32_t nheavy = J.info[2];
+  for (uint32_t h = blockIdx.x * HEAVY_BLOCK + threadIdx.x; h < nheavy; h += gridDim.x * HEAVY_BLOCK) {
+    const uint32_t b = heavy[h];
+    const uint32_t e = extra_segs(offset[b + 1] - offset[b], P.seg), x0 = xoff[b];
+    if (e >= HEAVY_MIN) continue;
+    typename E::Acc acc = partial[b];
+    for (uint32_t k = 0; k < e; ++k) E::add(acc, partial[P.nbuckets + x0 + k]);
+    partial[b] = acc;
+  }
+  for (uint32_t h = blockIdx.x; h < nheavy; h += gridDim.x) {
+    uint32_t b = heavy[h];
+    uint32_t e = extra_segs(offset[b + 1] - offset[b], P.seg), x0 = xoff[b];
+    if (e < HEAVY_MIN) continue;   // phase 1's (uniform per workgroup: no barrier is skipped unevenly)
+    typename E::Acc acc = E::acc_inf();
+    // segment 0 lives at partial[b]; segments 1..e at partial[nbuckets + x0 + s - 1]
+    for (uint32_t s = threadIdx.x; s <= e; s += HEAVY_BLOCK) {
+      uint32_t idx = s == 0 ? b : P.nbuckets + x0 + s - 1;
+      E::add(acc, partial[idx]);
+    }
+    // (block_sum ends in a barrier behind its last read of sh: the next bucket of this loop may write sh at once)
+    typename E::Acc r = block_sum<Lane<E>, HEAVY_BLOCK>(threadIdx.x, acc, sh);
+    if (threadIdx.x == 0) partial[b] = r;
+  }
+}
+
+// ---- K6: bucket reduction  S_w = sum_{k=1}^{K} k * B_{w,k},  K = 2^(c-1) -----------------------------
+// stage 1: thread per chunk of RC consecutive buckets: R_j = sum B_k, A_j = sum (k - j*RC) B_k
+// (RC = msm_red_chunk, msm_plan.hpp: 16, or 4 for small bucket sets)
+// A job that continues another MSM's bucket sums (MsmJob::init): a bucket without entries of its own still
+// holds the other MSM's sum, so every bucket is added (infinity is skipped inside the addition).
+template <class C>
+__global__ void __launch_bounds__(MSM_BLOCK, 1) msm_reduce1(const MsmBatch<C> B, uint32_t nbuckets, uint32_t rc) {
+  using E = Ec29<C>;   // running sums in the reduced-radix field; the chunk sums leave in the standard layout
+  const MsmJob<C>& J = B.job[blockIdx.y];
+  const typename E::Acc* __restrict__ partial = J.partial;
+  const uint32_t* __restrict__ offset = J.offset;
+  const bool always = J.init != nullptr;
+  uint32_t j = blockIdx.x * MSM_BLOCK + threadIdx.x;
+  uint32_t b0 = j * rc;
+  if (b0 >= nbuckets) return;
+  typename E::Acc run = E::acc_inf(), acc = E::acc_inf();
+#pragma unroll 1
+  for (int k = (int)rc - 1; k >= 0; --k) {
+    uint32_t b = b0 + k;
+    if (b < nbuckets && (always || offset[b + 1] != offset[b])) E::add(run, partial[b]);
+    E::add(acc, run);
+  }
+  J.chunkR[j] = E::to_std(run);
+  J.chunkA[j] = E::to_std(acc);
+}
+// stage 2: one workgroup per reduction set (a window, or a slice of the merged bucket set) over its M chunks
+// (chunk m holds buckets m*RC+1 .. (m+1)*RC of the set):
+//   S = sum_m A_m + RC * sum_m m * R_m ,      sum_m m R_m = sum_t [ wsum_t + lo_t * run_t ]
+// Slot t owns chunks [lo_t, lo_t + per): run_t = sum R, wsum_t = sum (m - lo_t) R_m, sumA_t = sum A_m by
+// running sums; sum_t lo_t run_t = per * sum_{t>=1} suffix(t) with suffix = inclusive suffix scan of run_t
+// (Hillis-Steele in LDS).  Each slot then forms  v_t = RC * (per * suffix_t[t>=1] + wsum_t) + sumA_t  with a
+// few doublings, and ONE LDS tree adds the v_t.  The whole kernel is a latency chain of ~40 group operations.  A slot
+// is what Coop says (above): a quad, whose operations are ~3 x shorter (4 * 128 / 4 * 64 threads), or one lane, and
+// then the block is as wide as the register budget allows (512 slots for G1, 256 for G2) or narrower (msm_plan.hpp).
+template <class C, class Coop, int SLOTS>
+__global__ void __launch_bounds__(Coop::W * SLOTS, 1) msm_reduce2(const MsmBatch<C> B, uint32_t chunks_per_window,
+                                                                  uint32_t rc) {
+  using Acc = typename C::Acc;
+  extern __shared__ __align__(16) unsigned char smem[];
+  Acc* sh = reinterpret_cast<Acc*>(smem);
   const MsmJob<C>& J = B.job[blockIdx.y];
   const uint32_t w = blockIdx.x, M = chunks_per_window;
-  const typename C::Acc* R = J.chunkR + (size_t)w * M;
-  const typename C::Acc* A = J.chunkA + (size_t)w * M;
-  const uint32_t slot = threadIdx.x >> 2, q = threadIdx.x & 3;
+  const Acc* R = J.chunkR + (size_t)w * M;
+  const Acc* A = J.chunkA + (size_t)w * M;
+  const uint32_t slot = threadIdx.x / Coop::W;
+  const uint32_t q = threadIdx.x % Coop::W;
   const uint32_t per = (M + SLOTS - 1) / SLOTS;
   const uint32_t lo = slot * per, hi = (lo + per < M) ? lo + per : M;
-  typename C::Acc sumA = C::acc_inf(), run = C::acc_inf(), wsum = C::acc_inf();
+  Acc sumA = C::acc_inf(), run = C::acc_inf(), wsum = C::acc_inf();
   if (lo < M) {
 #pragma unroll 1
     for (uint32_t m = hi; m-- > lo;) {
-      wsum = add_quad<C>(wsum, run);
-      run = add_quad<C>(run, R[m]);
-      sumA = add_quad<C>(sumA, A[m]);
+      Coop::add(wsum, run);   // each R_m' ends up counted (m' - lo) times
+      Coop::add(run, R[m]);
+      Coop::add(sumA, A[m]);
     }
   }
+  // inclusive suffix scan of the slice totals
   if (q == 0) sh[slot] = run;
   __syncthreads();
-  typename C::Acc incl = run;
+  Acc incl = run;
 #pragma unroll 1
   for (int d = 1; d < SLOTS; d <<= 1) {
-    typename C::Acc other = C::acc_inf();
+    Acc other = C::acc_inf();
     const bool has = (int)slot + d < SLOTS;
     if (has) other = sh[slot + d];
     __syncthreads();
-    if (has) incl = add_quad<C>(incl, other);
+    if (has) Coop::add(incl, other);
     if (q == 0) sh[slot] = incl;
     __syncthreads();
   }
-  if (threadIdx.x == 0) J.wsum[65 + w] = incl;
-  typename C::Acc v = (slot >= 1 && lo < M) ? mul_small_quad<C>(incl, per) : C::acc_inf();
-  v = add_quad<C>(v, wsum);
-  v = mul_small_quad<C>(v, rc);
-  v = add_quad<C>(v, sumA);
-  const typename C::Acc tot = block_sum_quad<C, SLOTS>(v, sh);
-  if (threadIdx.x == 0) J.wsum[w] = tot;
+  if (threadIdx.x == 0) J.wsum[65 + w] = incl;   // wsum[65 .. 129]: sum of every bucket of this set
+  // v_t = RC * (per * suffix_t + wsum_t) + sumA_t
+  Acc v = (slot >= 1 && lo < M) ? Coop::mul_small(incl, per) : C::acc_inf();
+  Coop::add(v, wsum);
+  v = Coop::mul_small(v, rc);
+  Coop::add(v, sumA);
+  __syncthreads();
+  const Acc tot = block_sum<Coop, SLOTS>(slot, v, sh);
+  if (threadIdx.x == 0) J.wsum[w] = tot;   // wsum[0 .. 64]: set sums
 }
 
 // ---- K7: fold windows + canonical affine ------------------------------------------------------------
@@ -966,7 +916,6 @@ __global__ void __launch_bounds__(4 * SLOTS, tail_waves<C>()) msm_reduce2_quad(c
 // One wave; every lane carries the same running point, the doublings are wave-cooperative (dbl_coop).
 template <class C>
 __global__ void __launch_bounds__(64) msm_fold(const MsmBatch<C> B, uint32_t nwin, uint32_t c) {
-  tail_prio();
   const MsmJob<C>& J = B.job[blockIdx.y];
   const typename C::Acc* __restrict__ window_sum = J.wsum;
   typename C::Aff* __restrict__ out_aff = J.out_aff;
@@ -978,10 +927,7 @@ __global__ void __launch_bounds__(64) msm_fold(const MsmBatch<C> B, uint32_t nwi
       for (uint32_t i = 0; i < c; ++i) r = dbl_coop<C>(r);
     C::add(r, window_sum[w]);
   }
-  if (threadIdx.x == 0) {
-    if (out_acc) *out_acc = r;
-    if (out_aff) *out_aff = C::to_affine(r);
-  }
+  if (threadIdx.x == 0) job_finish<C>(out_acc, out_aff, r);
 }
 
 // ---- K7': fold for the merged bucket set of a registered point set ------------------------------------
@@ -1008,8 +954,7 @@ __device__ __forceinline__ typename C::Acc wave_allreduce(typename C::Acc v) {
   return wave_get_acc<C>(v, 0);
 }
 template <class C>
-__global__ void __launch_bounds__(128, tail_waves<C>()) msm_fold_merged(const MsmBatch<C> B, uint32_t nsets, uint32_t log2ks) {
-  tail_prio();
+__global__ void __launch_bounds__(128, 1) msm_fold_merged(const MsmBatch<C> B, uint32_t nsets, uint32_t log2ks) {
   __shared__ typename C::Acc ysum;
   const MsmJob<C>& J = B.job[blockIdx.y];
   const typename C::Acc* __restrict__ set_sum = J.wsum;
@@ -1039,8 +984,7 @@ __global__ void __launch_bounds__(128, tail_waves<C>()) msm_fold_merged(const Ms
   __syncthreads();
   if (threadIdx.x == 0) {
     C::add(xs, ysum);
-    if (out_acc) *out_acc = xs;
-    if (out_aff) *out_aff = C::to_affine(xs);
+    job_finish<C>(out_acc, out_aff, xs);
   }
 }
 
@@ -1051,28 +995,26 @@ __global__ void __launch_bounds__(128, tail_waves<C>()) msm_fold_merged(const Ms
 //   S = sum_v y_v + 2 Ks * sum_v e_v T_v ,   y_v = 4^z (2 W_v - T_v)  (X: 64 W_v),   e_v = 4^z sigma  (X: 0; all < 32).
 // Wave 1 forms the y_v (one doubling, one addition, <= 5 more doublings per lane) and all-reduces them; wave 0 forms
 // sum e_v T_v as the sum over sigma >= 1 of the per-class suffix sums of T (segmented shuffle scan), scaled by 4^z per
-// lane, all-reduces, applies the log2(2 Ks) doublings cooperatively and finishes.
+// lane, all-reduces, applies the log2(2 Ks) doublings cooperatively and finishes.  Which class a slice is in, where the
+// class begins and ends and how many doublings 4^z takes: msm_class_slice (msm_params.hpp), for this fold and the next.
 template <class C>
-__global__ void __launch_bounds__(128, tail_waves<C>()) msm_fold_classes(const MsmBatch<C> B, uint32_t log2ks) {
-  tail_prio();
+__global__ void __launch_bounds__(128, 1) msm_fold_classes(const MsmBatch<C> B, uint32_t log2ks) {
   __shared__ typename C::Acc ysum;
   const MsmJob<C>& J = B.job[blockIdx.y];
   const typename C::Acc* __restrict__ set_sum = J.wsum;
   const typename C::Acc* __restrict__ set_tot = J.wsum + 65;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  // class, slice inside the class, first lane of the next class
-  const int z = lane < 32 ? 0 : lane < 40 ? 1 : lane < 42 ? 2 : 3;
-  const int first = z == 0 ? 0 : z == 1 ? 32 : z == 2 ? 40 : 42, end = z == 0 ? 32 : z == 1 ? 40 : z == 2 ? 42 : 43;
+  const MsmClassSlice S = msm_class_slice(lane);
   const bool live = lane < (int)MSM_CLASS_SLICES;
   if (wave == 1) {
     typename C::Acc y = live ? set_sum[lane] : C::acc_inf();
     y = C::dbl(y);                                             // 2 W
-    if (live && z < 3) C::add(y, C::neg(set_tot[lane]));       // - T
-    const int nd = z == 0 ? 0 : z == 1 ? 2 : z == 2 ? 4 : 5;  // 4^z; X: 2 W -> 64 W
+    if (live && S.z < 3) C::add(y, C::neg(set_tot[lane]));     // - T
+    // 4^z (X: 2 W -> 64 W), branch-free: the lanes of a wave differ in their counts
 #pragma unroll 1
     for (int i = 0; i < 5; ++i) {
       typename C::Acc d = C::dbl(y);
-      if (i < nd) y = d;
+      if (i < S.dbl_y) y = d;
     }
     y = wave_allreduce<C>(y);
     if (lane == 0) ysum = y;
@@ -1080,18 +1022,17 @@ __global__ void __launch_bounds__(128, tail_waves<C>()) msm_fold_classes(const M
   typename C::Acc xs = C::acc_inf();
   if (wave == 0) {
     // inclusive suffix scan of T inside each class, then the suffixes of sigma >= 1, scaled by 4^z
-    typename C::Acc suf = (live && z < 3) ? set_tot[lane] : C::acc_inf();
+    typename C::Acc suf = (live && S.z < 3) ? set_tot[lane] : C::acc_inf();
 #pragma unroll 1
     for (int d = 1; d < 32; d <<= 1) {
       typename C::Acc other = wave_get_acc<C>(suf, (lane + d) & 63);
-      if (lane + d < end && z < 3) C::add(suf, other);
+      if (lane + d < S.end && S.z < 3) C::add(suf, other);
     }
-    if (lane == first || z == 3 || !live) suf = C::acc_inf();   // sigma = 0 carries weight 0
-    const int nd = z == 1 ? 2 : z == 2 ? 4 : 0;
+    if (lane == S.first || S.z == 3 || !live) suf = C::acc_inf();   // sigma = 0 carries weight 0
 #pragma unroll 1
     for (int i = 0; i < 4; ++i) {
       typename C::Acc d = C::dbl(suf);
-      if (i < nd) suf = d;
+      if (i < S.dbl_e) suf = d;
     }
     xs = wave_allreduce<C>(suf);
 #pragma unroll 1
@@ -1100,16 +1041,14 @@ __global__ void __launch_bounds__(128, tail_waves<C>()) msm_fold_classes(const M
   __syncthreads();
   if (threadIdx.x == 0) {
     C::add(xs, ysum);
-    if (J.out_acc) *J.out_acc = xs;
-    if (J.out_aff) *J.out_aff = C::to_affine(xs);
+    job_finish<C>(J.out_acc, J.out_aff, xs);
   }
 }
 
 // msm_fold_classes with a quad per slice: threads 0..255 (role A) form  sum e_v T_v  and finish, threads 256..511
 // (role B) form  sum y_v.  The barriers are shared, so B's slice-local doublings run while A scales its suffixes.
 template <class C>
-__global__ void __launch_bounds__(512, tail_waves<C>()) msm_fold_classes_quad(const MsmBatch<C> B, uint32_t log2ks) {
-  tail_prio();
+__global__ void __launch_bounds__(512, 1) msm_fold_classes_quad(const MsmBatch<C> B, uint32_t log2ks) {
   extern __shared__ __align__(16) unsigned char smem[];
   typename C::Acc* shA = reinterpret_cast<typename C::Acc*>(smem);   // 64 + 64 accumulators
   const MsmJob<C>& J = B.job[blockIdx.y];
@@ -1118,16 +1057,15 @@ __global__ void __launch_bounds__(512, tail_waves<C>()) msm_fold_classes_quad(co
   const bool roleB = threadIdx.x >= 256;
   typename C::Acc* sh = shA + (roleB ? 64 : 0);
   const int lane = (threadIdx.x & 255) >> 2, q = threadIdx.x & 3;   // "lane" = slice, as in msm_fold_classes
-  const int z = lane < 32 ? 0 : lane < 40 ? 1 : lane < 42 ? 2 : 3;
-  const int first = z == 0 ? 0 : z == 1 ? 32 : z == 2 ? 40 : 42, end = z == 0 ? 32 : z == 1 ? 40 : z == 2 ? 42 : 43;
+  const MsmClassSlice S = msm_class_slice(lane);
   const bool live = lane < (int)MSM_CLASS_SLICES;
   // A: inclusive suffix scan of T inside each class
-  typename C::Acc val = (!roleB && live && z < 3) ? set_tot[lane] : C::acc_inf();
+  typename C::Acc val = (!roleB && live && S.z < 3) ? set_tot[lane] : C::acc_inf();
   if (q == 0) sh[lane] = val;
   __syncthreads();
 #pragma unroll 1
   for (int d = 1; d < 32; d <<= 1) {
-    const bool has = !roleB && lane + d < end && z < 3;
+    const bool has = !roleB && lane + d < S.end && S.z < 3;
     typename C::Acc other = C::acc_inf();
     if (has) other = sh[lane + d];
     __syncthreads();
@@ -1136,19 +1074,19 @@ __global__ void __launch_bounds__(512, tail_waves<C>()) msm_fold_classes_quad(co
     __syncthreads();
   }
   if (!roleB) {
-    if (lane == first || z == 3 || !live) val = C::acc_inf();   // sigma = 0 carries weight 0
-    const int nd = z == 1 ? 2 : z == 2 ? 4 : 0;
+    if (lane == S.first || S.z == 3 || !live) val = C::acc_inf();   // sigma = 0 carries weight 0
 #pragma unroll 1
-    for (int i = 0; i < nd; ++i) val = dbl_quad<C>(val);
+    for (int i = 0; i < S.dbl_e; ++i) val = dbl_quad<C>(val);
   } else {
     val = live ? set_sum[lane] : C::acc_inf();
     val = dbl_quad<C>(val);                                                  // 2 W
-    if (live && z < 3) val = add_quad<C>(val, C::neg(set_tot[lane]));        // - T
-    const int nd = z == 0 ? 0 : z == 1 ? 2 : z == 2 ? 4 : 5;                // 4^z; X: 2 W -> 64 W
+    if (live && S.z < 3) val = add_quad<C>(val, C::neg(set_tot[lane]));      // - T
 #pragma unroll 1
-    for (int i = 0; i < nd; ++i) val = dbl_quad<C>(val);
+    for (int i = 0; i < S.dbl_y; ++i) val = dbl_quad<C>(val);                // 4^z; X: 2 W -> 64 W
   }
-  // both sums: the same tree on either half (block_sum_quad over 64 slots, indexed inside the role)
+  // both sums: block_sum's tree on either half, over the 64 slots of the role.  Written out here: the sums are needed
+  // on the first quad alone, which reads them from shA[0] and shA[64], and block_sum's hand-back to every thread (one
+  // more LDS read and barrier) measured 4 % on this fold (profiles/tail_policy_2p20.txt)
   __syncthreads();
   if (q == 0) sh[lane] = val;
   __syncthreads();
@@ -1165,10 +1103,7 @@ __global__ void __launch_bounds__(512, tail_waves<C>()) msm_fold_classes_quad(co
 #pragma unroll 1
     for (uint32_t i = 0; i < log2ks + 1; ++i) xs = dbl_quad<C>(xs);
     xs = add_quad<C>(xs, shA[64]);
-    if (threadIdx.x == 0) {
-      if (J.out_acc) *J.out_acc = xs;
-      if (J.out_aff) *J.out_aff = C::to_affine(xs);
-    }
+    if (threadIdx.x == 0) job_finish<C>(J.out_acc, J.out_aff, xs);
   }
 }
 

@@ -96,4 +96,17 @@ G16_MSMP_HD uint32_t msm_class_bucket(uint32_t t, uint32_t c, uint32_t& s) {
   const uint32_t base = z == 0 ? 0u : z == 1 ? h / 2 : h / 2 + h / 8;
   return base + v;
 }
+// Slice v of the class set (MSM_CLASS_SLICES slices of 2^(c-7) buckets, in msm_class_bucket's bucket order): its class
+// z (0, 1, 2; 3 = X), the slices [first, end) of that class, and the doublings that scale the slice's two terms in the
+// fold by 4^z (msm_fold_classes, msm.cuh): y_v = 4^z (2 W_v - T_v) starts from 2 W_v, so that X's 64 W_v takes 5;
+// e_v = 4^z sigma, and X has none.  v >= MSM_CLASS_SLICES (an idle lane of a fold) reads as class X.
+struct MsmClassSlice {
+  int z, first, end, dbl_y, dbl_e;
+};
+G16_MSMP_HD MsmClassSlice msm_class_slice(int v) {
+  const int z = v < 32 ? 0 : v < 40 ? 1 : v < 42 ? 2 : 3;
+  const int first = z == 0 ? 0 : z == 1 ? 32 : z == 2 ? 40 : 42;
+  const int end = z == 0 ? 32 : z == 1 ? 40 : z == 2 ? 42 : (int)MSM_CLASS_SLICES;
+  return MsmClassSlice{z, first, end, z == 0 ? 0 : z == 1 ? 2 : z == 2 ? 4 : 5, z == 1 ? 2 : z == 2 ? 4 : 0};
+}
 }  // namespace g16

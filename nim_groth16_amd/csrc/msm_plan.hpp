@@ -207,7 +207,7 @@ void msm_job_layout(J& j, const MsmParams& P, size_t nchunks, size_t asz, size_t
 }
 
 // ---- the tail: split-bucket combine, reduce1, reduce2, fold -----------------------------------------------------------
-enum class MsmR2 { QUAD128, QUAD64, WIDE, NARROW, WAVE };           // which msm_reduce2 / msm_reduce2_quad
+enum class MsmR2 { QUAD128, QUAD64, WIDE, NARROW, WAVE };           // which msm_reduce2<C, Quad / Lane, slots>
 enum class MsmFold { CLASSES_QUAD, CLASSES, MERGED, PLAIN };        // which msm_fold*
 struct MsmTailPlan {
   uint32_t rc;          // buckets per chunk (msm_red_chunk)
@@ -257,18 +257,19 @@ inline MsmTailPlan msm_tail_plan(const MsmParams& P, bool is_g1, bool narrow_tai
   }
   T.cps = (uint32_t)(T.nchunks / T.nsets);
   // reduce2 is a latency chain (serial chunk sums -> Hillis-Steele suffix scan -> tree).
-  // Default: the quad-cooperative kernels (msm.cuh: an addition in 4 multiplications of wave time instead of 14;
+  // Default: a cooperating quad per slot (Quad, msm.cuh: an addition in 4 multiplications of wave time instead of 14;
   // tools/ubench_quad.hip: 2.1-2.4 x per operation), 64 slots per slice (128 for G1 slices of >= 512 chunks; G2 at 512
   // threads would have to live in 256 registers).  Shards: 2.71-2.94 -> 2.61-2.82 ms per rank at G = 8; stand-alone 2^20
   // MSM 2.18 -> 2.00 ms (G1), 5.21 -> 4.87 (G2); 2^20 proofs: single-proof latency 10.79 -> 10.59 and 10.84 -> 10.54 ms in
   // two sessions, proofs/s 121.57 -> 120.91 and 119.23 -> 120.63, i.e. inside the noise (profiles/r04_ab_tail_quad.txt,
   // r04_ab_g2first_2p20.txt, r04_perf_reg_quad.txt).
-  // G16_TAIL_QUAD=0 or any G16_R2_WIDTH selects the one-lane-per-slot kernels of rounds 1-3.  There every scan step costs
-  // one group addition on EVERY wave of the workgroup: wide workgroups (512 / 256 threads: one chunk per thread) have the
-  // shortest chain; narrow ones (128 / 64 threads: four chunks per thread, work-efficient serial sums, a 7- / 6-step
-  // scan) issue ~2.5x fewer wave-instructions for a ~20 % longer chain and were the choice inside proofs (same-box A/B,
-  // profiles/r03_ab_knobs.txt: 111.6 -> 114.7 proofs/s, 11.67 -> 11.85 ms), wide for stand-alone MSMs and for 4-bucket
-  // chunks.  G16_R2_WIDTH = 0 / 1 / 2 forces wide / narrow / a single wave per slice.
+  // G16_TAIL_QUAD=0 or any G16_R2_WIDTH selects one lane per slot (Lane, the form of rounds 1-3) and the wave-shuffle
+  // fold.  There every scan step costs one group addition on EVERY wave of the workgroup: wide workgroups (512 / 256
+  // threads: one chunk per thread) have the shortest chain; narrow ones (128 / 64 threads: four chunks per thread,
+  // work-efficient serial sums, a 7- / 6-step scan) issue ~2.5x fewer wave-instructions for a ~20 % longer chain and
+  // were the choice inside proofs (same-box A/B, profiles/r03_ab_knobs.txt: 111.6 -> 114.7 proofs/s, 11.67 -> 11.85
+  // ms), wide for stand-alone MSMs and for 4-bucket chunks.  G16_R2_WIDTH = 0 / 1 / 2 forces wide / narrow / a single
+  // wave per slice.
   const uint32_t wide = is_g1 ? 512u : 256u;
   const bool quad = env.r2_width < 0 && env.tail_quad != 0;
   if (quad) {

@@ -53,19 +53,19 @@ int32_t stage_reduce2_fold(g16_ctx* ctx, hipStream_t st, const MsmParams& P, con
   const size_t lds = T.r2_lds * sizeof(typename C::Acc);
   switch (T.r2) {
     case MsmR2::QUAD128:
-      KLAUNCH_ON(ctx, st, nm, (msm_reduce2_quad<C, is_g1 ? 128 : 64>), grid, T.r2_threads, lds, B, T.cps, T.rc);
+      KLAUNCH_ON(ctx, st, nm, (msm_reduce2<C, Quad<C>, is_g1 ? 128 : 64>), grid, T.r2_threads, lds, B, T.cps, T.rc);
       break;
     case MsmR2::QUAD64:
-      KLAUNCH_ON(ctx, st, nm, (msm_reduce2_quad<C, 64>), grid, T.r2_threads, lds, B, T.cps, T.rc);
+      KLAUNCH_ON(ctx, st, nm, (msm_reduce2<C, Quad<C>, 64>), grid, T.r2_threads, lds, B, T.cps, T.rc);
       break;
     case MsmR2::WIDE:
-      KLAUNCH_ON(ctx, st, nm, (msm_reduce2<C, R2B>), grid, T.r2_threads, lds, B, T.cps, T.rc);
+      KLAUNCH_ON(ctx, st, nm, (msm_reduce2<C, Lane<C>, R2B>), grid, T.r2_threads, lds, B, T.cps, T.rc);
       break;
     case MsmR2::WAVE:
-      KLAUNCH_ON(ctx, st, nm, (msm_reduce2<C, 64>), grid, T.r2_threads, lds, B, T.cps, T.rc);
+      KLAUNCH_ON(ctx, st, nm, (msm_reduce2<C, Lane<C>, 64>), grid, T.r2_threads, lds, B, T.cps, T.rc);
       break;
     case MsmR2::NARROW:
-      KLAUNCH_ON(ctx, st, nm, (msm_reduce2<C, R2N>), grid, T.r2_threads, lds, B, T.cps, T.rc);
+      KLAUNCH_ON(ctx, st, nm, (msm_reduce2<C, Lane<C>, R2N>), grid, T.r2_threads, lds, B, T.cps, T.rc);
       break;
   }
   nm = g2 ? "msm_fold_g2" : "msm_fold_g1";

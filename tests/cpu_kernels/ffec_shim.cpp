@@ -252,6 +252,12 @@ uint32_t shim_class_buckets_check(uint32_t c) {
   return nb == h / 2 + h / 8 + h / 32 + h / 64 && nb % (MSM_CLASS_SLICES) == 0 && nb / MSM_CLASS_SLICES == (1u << (c - 7)) ? 0 : 1;
 }
 
+// msm_class_slice (msm_params.hpp) as the class folds read it -> out[5] = z, first, end, doublings of y_v, of e_v
+void shim_class_slice(int v, int32_t* out) {
+  const MsmClassSlice s = msm_class_slice(v);
+  out[0] = s.z, out[1] = s.first, out[2] = s.end, out[3] = s.dbl_y, out[4] = s.dbl_e;
+}
+
 // op: 0 add 1 sub 2 mul 3 sqr 4 neg 5 dbl 6 div2 7 inv 8 from_mont 9 to_mont ; field: 0 Fp 1 Fr
 void shim_field_op(int field, int op, const void* a, const void* b, void* r) {
   u256 x = ld<u256>(a), y = ld<u256>(b), z;

@@ -319,3 +319,32 @@ def test_plan_boundaries(shim):  # noqa: F811
     # the split-bucket combine: 1024 workgroups for one job, 512 each for a batch, or what G16_HEAVY_GRID says
     p = run_plan(shim, n, True, True, False, {"G16_HEAVY_GRID": "64"})
     assert (p.heavy1, p.heavy3) == (64, 64)
+
+
+def test_class_slice_geometry(shim):  # noqa: F811
+    """msm_class_slice (msm_params.hpp), which both class folds read: the classes cut the 43 slices into 32 + 8 + 2 + 1,
+    and the doublings it hands the folds give the first bucket of every slice the weight that class_weight of
+    tests/msm_pictures.py -- the inverse of msm_class_bucket, which knows nothing of slices -- says it has"""
+    from tests.msm_pictures import class_weight                      # imported here: that module imports this one
+
+    def class_slice(v):
+        out = (ctypes.c_int32 * 5)()
+        shim.shim_class_slice(v, out)
+        return tuple(out)
+    slices = [class_slice(v) for v in range(CLASS_SLICES)]
+    classes = sorted({(z, first, end) for z, first, end, _, _ in slices})
+    assert [end - first for _, first, end in classes] == [32, 8, 2, 1]
+    assert [z for z, _, _ in classes] == [0, 1, 2, 3] and classes[0][1] == 0 and classes[-1][2] == CLASS_SLICES
+    assert all(a[2] == b[1] for a, b in zip(classes, classes[1:]))
+    for v, (z, first, end, dbl_y, dbl_e) in enumerate(slices):
+        assert first <= v < end
+        assert (dbl_y, dbl_e) == ((2 * z, 2 * z) if z < 3 else (5, 0))
+    # the fold's  S = sum_v y_v + 2 Ks sum_v e_v T_v  at slice-local weight l = 1 (W_v = T_v = B, one bucket):
+    # y_v = 2^dbl_y (2 W_v - T_v)  (X: 2^dbl_y * 2 W_v),  e_v = 2^dbl_e * sigma  (X: none)
+    for c in (15, 20):
+        ks = 1 << (c - 7)
+        for v, (z, first, end, dbl_y, dbl_e) in enumerate(slices):
+            sigma = v - first
+            y, e = ((1 << dbl_y) * (2 - 1), (1 << dbl_e) * sigma) if z < 3 else ((1 << dbl_y) * 2, 0)
+            assert y + 2 * ks * e == class_weight(v * ks, c), (c, v)
+            assert class_weight(v * ks, c) == (4 ** z * (2 * sigma * ks + 1) if z < 3 else 64)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Build a variant of libg16hip.so out of tree (objects of the tree are reused where the flags do not touch them):
 #   bash tools/build_variant.sh NAME "make variables" obj1.o obj2.o ...   -> nim_groth16_amd/csrc/build_variants/libg16hip_NAME.so
-# e.g. bash tools/build_variant.sh t4 'TAIL_FLAGS="-DG16_TAIL_WAVES_G1=4 -DG16_TAIL_WAVES_G2=2"' msm_g1_reduce1.o msm_g1_reduce2.o
+# e.g. bash tools/build_variant.sh serial 'G1_ACCUM_FLAGS=-DG16_F29_SERIAL' msm_g1_accum.o
 set -e
 name=$1; vars=$2; shift 2
 src=$(cd "$(dirname "$0")/../nim_groth16_amd/csrc" && pwd)
