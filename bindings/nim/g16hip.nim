@@ -361,6 +361,40 @@ proc auditKey*(zkey: ZKey): KeyReport =
       if any: break
   check g16_key_audit(gctx, addr d, addr v, nil, 0, addr zs[0], addr result)
 
+# --- circuit audit (include/g16hip.h "circuit audit"): does the key belong to THIS .r1cs and THIS .ptau? ---------------
+# What `snarkjs zkey verify circuit.r1cs pot.ptau circuit.zkey` checks before the contribution chain: the key's
+# coefficients against the r1cs as linear maps, every point array of the key against the powers of tau.  Declarations
+# only: the caller fills the two descriptions from its own r1cs / ptau readers and draws the multipliers (nvars and
+# 2^log2_domain of them, 16 bytes each, none zero) from the OS CSPRNG as auditKey does.
+const
+  G16_PTAU_SECTIONS* = 5
+  G16_CIRCUIT_RELATIONS* = 9
+  ptauSectionNames* = ["tauG1", "tauG2", "alphaTauG1", "betaTauG1", "betaG2"]
+  circuitRelationNames* = ["COEFFS_A", "COEFFS_B", "SPEC", "A1", "B1", "B2", "C1", "IC", "H1"]
+type
+  G16R1csDesc* {.importc: "g16_r1cs_desc", header: "g16hip.h".} = object
+    nvars*, npubs*, nconstraints*, flavour*: uint32
+    row*, col*: array[3, ptr uint32]
+    val*: array[3, pointer]
+    nnz*: array[3, csize_t]
+    flags*: uint32
+  G16PtauDesc* {.importc: "g16_ptau_desc", header: "g16hip.h".} = object
+    power*: uint32
+    tauG1*, tauG2*, alphaTauG1*, betaTauG1*, betaG2*: pointer
+  CircuitReport* {.importc: "g16_circuit_report", header: "g16hip.h".} = object
+    key*: KeyReport
+    ptau_first_bad*: array[G16_PTAU_SECTIONS, array[3, csize_t]]
+    ptau_bad_count*: array[G16_PTAU_SECTIONS, array[3, csize_t]]
+    relation*: array[G16_CIRCUIT_RELATIONS, int32]   ## 1 holds, 0 fails, -1 not run
+    failed*: uint32                                   ## OR of G16_CIRCUIT_*: 0 = belongs to the circuit and the ptau
+    first_row*: array[2, csize_t]                     ## COEFFS_A / COEFFS_B: first differing row, high(csize_t) = none
+
+proc g16_circuit_audit(ctx: ptr G16Ctx, desc: ptr G16PKeyDesc, vk: ptr G16VKeyDesc, section4: pointer,
+                       section4Bytes: csize_t, r1cs: ptr G16R1csDesc, ptau: ptr G16PtauDesc, wireMultipliers,
+                       hMultipliers: pointer, res: ptr CircuitReport): int32 {.importc, header: "g16hip.h".}
+
+proc ok*(r: CircuitReport): bool = r.failed == 0
+
 # --- drop-in for fakeCircuitSetup (groth16/fake_setup.nim:201-326): one g16_fake_setup call ----------------------------
 # The Lagrange values, the column sums, the combinations and the H scalars are formed on the device and stay in HBM; the
 # points come back into the seqs of the ZKey.  ZKey.coeffs is the reference's own r1csToCoeffs (fake_setup.nim:46-65).

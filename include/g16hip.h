@@ -536,11 +536,94 @@ typedef struct {
  * Every array is uploaded whole, one at a time, into the context's staging buffer; all work runs on the context's
  * stream with one wait after the element passes (the relations run only on sections whose every element passed)
  * and one at the end.
- * What the audit CANNOT establish: that the key belongs to any circuit.  Nothing ties pointsA1 / pointsC1 / pointsH1 /
- * pointsIC (or the values of alpha, beta, gamma, delta) to an R1CS without the ceremony transcript; a key can pass
- * every check here and still prove nothing about the statement its user has in mind. */
+ * What the audit CANNOT establish: that the key belongs to any circuit.  Nothing in the key alone ties pointsA1 /
+ * pointsC1 / pointsH1 / pointsIC (or the values of alpha, beta, gamma, delta) to an R1CS; a key can pass every check
+ * here and still prove nothing about the statement its user has in mind.  A caller who also holds the circuit's .r1cs
+ * and the ceremony's .ptau can establish that tie: g16_circuit_audit, below. */
 int32_t g16_key_audit(g16_ctx* ctx, const g16_pkey_desc* desc, const g16_vkey_desc* vk, const void* section4,
                       size_t section4_bytes, const void* multipliers, g16_key_report* out);
+
+/* ---- circuit audit: does an UNTRUSTED proving key belong to THIS circuit and THIS powers of tau? --------------------
+ * What `snarkjs zkey verify circuit.r1cs pot.ptau circuit.zkey` checks before it walks the contribution chain; the
+ * reference lists a piece of it as open ("compare .r1cs to the 'coeffs' section of .zkey").  The caller's multipliers
+ * z (one per wire) are treated as a witness: buildABC over the key's coefficients and the same products over the R1CS
+ * must agree, and every point array of the key, combined with z, must equal the matching combination of the powers of
+ * tau.  Like the key audit the call changes no state: a context proves the same bytes before and after.  Host pointers.
+ *
+ * g16_r1cs_desc: the R1CS as triplets, the first members of g16_setup_desc under the same rules (entries of one
+ *   (constraint, wire) add up; the library adds snarkjs's dummy A entries (nconstraints + i, wire i, 1), i <= npubs).
+ * g16_ptau_desc: sections 2..6 of a .ptau, Montgomery affine like every point here. */
+typedef struct {
+  uint32_t nvars, npubs, nconstraints;
+  uint32_t flavour;         /* must equal the key's */
+  const uint32_t* row[3];
+  const uint32_t* col[3];
+  const void* val[3];
+  size_t nnz[3];
+  uint32_t flags;           /* G16_SCALARS_MONT or G16_SCALARS_STD for val */
+} g16_r1cs_desc;
+typedef struct {
+  uint32_t power;           /* tauG1: 2^(power+1) - 1 points; tauG2, alphaTauG1, betaTauG1: 2^power; betaG2: 1 */
+  const void *tauG1, *tauG2, *alphaTauG1, *betaTauG1, *betaG2;
+} g16_ptau_desc;
+#define G16_PTAU_SECTIONS 5
+#define G16_CIRCUIT_RELATIONS 9
+enum {
+  G16_PTAU_TAU_G1 = 0, G16_PTAU_TAU_G2, G16_PTAU_ALPHA_TAU_G1, G16_PTAU_BETA_TAU_G1, G16_PTAU_BETA_G2
+};
+enum {
+  G16_REL_COEFFS_A = 0, G16_REL_COEFFS_B, G16_REL_SPEC, G16_REL_A1, G16_REL_B1, G16_REL_B2, G16_REL_C1, G16_REL_IC,
+  G16_REL_H1
+};
+#define G16_CIRCUIT_KEY 1u     /* the key's own report has failed != 0 */
+#define G16_CIRCUIT_PTAU 2u    /* an element of a ptau array fails a check of g16_points_audit_* */
+#define G16_CIRCUIT_COEFFS 4u  /* COEFFS_A or COEFFS_B fails */
+#define G16_CIRCUIT_SPEC 8u    /* SPEC fails */
+#define G16_CIRCUIT_POINTS 16u /* A1, B1, B2, C1, IC or H1 fails */
+typedef struct {
+  g16_key_report key;       /* exactly what g16_key_audit(ctx, desc, vk, section4, section4_bytes, wire_multipliers) reports */
+  /* the five ptau arrays (G16_PTAU_*), only the elements the call reads -- tauG1[0 .. 2n), tauG2 / alphaTauG1 /
+   * betaTauG1 [0 .. n), betaG2 -- per check as g16_points_audit_*; check [2] applies to tauG2 and betaG2 */
+  size_t ptau_first_bad[G16_PTAU_SECTIONS][3];
+  size_t ptau_bad_count[G16_PTAU_SECTIONS][3];
+  int32_t relation[G16_CIRCUIT_RELATIONS]; /* G16_REL_*: 1 = holds, 0 = fails, -1 = not run */
+  uint32_t failed;          /* OR of G16_CIRCUIT_*; 0 = the key belongs to the circuit and the powers of tau */
+  size_t first_row[2];      /* COEFFS_A / COEFFS_B: the first row of the domain where the two products differ, (size_t)-1: none */
+} g16_circuit_report;
+/* Write n = 2^log2_domain, coef_m(v) = the inverse NTT of v on the m-point domain, z|pub = z with the wires above npubs
+ * zeroed, z|priv = z - z|pub.  Every matrix-vector product includes the dummy A entries.  The relations:
+ *   COEFFS_A, COEFFS_B  A_key z == A_r1cs z as vectors of n Fr values, for z|pub and for z|priv (B likewise): a comparison
+ *             of linear maps -- entry order, duplicates that add up and explicit zeros in either description do not matter
+ *   SPEC      alpha1 == alphaTauG1[0], beta1 == betaTauG1[0], beta2 == betaG2 byte for byte; tauG1[0], tauG2[0] = gen1, gen2
+ *   A1        MSM(z, pointsA1) == MSM(coef_n(A z), tauG1[0..n))                     (A, B, C below: the R1CS's matrices)
+ *   B1, B2    the same with B, against tauG1 and tauG2
+ *   C1        e(MSM(z|priv, pointsC1), delta2) == e(R, gen2),  R = MSM(coef_n(A z|priv), betaTauG1)
+ *             + MSM(coef_n(B z|priv), alphaTauG1) + MSM(coef_n(C z|priv), tauG1); no private wire: holds trivially (1)
+ *   IC        the same over z|pub with gamma2 and pointsIC; -1 when vk == NULL
+ *   H1        e(MSM(y, pointsH1), delta2) == e(MSM(c, tauG1[0..2n)), gen2), y = h_multipliers; snarkjs flavour:
+ *             c = coef_2n(v), v[2i+1] = y_i, v[even] = 0; JensGroth: c[i] = -y_i, c[n+i] = +y_i
+ * A relation is -1 if a section it reads failed an element check (SPEC reads alpha1, beta1, beta2 and all five ptau
+ * arrays; COEFFS_* the key's coefficients): nothing is evaluated on points that are not canonical members of their group.
+ * wire_multipliers: nvars x 16 bytes, h_multipliers: n x 16 bytes, under the rules of g16_verify_batch: little-endian
+ * 128-bit integers, every one non-zero, drawn by the CALLER from a CSPRNG after every input is fixed; the library draws
+ * nothing.  A zero multiplier is G16_EINVAL and g16_last_error names its index.
+ * Soundness, as for g16_verify_batch: write every point of the key as its logarithm times the generator.  If the
+ * logarithm of any point differs from the value its circuit and the powers of tau give it (or any entry of A_key - A_r1cs,
+ * B_key - B_r1cs is non-zero), the relation that covers it is a non-zero linear form in the multipliers over Fr, and
+ * r > 2^128: it reports 1 with probability at most 1/(2^128 - 1) over multipliers uniform in the non-zero 128-bit values
+ * and independent of the inputs.
+ * G16_EINVAL, checked on the host before anything is queued: a null pointer; r1cs->nvars or npubs different from the
+ * key's; ceilingLog2(nconstraints + npubs + 1) != log2_domain; a flavour mismatch; an R1CS entry out of range or not
+ * canonical; ptau->power < log2_domain + 1 (the rule of `snarkjs zkey new`: tau^(2n-1) is needed and tauG1 holds
+ * 2^(power+1) - 1 powers); a sharded key description; everything g16_key_audit rejects.
+ * What the call does NOT cover:
+ *   - the ptau is the trusted anchor: its self-consistency (`snarkjs powersoftau verify`) is out of scope;
+ *   - the phase-2 contribution chain and its hashes (section 10 of a .zkey) are out of scope;
+ *   - gamma and delta are taken from the key: a legitimately contributed key (delta changed, pointsC1 and pointsH1
+ *     rescaled) passes, as it should. */
+int32_t g16_circuit_audit(g16_ctx* ctx, const g16_pkey_desc* desc, const g16_vkey_desc* vk, const void* section4,
+                          size_t section4_bytes, const g16_r1cs_desc* r1cs, const g16_ptau_desc* ptau,
+                          const void* wire_multipliers, const void* h_multipliers, g16_circuit_report* out);
 
 /* ---- profiling ---------------------------------------------------------------------------------- */
 /* on = 1: every kernel launch is bracketed by HIP events on the stream it is launched on; on = 2: only the

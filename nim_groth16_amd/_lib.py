@@ -33,7 +33,7 @@ SYMBOLS = [
     "g16_pkey_create_zkey_lean", "g16_group_pkey_create_lean",
     "g16_setup_log2_domain", "g16_fake_setup", "g16_lagrange_fr", "g16_powers_fr",
     "g16_points_audit_g1", "g16_points_audit_g2", "g16_points_pairs_check", "g16_key_audit",
-    "g16_pkey_b1_fold",
+    "g16_pkey_b1_fold", "g16_circuit_audit",
 ]
 VERIFY_SUBGROUP = 16
 GT_BYTES = 384
@@ -132,6 +132,82 @@ class KeyReport:
             skipped = [AUDIT_RELATIONS[k] for k in range(3) if self.relation[k] < 0]
             return "key audit: ok" + (f" (not run: {', '.join(skipped)})" if skipped else "")
         return "key audit: FAILED\n" + "\n".join("  " + f for f in self.findings())
+
+
+class R1csDesc(ctypes.Structure):
+    """g16_r1cs_desc (include/g16hip.h): the first members of g16_setup_desc"""
+    _fields_ = [("nvars", ctypes.c_uint32), ("npubs", ctypes.c_uint32), ("nconstraints", ctypes.c_uint32),
+                ("flavour", ctypes.c_uint32),
+                ("row", ctypes.c_void_p * 3), ("col", ctypes.c_void_p * 3), ("val", ctypes.c_void_p * 3),
+                ("nnz", ctypes.c_size_t * 3), ("flags", ctypes.c_uint32)]
+
+
+class PtauDesc(ctypes.Structure):
+    """g16_ptau_desc (include/g16hip.h)"""
+    _fields_ = [("power", ctypes.c_uint32), ("tauG1", ctypes.c_void_p), ("tauG2", ctypes.c_void_p),
+                ("alphaTauG1", ctypes.c_void_p), ("betaTauG1", ctypes.c_void_p), ("betaG2", ctypes.c_void_p)]
+
+
+# circuit audit (include/g16hip.h): the ptau arrays and the relations of a report in order, the bits of `failed`
+PTAU_SECTIONS = ("tauG1", "tauG2", "alphaTauG1", "betaTauG1", "betaG2")
+PTAU_GROUP = {"tauG1": 1, "tauG2": 2, "alphaTauG1": 1, "betaTauG1": 1, "betaG2": 2}
+CIRCUIT_RELATIONS = ("COEFFS_A", "COEFFS_B", "SPEC", "A1", "B1", "B2", "C1", "IC", "H1")
+CIRCUIT_KEY, CIRCUIT_PTAU, CIRCUIT_COEFFS, CIRCUIT_SPEC, CIRCUIT_POINTS = 1, 2, 4, 8, 16
+
+
+class CircuitReportC(ctypes.Structure):
+    """g16_circuit_report (include/g16hip.h)"""
+    _fields_ = [("key", KeyReportC),
+                ("ptau_first_bad", (ctypes.c_size_t * 3) * len(PTAU_SECTIONS)),
+                ("ptau_bad_count", (ctypes.c_size_t * 3) * len(PTAU_SECTIONS)),
+                ("relation", ctypes.c_int32 * len(CIRCUIT_RELATIONS)), ("failed", ctypes.c_uint32),
+                ("first_row", ctypes.c_size_t * 2)]
+
+
+class CircuitReport:
+    """What g16_circuit_audit found: `key`, the KeyReport of the key on its own; ptau_first_bad / ptau_bad_count
+    [array][check] for PTAU_SECTIONS as in a KeyReport; relation[k] = 1 (holds), 0 (fails) or -1 (not run) for
+    CIRCUIT_RELATIONS[k]; first_row[m] = the first row where matrix A (m = 0) / B (m = 1) of the key and of the r1cs
+    act differently on the multipliers, or None."""
+
+    def __init__(self, key: KeyReport, ptau_first_bad, ptau_bad_count, relation, failed, first_row):
+        self.key, self.ptau_first_bad, self.ptau_bad_count = key, ptau_first_bad, ptau_bad_count
+        self.relation, self.failed, self.first_row = list(relation), failed, list(first_row)
+
+    @property
+    def ok(self) -> bool:
+        """the key is fit to prove with and belongs to the circuit and the powers of tau"""
+        return self.failed == 0
+
+    def as_dict(self) -> dict:
+        return {"key": self.key.as_dict(), "ptau_first_bad": self.ptau_first_bad, "ptau_bad_count": self.ptau_bad_count,
+                "relation": self.relation, "failed": self.failed, "first_row": self.first_row}
+
+    def findings(self):
+        out = list(self.key.findings())
+        for s, name in enumerate(PTAU_SECTIONS):
+            for k, check in enumerate(AUDIT_CHECKS):
+                if self.ptau_bad_count[s][k]:
+                    what = {"canonical": "is not a canonical encoding", "curve": "is not on the curve",
+                            "subgroup": "is not in the order-r subgroup"}[check]
+                    more = self.ptau_bad_count[s][k] - 1
+                    out.append(f"ptau {name}[{self.ptau_first_bad[s][k]}] {what}" + (f" (and {more} more)" if more else ""))
+        for m in range(2):
+            if self.relation[m] == 0:
+                out.append(f"coeffs: matrix {'AB'[m]} differs from the r1cs first at row {self.first_row[m]}")
+        if self.relation[2] == 0:
+            out.append("alpha1 / beta1 / beta2 are not those of the powers of tau (or its first powers are not the generators)")
+        for k in range(3, len(CIRCUIT_RELATIONS)):
+            if self.relation[k] == 0:
+                out.append(f"points{CIRCUIT_RELATIONS[k]} does not belong to the circuit")
+        return out
+
+    def __str__(self):
+        if self.ok:
+            skipped = [AUDIT_RELATIONS[k] for k in range(3) if self.key.relation[k] < 0]
+            skipped += [CIRCUIT_RELATIONS[k] for k in range(len(CIRCUIT_RELATIONS)) if self.relation[k] < 0]
+            return "circuit audit: ok" + (f" (not run: {', '.join(skipped)})" if skipped else "")
+        return "circuit audit: FAILED\n" + "\n".join("  " + f for f in self.findings())
 
 
 class G16Error(RuntimeError):
@@ -288,6 +364,9 @@ def load_library():
     lib.g16_points_pairs_check.argtypes = [vp, vp, vp, sz, vp, ctypes.POINTER(i32)]
     lib.g16_key_audit.argtypes = [vp, ctypes.POINTER(PkeyDesc), ctypes.POINTER(VkeyDesc), vp, sz, vp,
                                   ctypes.POINTER(KeyReportC)]
+    lib.g16_circuit_audit.argtypes = [vp, ctypes.POINTER(PkeyDesc), ctypes.POINTER(VkeyDesc), vp, sz,
+                                      ctypes.POINTER(R1csDesc), ctypes.POINTER(PtauDesc), vp, vp,
+                                      ctypes.POINTER(CircuitReportC)]
     for name in SYMBOLS:
         if name not in ("g16_ctx_destroy", "g16_last_error", "g16_points_release", "g16_points_count",
                         "g16_points_inf_count",
@@ -448,6 +527,32 @@ class Context:
         return KeyReport(rep.failed, rep.spec_infinity, list(rep.relation),
                          [[None if f == none else f for f in row] for row in rep.first_bad],
                          [list(row) for row in rep.bad_count])
+
+    def circuit_audit(self, desc: PkeyDesc, vk, section4, r1cs: R1csDesc, ptau: PtauDesc, wire_multipliers,
+                      h_multipliers) -> CircuitReport:
+        """g16_circuit_audit.  desc / vk / section4 as for key_audit; r1cs, ptau: the two descriptions (the caller keeps
+        their buffers alive); wire_multipliers: desc.nvars ints in [1, 2^128), h_multipliers: 2^log2_domain of them (or
+        their 16-byte encodings, joined), drawn by the caller after every input is fixed."""
+        def enc(zs, n, what):
+            if isinstance(zs, (bytes, bytearray)):
+                assert len(zs) == 16 * n, f"one {what} multiplier of 16 bytes each"
+                return bytes(zs)
+            assert len(zs) == n, f"{n} {what} multipliers"
+            return b"".join(int(z).to_bytes(16, "little") for z in zs)
+        zw = enc(wire_multipliers, desc.nvars, "wire")
+        zh = enc(h_multipliers, 1 << min(desc.log2_domain, 28), "h")
+        rep = CircuitReportC()
+        self._check(self._lib.g16_circuit_audit(self._h, ctypes.byref(desc), ctypes.byref(vk) if vk is not None else None,
+                                                _buf(section4) if section4 is not None else None,
+                                                len(section4) if section4 is not None else 0,
+                                                ctypes.byref(r1cs), ctypes.byref(ptau), _buf(zw), _buf(zh),
+                                                ctypes.byref(rep)))
+        none = ctypes.c_size_t(-1).value
+        fix = lambda rows: [[None if f == none else f for f in row] for row in rows]     # noqa: E731
+        key = KeyReport(rep.key.failed, rep.key.spec_infinity, list(rep.key.relation), fix(rep.key.first_bad),
+                        [list(row) for row in rep.key.bad_count])
+        return CircuitReport(key, fix(rep.ptau_first_bad), [list(row) for row in rep.ptau_bad_count], list(rep.relation),
+                             rep.failed, [None if f == none else f for f in rep.first_row])
 
     def fixed_base(self, group: int, scalars: bytes, mont: bool = True) -> bytes:
         """scalars[i] * generator -> affine points (fake_setup.nim:258-261 `y ** gen1/gen2`)."""

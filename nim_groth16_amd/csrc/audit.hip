@@ -87,8 +87,10 @@ int32_t points_audit(g16_ctx* ctx, const void* points, size_t n, size_t first_ba
   return G16_OK;
 }
 
+}  // namespace
+
 // 16-byte multipliers -> 32-byte standard scalars; the index of a zero one goes to the error text
-int32_t widen_multipliers(g16_ctx* ctx, const char* who, const void* multipliers, size_t n, std::vector<uint64_t>& out) {
+int32_t g16_widen_multipliers(g16_ctx* ctx, const char* who, const void* multipliers, size_t n, std::vector<uint64_t>& out) {
   try {
     out.assign(4 * n, 0);
   } catch (const std::bad_alloc&) {
@@ -104,6 +106,28 @@ int32_t widen_multipliers(g16_ctx* ctx, const char* who, const void* multipliers
   }
   return G16_OK;
 }
+
+// the element passes of `nsec` arrays on their own (the ptau arrays of the circuit audit): one wait at the end
+int32_t g16_audit_sections(g16_ctx* ctx, const g16_audit_section* sec, int nsec, size_t (*first_bad)[3],
+                           size_t (*bad_count)[3]) {
+  std::vector<AuditCounts> h(nsec);
+  counts_reset(h.data(), nsec);
+  DevMem<AuditCounts> d_counts;
+  SyncOnExit drain{ctx->stream};
+  HIPCHK(ctx, dev_alloc(d_counts, nsec * sizeof(AuditCounts)));
+  HIPCHK(ctx, hipMemcpyAsync(d_counts.get(), h.data(), nsec * sizeof(AuditCounts), hipMemcpyHostToDevice, ctx->stream));
+  for (int s = 0; s < nsec; ++s) {
+    const int32_t rc = sec[s].group == 1 ? audit_array<G1>(ctx, sec[s].p, sec[s].n, d_counts.get() + s)
+                                         : audit_array<G2>(ctx, sec[s].p, sec[s].n, d_counts.get() + s);
+    if (rc) return rc;
+  }
+  HIPCHK(ctx, hipMemcpyAsync(h.data(), d_counts.get(), nsec * sizeof(AuditCounts), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  for (int s = 0; s < nsec; ++s) counts_out(h[s], first_bad[s], bad_count[s]);
+  return G16_OK;
+}
+
+namespace {
 
 // device scratch of the relations: a[3] | b[3] | result[3]
 struct RelBuf {
@@ -153,7 +177,7 @@ extern "C" int32_t g16_points_pairs_check(g16_ctx* ctx, const void* g1_points, c
   }
   std::vector<uint64_t> scalars;
   int32_t rc;
-  if ((rc = widen_multipliers(ctx, "g16_points_pairs_check", multipliers, n, scalars))) return rc;
+  if ((rc = g16_widen_multipliers(ctx, "g16_points_pairs_check", multipliers, n, scalars))) return rc;
   *result = 1;
   if (!n) return G16_OK;
   CTX_ENTER(ctx);
@@ -169,6 +193,12 @@ extern "C" int32_t g16_points_pairs_check(g16_ctx* ctx, const void* g1_points, c
 
 extern "C" int32_t g16_key_audit(g16_ctx* ctx, const g16_pkey_desc* d, const g16_vkey_desc* vk, const void* section4,
                                  size_t section4_bytes, const void* multipliers, g16_key_report* out) {
+  return g16_key_audit_body(ctx, d, vk, section4, section4_bytes, multipliers, out);
+}
+
+// the whole of g16_key_audit, shared with g16_circuit_audit (circuit_audit.hip), whose report starts with the key's
+int32_t g16_key_audit_body(g16_ctx* ctx, const g16_pkey_desc* d, const g16_vkey_desc* vk, const void* section4,
+                           size_t section4_bytes, const void* multipliers, g16_key_report* out) {
   if (!ctx) return G16_EINVAL;
   if (!d || !out) {
     ctx->err = "g16_key_audit: null argument";
@@ -220,7 +250,7 @@ extern "C" int32_t g16_key_audit(g16_ctx* ctx, const g16_pkey_desc* d, const g16
   }
   std::vector<uint64_t> scalars;
   int32_t rc;
-  if (multipliers && (rc = widen_multipliers(ctx, "g16_key_audit", multipliers, d->nvars, scalars))) return rc;
+  if (multipliers && (rc = g16_widen_multipliers(ctx, "g16_key_audit", multipliers, d->nvars, scalars))) return rc;
   CTX_ENTER(ctx);
 
   struct Section {

@@ -338,6 +338,22 @@ int32_t g16_coset_pipeline_device(g16_ctx* ctx, const void* d_in, uint32_t log2n
 int32_t g16_abc_pointwise_device(g16_ctx* ctx, const void* d_a, const void* d_b, const void* d_c, size_t count,
                                  void* d_out);
 
+// ---- key audit (audit.hip), shared with the circuit audit (circuit_audit.hip) ------------------------------------------
+// 16-byte multipliers -> 32-byte standard scalars; a zero one: G16_EINVAL, "<who>: multiplier <i> is zero"
+int32_t g16_widen_multipliers(g16_ctx* ctx, const char* who, const void* multipliers, size_t n, std::vector<uint64_t>& out);
+// the body of g16_key_audit
+int32_t g16_key_audit_body(g16_ctx* ctx, const g16_pkey_desc* d, const g16_vkey_desc* vk, const void* section4,
+                           size_t section4_bytes, const void* multipliers, g16_key_report* out);
+// the element passes (audit_points) over `nsec` host arrays, group 1 = G1, 2 = G2 (with the order-r check); results as
+// g16_points_audit_*.  The caller has entered the context.
+struct g16_audit_section {
+  int group;
+  const void* p;
+  size_t n;
+};
+int32_t g16_audit_sections(g16_ctx* ctx, const g16_audit_section* sec, int nsec, size_t (*first_bad)[3],
+                           size_t (*bad_count)[3]);
+
 // ---- the two halves of g16_prove_combine (prover.hip), shared with the prover pool (pool.hip) ----------------------
 // What the finish half needs from the enqueue half: the mask in standard form and the mask-only parts of the proof
 // (r, s; alpha1 + r delta1; beta2 + s delta2; s alpha1 + r beta1 + rs delta1), as bytes.

@@ -222,3 +222,19 @@ def fakeCircuitSetup(r1cs: R1CS, toxic: ToxicWaste, flavour=Snarkjs, ctx=None, s
         pointsH1=g1(hs))
     zkey.coeffs = r1csToCoeffArray(r1cs) if hasattr(r1cs, "values") else r1csToCoeffs(r1cs)
     return zkey
+
+
+def fakePtau(tau: int, alpha: int, beta: int, power: int, ctx=None):
+    """The powers of tau a ceremony with this toxic waste would publish (files/ptau.py): tau^k gen1 for k < 2^(power+1) - 1,
+    tau^k gen2, alpha tau^k gen1 and beta tau^k gen1 for k < 2^power, beta gen2 -- the scalars by g16_powers_fr, the points
+    by g16_fixed_base_g1/g2.  A key that fakeCircuitSetup builds from the same (tau, alpha, beta) passes the circuit audit
+    (files/zkey.auditCircuit) against it, whatever its gamma and delta."""
+    from .files.ptau import Ptau
+    ctx = ctx or default_context()
+    enc = F.frToMontBytes
+    n1, n = (2 << power) - 1, 1 << power
+    taus = ctx.powers(enc(tau % R), n1)
+    return Ptau(power=power, tauG1=ctx.fixed_base(1, taus), tauG2=ctx.fixed_base(2, taus[:32 * n]),
+                alphaTauG1=ctx.fixed_base(1, ctx.powers(enc(tau % R), n, scale=enc(alpha % R))),
+                betaTauG1=ctx.fixed_base(1, ctx.powers(enc(tau % R), n, scale=enc(beta % R))),
+                betaG2=ctx.fixed_base(2, enc(beta % R)))

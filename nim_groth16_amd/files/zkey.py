@@ -53,6 +53,65 @@ def auditZKey(zk: ZKey, ctx=None, multipliers=None):
     return rep
 
 
+def r1csDesc(r1cs, flavour: int):
+    """The g16_r1cs_desc of an R1CS (the list form of files/r1cs.py or a synthetic.SparseR1CS) -> (desc, keepalive)"""
+    from .._lib import SCALARS_MONT, R1csDesc, _buf
+    from ..fake_setup import _triplets
+    values, A, B, C = _triplets(r1cs)
+    table = np.frombuffer(F.frSeqToMontBytes(list(values) + [0]), dtype=np.uint8).reshape(-1, 32)
+    d = R1csDesc()
+    d.nvars, d.npubs = r1cs.nWires, r1cs.nPubIn + r1cs.nPubOut
+    d.nconstraints = r1cs.nConstraints if hasattr(r1cs, "nConstraints") else len(r1cs.constraints)
+    d.flavour, d.flags = flavour, SCALARS_MONT
+    keep = []
+    for k, (rows, wires, vi) in enumerate((A, B, C)):
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        wires = np.ascontiguousarray(wires, dtype=np.uint32)
+        vals = np.ascontiguousarray(table[np.asarray(vi, dtype=np.int64)])
+        keep += [rows, wires, vals]
+        d.nnz[k] = len(rows)
+        if len(rows):
+            d.row[k], d.col[k], d.val[k] = (_buf(x).value for x in (rows, wires, vals))
+    return d, keep
+
+
+def ptauDesc(ptau):
+    """The g16_ptau_desc of a files.ptau.Ptau -> (desc, keepalive)"""
+    import ctypes
+
+    from .._lib import PTAU_SECTIONS, PtauDesc
+    bufs = [ctypes.create_string_buffer(x, len(x)) for x in (getattr(ptau, name) for name in PTAU_SECTIONS)]
+    return PtauDesc(ptau.power, *[ctypes.cast(b, ctypes.c_void_p) for b in bufs]), bufs
+
+
+def auditCircuit(zk: ZKey, r1cs, ptau, ctx=None, multipliers=None):
+    """Does an untrusted key belong to THIS circuit and THIS powers of tau?  One g16_circuit_audit (include/g16hip.h):
+    the key audit of auditZKey, the same element checks over the ptau, the key's coefficients against the r1cs as linear
+    maps, and every point array of the key against the powers of tau -- what `snarkjs zkey verify` checks before the
+    contribution chain.  r1cs: as parseR1CS returns it; ptau: a files.ptau.Ptau.  -> _lib.CircuitReport: `.ok`, str()
+    names every first finding.  multipliers: (one int in [1, 2^128) per wire, one per domain element); None draws them
+    with `secrets`.  Not covered: the ptau's own consistency, and the contribution chain (section 10)."""
+    import ctypes
+    import secrets
+
+    from .._lib import VkeyDesc, default_context
+    from ..prover import pkeyDesc
+    ctx = ctx or default_context()
+    desc, bufs, raw4 = pkeyDesc(zk)
+    sp = zk.specPoints
+    vbufs = [ctypes.create_string_buffer(x, len(x)) for x in (sp.alpha1, sp.beta2, sp.gamma2, sp.delta2, zk.pointsIC)]
+    va = [ctypes.cast(b, ctypes.c_void_p) for b in vbufs]
+    vk = VkeyDesc(zk.header.npubs, va[0], va[1], va[2], va[3], va[4])
+    rd, rkeep = r1csDesc(r1cs, zk.header.flavour)
+    pd, pkeep = ptauDesc(ptau)
+    if multipliers is None:
+        draw = lambda k: [secrets.randbelow((1 << 128) - 1) + 1 for _ in range(k)]     # noqa: E731
+        multipliers = (draw(zk.header.nvars), draw(zk.header.domainSize))
+    rep = ctx.circuit_audit(desc, vk, raw4, rd, pd, multipliers[0], multipliers[1])
+    del bufs, vbufs, rkeep, pkeep
+    return rep
+
+
 def parseZKey(fname: str, check: bool = False, ctx=None, rawCoeffs: bool = False) -> ZKey:
     """zkey.nim:241-246.  rawCoeffs: keep the coefficient section as it lies in the file (ZKey.coeffsSection4, handed to
     the GPU unparsed by loadProvingKey -> g16_pkey_create_zkey) instead of un-Montgomerying every entry on the host

@@ -321,6 +321,45 @@ struct R1csFile {
     if (rc.sec.count(3) && rc.get(3).len != (size_t)nwires * 8) die("unexpected label section length");   // r1cs.nim:146-152
   }
   uint32_t npubs() const { return npubout + npubin; }
+  // the description g16_circuit_audit takes: the triplets as they are, values in standard form
+  g16_r1cs_desc desc(uint32_t flavour) const {
+    g16_r1cs_desc d;
+    memset(&d, 0, sizeof d);
+    d.nvars = nwires, d.npubs = npubs(), d.nconstraints = nconstraints, d.flavour = flavour;
+    for (int k = 0; k < 3; ++k)
+      d.row[k] = row[k].data(), d.col[k] = col[k].data(), d.val[k] = val[k].data(), d.nnz[k] = row[k].size();
+    d.flags = G16_SCALARS_STD;
+    return d;
+  }
+};
+
+// ---- parsed .ptau (snarkjs powers of tau; the maintainers' reading of the format, nim_groth16_amd/files/ptau.py):
+// section 1 = n8 | q | power | ceremonyPower, sections 2..6 = tauG1 (2^(power+1) - 1 points), tauG2, alphaTauG1, betaTauG1
+// (2^power each), betaG2; points as in a .zkey.  Sections 7 and 12-15 are not read.
+struct PtauFile {
+  Container pt;
+  uint32_t power = 0;
+  explicit PtauFile(const char* path) : pt(path, "ptau", 1) {
+    Section s1 = pt.get(1);
+    if (s1.len != 4 + 32 + 8) die("unexpected ptau header length");
+    const uint8_t* p = s1.p;
+    expect_prime(p, PRIME_P, "ptau base field");
+    power = u32(p);
+    if (power > 28 || power > u32(p + 4)) die("ptau power out of range");
+  }
+  const uint8_t* points(uint32_t id, size_t psz, size_t n) const {
+    Section s = pt.get(id);
+    if (s.len != psz * n) die("unexpected length of ptau section " + std::to_string(id));
+    return s.p;
+  }
+  g16_ptau_desc desc() const {
+    const size_t n = size_t(1) << power;
+    g16_ptau_desc d;
+    d.power = power;
+    d.tauG1 = points(2, 64, 2 * n - 1), d.tauG2 = points(3, 128, n), d.alphaTauG1 = points(4, 64, n);
+    d.betaTauG1 = points(5, 64, n), d.betaG2 = points(6, 128, 1);
+    return d;
+  }
 };
 
 }  // namespace

@@ -14,6 +14,9 @@ snarkjs, ptau or network).  Given external files the checked recipe is
       --audit  for a key from a third party: before it is loaded, every section is audited on the GPU (auditZKey:
           canonical encodings, curve, order-r subgroup, coefficient values, the B1/B2, beta and delta relations);
           findings are printed, and a key that fails gives exit code 2 and no proof
+      --audit-circuit R1CS PTAU  the same and more: the key must also belong to this circuit and this powers of tau
+          (auditCircuit: the key's coefficients against the r1cs, every point array against the ptau -- what
+          `snarkjs zkey verify` checks before the contribution chain); exit code 2 and no proof otherwise
     snarkjs groth16 verify verification_key.json public.json proof.json        # offline, wherever snarkjs exists
 (the reference's own recipe: groth16/example/prove.sh:52-59)."""
 import argparse
@@ -44,6 +47,9 @@ def main():
                     help="check every key point against its curve equation on the GPU while parsing")
     ap.add_argument("--audit", action="store_true",
                     help="audit the key on the GPU before loading it; no proof from a key that fails")
+    ap.add_argument("--audit-circuit", nargs=2, metavar=("R1CS", "PTAU"), default=None,
+                    help="audit the key against its circuit and powers of tau before loading it; no proof from a key "
+                         "that does not belong to them")
     ap.add_argument("-y", "--verify", action="store_true",
                     help="also verify the proof against the zkey's verification key (cli_main.nim -y)")
     args = ap.parse_args()
@@ -55,6 +61,12 @@ def main():
     if args.audit:
         from nim_groth16_amd.files import auditZKey
         report = auditZKey(zkey, ctx)
+        print(report)
+        if not report.ok:
+            raise SystemExit(2)
+    if args.audit_circuit:
+        from nim_groth16_amd.files import auditCircuit, parsePtau, parseR1CS
+        report = auditCircuit(zkey, parseR1CS(args.audit_circuit[0]), parsePtau(args.audit_circuit[1]), ctx)
         print(report)
         if not report.ok:
             raise SystemExit(2)
