@@ -448,3 +448,62 @@ proc fakeCircuitSetup*(r1cs: R1CS, toxic: ToxicWaste, flavour = Snarkjs): ZKey =
                            domainSize: domSize, logDomainSize: int(logDom))
   return ZKey(header: header, specPoints: spec, vPoints: VerifierPoints(pointsIC: ic), pPoints: pts,
               coeffs: r1csToCoeffs(r1cs))
+
+# --- real circuit setup (include/g16hip.h "circuit setup"): the key of `snarkjs zkey new circuit.r1cs pot.ptau` ----------
+# One g16_circuit_setup call from the R1CS and the powers of tau of a ceremony (sections 2-6 of the .ptau, which the
+# caller's reader hands over as a G16PtauDesc: Montgomery affine points, power >= log2 of the domain + 1); no toxic waste.
+# gamma = 1, and delta = 1 unless one is given: such a key is sound only after a phase-2 contribution.  For the powers of
+# a known tau it is fakeCircuitSetup's key for (alpha, beta, 1, delta, tau), byte for byte.
+proc g16_points_intt_g1(ctx: ptr G16Ctx, points: pointer, log2n: uint32, res: pointer): int32 {.importc, header: "g16hip.h".}
+proc g16_points_intt_g2(ctx: ptr G16Ctx, points: pointer, log2n: uint32, res: pointer): int32 {.importc, header: "g16hip.h".}
+proc g16_circuit_setup(ctx: ptr G16Ctx, r1cs: ptr G16R1csDesc, ptau: ptr G16PtauDesc, delta: pointer,
+                       res: ptr G16SetupPoints): int32 {.importc, header: "g16hip.h".}
+
+## out[k] = sum_j (omega^(-jk) / n) points[j]: the inverse NTT with curve points for elements; points.len a power of two
+proc pointsInverseNTT*(points: seq[G1]): seq[G1] =
+  result = newSeq[G1](points.len)
+  var log2n = 0'u32
+  while (1 shl int(log2n)) < points.len: inc log2n
+  doAssert (1 shl int(log2n)) == points.len, "a power-of-two number of points"
+  check g16_points_intt_g1(gctx, unsafeAddr points[0], log2n, addr result[0])
+proc pointsInverseNTT*(points: seq[G2]): seq[G2] =
+  result = newSeq[G2](points.len)
+  var log2n = 0'u32
+  while (1 shl int(log2n)) < points.len: inc log2n
+  doAssert (1 shl int(log2n)) == points.len, "a power-of-two number of points"
+  check g16_points_intt_g2(gctx, unsafeAddr points[0], log2n, addr result[0])
+
+proc circuitSetup*(r1cs: R1CS, ptau: G16PtauDesc, flavour = Snarkjs, delta: ptr Fr = nil): ZKey =
+  let nvars = r1cs.cfg.nWires
+  let npubs = r1cs.cfg.nPubOut + r1cs.cfg.nPubIn
+  var rows, cols: array[3, seq[uint32]]
+  var vals: array[3, seq[Fr]]
+  for i, ct in r1cs.constraints:                            # files/r1cs.nim:62-80 -> triplets per matrix
+    for k, lc in [ct.A, ct.B, ct.C]:
+      for term in lc:
+        rows[k].add(uint32(i)); cols[k].add(uint32(term.wireIdx)); vals[k].add(term.value)
+  var d = G16R1csDesc(nvars: uint32(nvars), npubs: uint32(npubs), nconstraints: uint32(r1cs.constraints.len),
+    flavour: uint32(ord(flavour)), flags: G16_SCALARS_MONT)
+  for k in 0..2:
+    d.nnz[k] = csize_t(rows[k].len)
+    if rows[k].len > 0:
+      d.row[k] = addr rows[k][0]; d.col[k] = addr cols[k][0]; d.val[k] = addr vals[k][0]
+  var logDom = 0
+  while (1 shl logDom) < r1cs.constraints.len + npubs + 1: inc logDom     # ceilingLog2, as g16_setup_log2_domain
+  let domSize = 1 shl logDom
+  var spec: SpecPoints
+  var ic = newSeq[G1](npubs + 1)
+  var pts = ProverPoints(pointsA1: newSeq[G1](nvars), pointsB1: newSeq[G1](nvars), pointsB2: newSeq[G2](nvars),
+                         pointsC1: newSeq[G1](max(nvars - npubs - 1, 1)), pointsH1: newSeq[G1](domSize))
+  var o = G16SetupPoints(alpha1: addr spec.alpha1, beta1: addr spec.beta1, delta1: addr spec.delta1,
+    beta2: addr spec.beta2, gamma2: addr spec.gamma2, delta2: addr spec.delta2, pointsIC: addr ic[0],
+    pointsA1: addr pts.pointsA1[0], pointsB1: addr pts.pointsB1[0], pointsB2: addr pts.pointsB2[0],
+    pointsC1: addr pts.pointsC1[0], pointsH1: addr pts.pointsH1[0])
+  var pd = ptau
+  check g16_circuit_setup(gctx, addr d, addr pd, delta, addr o)
+  pts.pointsC1.setLen(nvars - npubs - 1)
+  spec.alphaBeta = pairing(spec.alpha1, spec.beta2)
+  let header = GrothHeader(curve: "bn128", flavour: flavour, p: primeP, r: primeR, nvars: nvars, npubs: npubs,
+                           domainSize: domSize, logDomainSize: logDom)
+  return ZKey(header: header, specPoints: spec, vPoints: VerifierPoints(pointsIC: ic), pPoints: pts,
+              coeffs: r1csToCoeffs(r1cs))

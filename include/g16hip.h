@@ -210,6 +210,49 @@ int32_t g16_lagrange_fr(g16_ctx* ctx, uint32_t log2n, uint32_t first, uint32_t s
                         const void* scale, void* out);
 int32_t g16_powers_fr(g16_ctx* ctx, const void* base, const void* scale, size_t count, void* out);
 
+/* ---- circuit setup: the key of `snarkjs zkey new circuit.r1cs pot.ptau` -- a proving key from an R1CS and the powers of
+ *      tau of a ceremony, with no toxic waste -------------------------------------------------------------------------
+ * g16_r1cs_desc / g16_ptau_desc: declared with the circuit audit, below. */
+typedef struct g16_r1cs_desc_s g16_r1cs_desc;
+typedef struct g16_ptau_desc_s g16_ptau_desc;
+/* out[k] = sum_{j<n} (omega^(-jk) / n) * points[j], n = 2^log2n: the inverse NTT of g16_ntt_fr with curve points for
+ * elements -- the Lagrange form of a run of powers of tau.  Host pointers, affine Montgomery in and out, (0,0) legal
+ * anywhere; log2n <= 24.  Any points of the group, not only powers. */
+int32_t g16_points_intt_g1(g16_ctx* ctx, const void* points, uint32_t log2n, void* out);
+int32_t g16_points_intt_g2(g16_ctx* ctx, const void* points, uint32_t log2n, void* out);
+/* The whole key; r1cs / ptau exactly the structs of g16_circuit_audit, out the struct of g16_fake_setup;
+ * delta: NULL (= 1) or 32 bytes, canonical, non-zero, in the form r1cs->flags names.
+ * Write n = 2^log2_domain, log2_domain = ceilingLog2(nconstraints + npubs + 1) as for g16_fake_setup, L_k for the Lagrange
+ * polynomials of the n-point domain, and let A include snarkjs's dummy entries (nconstraints + i, wire i, 1), i <= npubs:
+ *   LG1[k] = L_k(tau) gen1 = the inverse NTT (g16_points_intt_g1) of tauG1[0 .. n); LG2, LaG1, LbG1 the same of tauG2,
+ *            alphaTauG1, betaTauG1
+ *   pointsA1[w] = sum over the entries (row, w, v) of A of v LG1[row]; pointsB1 with B; pointsB2 with B over LG2
+ *   comb[w]     = sum_A v LbG1[row] + sum_B v LaG1[row] + sum_C v LG1[row];  pointsIC = comb[0 .. npubs],
+ *                 pointsC1[w - npubs - 1] = delta^-1 comb[w] for the private wires
+ *   pointsH1[i] = delta^-1 L'_(2i+1)(tau) gen1 on the doubled domain (snarkjs flavour: the size-n transform of
+ *                 (tauG1[j] - tauG1[j+n]) eta^-j / 2, eta = omega_2n), or delta^-1 (tauG1[i+n] - tauG1[i]) (JensGroth)
+ *   alpha1 = alphaTauG1[0], beta1 = betaTauG1[0], beta2 = betaG2, gamma2 = gen2, delta1 = delta gen1, delta2 = delta gen2
+ * By construction this is g16_fake_setup's key for the toxic waste (alpha, beta, gamma = 1, delta, tau) when the ptau is
+ * the powers of that tau, byte for byte, and it passes g16_circuit_audit against the same r1cs and ptau.
+ * SOUNDNESS: gamma = 1 always, and with delta == NULL delta = 1 as well -- exactly the key of `snarkjs zkey new`.  Such a
+ * key is NOT fit for production: anyone can forge proofs for it.  It becomes sound only after a phase-2 contribution
+ * (`snarkjs zkey contribute`: delta replaced by a secret, pointsC1 / pointsH1 rescaled).  A caller-supplied delta is that
+ * step for a caller who may know delta; it is toxic waste of the caller's.
+ * Out of scope: the contribution transcript of a .zkey (section 10 and its hashes); the pre-computed Lagrange sections
+ * 12-15 of a "prepared" .ptau -- the call always works from the monomial sections 2-6.
+ * Before any arithmetic the element passes of g16_circuit_audit run over the ptau elements the call reads (tauG1[0 .. 2n),
+ * tauG2 / alphaTauG1 / betaTauG1 [0 .. n), betaG2): canonical and on the curve for every element, the order-r subgroup
+ * for the G2 arrays.  An element that fails is G16_EINVAL; g16_last_error names section, index and check in the words
+ * of the circuit-audit report ("ptau tauG2[3] is not in the order-r subgroup").
+ * G16_EINVAL, checked on the host before anything is queued: a null pointer; an unknown flavour or flags; a matrix entry
+ * out of range or not canonical; nvars <= npubs; a domain above 2^24; ptau->power < log2_domain + 1 (the audit's rule);
+ * delta zero or >= r.  No output is promised after a failure.
+ * The call changes no context state (a context proves the same bytes before and after), runs on the context's stream
+ * with one wait after the element passes and one at the end; intermediates stay in HBM between the stages.  Outputs are
+ * canonical affine bytes. */
+int32_t g16_circuit_setup(g16_ctx* ctx, const g16_r1cs_desc* r1cs, const g16_ptau_desc* ptau, const void* delta,
+                          g16_setup_points* out);
+
 /* ---- NTT: replaces forwardNTT / inverseNTT (groth16/math/ntt.nim:55-77, 139-161) ------------------- */
 /* natural order in and out; forward unscaled, inverse includes 1/n; omega = gen28^(2^(28-log2n))
  * (math/domain.nim:26-33).  src/dst: n = 2^log2n Fr elements (Montgomery), host memory. 0 <= log2n <= 28 */
@@ -553,7 +596,7 @@ int32_t g16_key_audit(g16_ctx* ctx, const g16_pkey_desc* desc, const g16_vkey_de
  * g16_r1cs_desc: the R1CS as triplets, the first members of g16_setup_desc under the same rules (entries of one
  *   (constraint, wire) add up; the library adds snarkjs's dummy A entries (nconstraints + i, wire i, 1), i <= npubs).
  * g16_ptau_desc: sections 2..6 of a .ptau, Montgomery affine like every point here. */
-typedef struct {
+struct g16_r1cs_desc_s {
   uint32_t nvars, npubs, nconstraints;
   uint32_t flavour;         /* must equal the key's */
   const uint32_t* row[3];
@@ -561,11 +604,11 @@ typedef struct {
   const void* val[3];
   size_t nnz[3];
   uint32_t flags;           /* G16_SCALARS_MONT or G16_SCALARS_STD for val */
-} g16_r1cs_desc;
-typedef struct {
+};
+struct g16_ptau_desc_s {
   uint32_t power;           /* tauG1: 2^(power+1) - 1 points; tauG2, alphaTauG1, betaTauG1: 2^power; betaG2: 1 */
   const void *tauG1, *tauG2, *alphaTauG1, *betaTauG1, *betaG2;
-} g16_ptau_desc;
+};
 #define G16_PTAU_SECTIONS 5
 #define G16_CIRCUIT_RELATIONS 9
 enum {

@@ -34,6 +34,7 @@ SYMBOLS = [
     "g16_setup_log2_domain", "g16_fake_setup", "g16_lagrange_fr", "g16_powers_fr",
     "g16_points_audit_g1", "g16_points_audit_g2", "g16_points_pairs_check", "g16_key_audit",
     "g16_pkey_b1_fold", "g16_circuit_audit",
+    "g16_points_intt_g1", "g16_points_intt_g2", "g16_circuit_setup",
 ]
 VERIFY_SUBGROUP = 16
 GT_BYTES = 384
@@ -367,6 +368,10 @@ def load_library():
     lib.g16_circuit_audit.argtypes = [vp, ctypes.POINTER(PkeyDesc), ctypes.POINTER(VkeyDesc), vp, sz,
                                       ctypes.POINTER(R1csDesc), ctypes.POINTER(PtauDesc), vp, vp,
                                       ctypes.POINTER(CircuitReportC)]
+    lib.g16_points_intt_g1.argtypes = [vp, vp, u32, vp]
+    lib.g16_points_intt_g2.argtypes = [vp, vp, u32, vp]
+    lib.g16_circuit_setup.argtypes = [vp, ctypes.POINTER(R1csDesc), ctypes.POINTER(PtauDesc), vp,
+                                      ctypes.POINTER(SetupPoints)]
     for name in SYMBOLS:
         if name not in ("g16_ctx_destroy", "g16_last_error", "g16_points_release", "g16_points_count",
                         "g16_points_inf_count",
@@ -634,6 +639,36 @@ class Context:
             setattr(o, name, ctypes.cast(bufs[name], ctypes.c_void_p).value)
         self._check(self._lib.g16_fake_setup(self._h, ctypes.byref(d), ctypes.byref(o)))
         return log2.value, {name: bufs[name].raw[: sizes[name]] for name in SETUP_POINTS}
+
+    def points_intt(self, group: int, points: bytes, log2n: int) -> bytes:
+        """g16_points_intt_g1/g2: out[k] = sum_j (omega^-jk / n) points[j] over n = 2^log2n affine points -- the inverse
+        NTT with curve points for elements (the Lagrange form of a run of powers of tau)"""
+        psz = 64 if group == 1 else 128
+        assert len(points) == psz << log2n, f"2^{log2n} points of {psz} bytes"
+        out = ctypes.create_string_buffer(len(points))
+        fn = self._lib.g16_points_intt_g1 if group == 1 else self._lib.g16_points_intt_g2
+        self._check(fn(self._h, _buf(points), log2n, out))
+        return out.raw
+
+    def circuit_setup(self, r1cs: R1csDesc, ptau: PtauDesc, delta: bytes = None):
+        """g16_circuit_setup: the key of `snarkjs zkey new` from the two descriptions of the circuit audit (the caller
+        keeps their buffers alive); delta: None (= 1) or 32 bytes in the form r1cs.flags names.
+        -> (log2 of the domain, {name: bytes} for every member of g16_setup_points)"""
+        nvars, npubs = r1cs.nvars, r1cs.npubs
+        log2 = max(0, (r1cs.nconstraints + npubs).bit_length())          # ceilingLog2(nconstraints + npubs + 1)
+        sizes = dict(alpha1=64, beta1=64, delta1=64, beta2=128, gamma2=128, delta2=128, pointsIC=64 * (npubs + 1),
+                     pointsA1=64 * nvars, pointsB1=64 * nvars, pointsB2=128 * nvars,
+                     pointsC1=64 * max(0, nvars - npubs - 1), pointsH1=64 << log2)
+        if log2 > 24:                                        # the call rejects the domain before it writes anything
+            sizes = dict.fromkeys(sizes, 0)
+        o = SetupPoints()
+        bufs = {}
+        for name, nbytes in sizes.items():
+            bufs[name] = ctypes.create_string_buffer(max(1, nbytes))
+            setattr(o, name, ctypes.cast(bufs[name], ctypes.c_void_p).value)
+        self._check(self._lib.g16_circuit_setup(self._h, ctypes.byref(r1cs), ctypes.byref(ptau),
+                                                _buf(bytes(delta)) if delta is not None else None, ctypes.byref(o)))
+        return log2, {name: bufs[name].raw[: sizes[name]] for name in SETUP_POINTS}
 
     def quotient(self, Az, Bz, Cz, log2n: int, flavour: int, out=None, device: bool = False):
         if device:

@@ -14,6 +14,7 @@
 #include "g16_env.hpp"
 #include "hip_owners.hpp"
 #include "msm_params.hpp"
+#include "circuit_setup_plan.hpp"
 #include "msm_plan.hpp"
 #include "proof_plan.hpp"
 
@@ -353,6 +354,31 @@ struct g16_audit_section {
 };
 int32_t g16_audit_sections(g16_ctx* ctx, const g16_audit_section* sec, int nsec, size_t (*first_bad)[3],
                            size_t (*bad_count)[3]);
+
+// ---- circuit setup (circuit_setup.hip); kernels and launcher bodies in circuit_setup.cuh, instantiated per curve in
+// circuit_setup_g1.hip / circuit_setup_g2.hip.  Device pointers, the context's stream, nothing waits. ----------------------
+namespace g16 {
+struct u256;   // ff.cuh
+}
+// d_out[i] = c * w0 * s^i (setup.hip: the geometric-sequence kernel of the fake setup; `lagrange`: c x_i / (tau - x_i))
+int32_t g16_setup_geometric(g16_ctx* ctx, bool lagrange, const g16::u256& w0, const g16::u256& s, const g16::u256& c,
+                            const g16::u256& tau, size_t count, g16::u256* d_out, uint32_t* d_first_zero);
+namespace g16 {
+// out_acc[rev(e)] = val[vstride * ord[e]] * pts[src[e]], e < count (cs_term, circuit_setup.cuh)
+template <class C>
+int32_t cs_term_device(g16_ctx* ctx, const void* d_pts, const uint32_t* d_src, const void* d_val, const uint32_t* d_ord,
+                       uint32_t vstride, uint32_t mont, uint32_t log2rev, size_t count, void* d_out_acc);
+// the log2n stages of the inverse NTT over 2^log2n XYZZ points in bit-reversed order, in place
+template <class C>
+int32_t cs_butterflies_device(g16_ctx* ctx, void* d_v, const void* d_tw, uint32_t log2n);
+template <class C>
+int32_t cs_segsum_device(g16_ctx* ctx, const void* d_terms, const uint32_t* d_off, const uint32_t* d_wires,
+                         const CsSumPlan& plan, void* d_out_aff);
+template <class C>
+int32_t cs_to_affine_device(g16_ctx* ctx, const void* d_acc, size_t count, void* d_out_aff);
+template <class C>
+int32_t cs_diff_device(g16_ctx* ctx, const void* d_p, const void* d_q, size_t count, void* d_out_aff);
+}  // namespace g16
 
 // ---- the two halves of g16_prove_combine (prover.hip), shared with the prover pool (pool.hip) ----------------------
 // What the finish half needs from the enqueue half: the mask in standard form and the mask-only parts of the proof

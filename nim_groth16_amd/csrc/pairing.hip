@@ -3,6 +3,7 @@
 // it exists so that a user of the reference's verifyProof finds it here, running on the same device.
 #include "g16_internal.hpp"
 #include "pairing.cuh"
+#include "scalar_mul.cuh"   // scalar_mul: k * P over a canonical 254-bit scalar
 
 using namespace g16;
 
@@ -17,25 +18,6 @@ struct g16_vkey {
 namespace {
 
 constexpr int PBLOCK = 64;
-
-// k * P by double-and-add over the 254 bits of a canonical scalar
-template <class C>
-__device__ typename C::Acc scalar_mul(const typename C::Aff& p, u256 k) {
-  typename C::Acc acc = C::acc_inf();
-#pragma unroll 1
-  for (int j = 7; j >= 0; --j) {
-    uint32_t limb = k.v[7];
-#pragma unroll
-    for (int q = 7; q > 0; --q) k.v[q] = k.v[q - 1];   // rotate: static register indices
-    k.v[0] = limb;
-#pragma unroll 1
-    for (int b = 31; b >= 0; --b) {
-      acc = C::dbl(acc);
-      if ((limb >> b) & 1) C::madd(acc, p);
-    }
-  }
-  return acc;
-}
 
 __device__ bool on_curve_g1(const g1_aff& p) {
   if (G1::is_inf(p)) return true;

@@ -86,6 +86,12 @@ int32_t tau_in_domain(g16_ctx* ctx, uint32_t log2n, uint64_t first, uint64_t ste
 
 }  // namespace
 
+// the geometric-sequence kernel for the circuit setup (circuit_setup.hip): its twiddles and coset factors
+int32_t g16_setup_geometric(g16_ctx* ctx, bool lagrange, const u256& w0, const u256& s, const u256& c, const u256& tau,
+                            size_t count, u256* d_out, uint32_t* d_first_zero) {
+  return launch_geometric(ctx, lagrange, w0, s, c, tau, count, d_out, d_first_zero);
+}
+
 // ceilingLog2(n + p + 1) (fake_setup.nim:203-206): pure
 extern "C" int32_t g16_setup_log2_domain(const g16_setup_desc* desc, uint32_t* log2_domain) {
   if (!desc || !log2_domain) return G16_EINVAL;

@@ -7,6 +7,7 @@
 //   ./g16prove -z circuit.zkey -w witness.wtns -o proof.json -i public.json [-n] [-y] [-t] [--gpus 0,1,2,3]
 //             [--table-stride S] [--audit-key] [--audit-circuit-r1cs circuit.r1cs --audit-circuit-ptau pot.ptau]
 //   ./g16prove -u -r circuit.r1cs [--toxic-seed N] -w witness.wtns -o proof.json -i public.json [-y] ...
+//   ./g16prove -u -r circuit.r1cs --ptau pot.ptau [--delta-seed N] [-z new.zkey] -w witness.wtns ...
 //
 // -u/--setup -r/--r1cs circuit.r1cs: the reference's fake circuit-specific trusted setup (cli/cli_main.nim:184-193,
 // groth16/fake_setup.nim:201-326) in place of a .zkey: g16_fake_setup builds the key's points on the GPU from the R1CS and
@@ -14,6 +15,12 @@
 // and verified against that key.  --toxic-seed N (default 0): the five toxic scalars alpha, beta, gamma, delta, tau are
 // 256-bit draws of SplitMix64(N), four words each in that order, least significant word first, with the top three bits
 // cleared -- below r without any host arithmetic.  Toxic waste that anyone can derive: for tests and benchmarks only.
+//
+// -u -r circuit.r1cs --ptau pot.ptau: the REAL circuit setup instead -- g16_circuit_setup builds the key of `snarkjs zkey
+// new` from the R1CS and the powers of tau of a ceremony (sections 2-6 of the .ptau); no toxic waste is involved.  gamma =
+// delta = 1: such a key is sound only after a phase-2 contribution.  --delta-seed N: delta is the first 256-bit draw of
+// SplitMix64(N) as above -- a delta anyone can derive, for tests only.  -z new.zkey: the key is also written there
+// (sections 1-9, as the Python writer does).
 //
 // --table-stride S: a lean key -- window tables for every S-th window only (g16_pkey_create_zkey_lean: about 1 / S of
 // the HBM, more bucket reduction per proof, the same proof).
@@ -45,8 +52,10 @@ struct SetupKey {
   uint32_t log2n = 0;
   std::vector<uint8_t> spec, ic, a1, b1, b2, c1, h1;   // spec = alpha1 | beta1 | delta1 | beta2 | gamma2 | delta2
   std::vector<g16_coeff> coeffs;
-  SetupKey(const char* path, uint64_t seed, g16_ctx* ctx) : rf(path) {
-    uint64_t state = seed;
+  // ptau == nullptr: g16_fake_setup from SplitMix64(seed); else g16_circuit_setup, delta from delta_seed if given
+  SetupKey(const char* path, uint64_t seed, g16_ctx* ctx, const char* ptau = nullptr, const uint64_t* delta_seed = nullptr)
+      : rf(path) {
+    uint64_t state = ptau && delta_seed ? *delta_seed : seed;
     auto splitmix = [&]() {
       uint64_t z = (state += 0x9E3779B97F4A7C15ull);
       z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -76,7 +85,15 @@ struct SetupKey {
     o.beta2 = &spec[192], o.gamma2 = &spec[320], o.delta2 = &spec[448];
     o.pointsIC = ic.data(), o.pointsA1 = a1.data(), o.pointsB1 = b1.data(), o.pointsB2 = b2.data();
     o.pointsC1 = c1.data(), o.pointsH1 = h1.data();
-    if (g16_fake_setup(ctx, &d, &o) != G16_OK) die(std::string("g16_fake_setup failed: ") + g16_last_error(ctx));
+    if (ptau) {
+      PtauFile pf(ptau);
+      const g16_r1cs_desc rd = rf.desc(G16_FLAVOUR_SNARKJS);
+      const g16_ptau_desc pd = pf.desc();
+      if (g16_circuit_setup(ctx, &rd, &pd, delta_seed ? toxic[0].v : nullptr, &o) != G16_OK)
+        die(std::string("g16_circuit_setup failed: ") + g16_last_error(ctx));
+    } else if (g16_fake_setup(ctx, &d, &o) != G16_OK) {
+      die(std::string("g16_fake_setup failed: ") + g16_last_error(ctx));
+    }
     // ZKey.coeffs (fake_setup.nim:46-65): the A and B entries with Montgomery values, then the dummy A rows
     for (uint32_t m = 0; m < 2; ++m)
       for (size_t i = 0; i < rf.row[m].size(); ++i) {
@@ -92,6 +109,40 @@ struct SetupKey {
       memcpy(c.value, FR_ONE.v, 32);
       coeffs.push_back(c);
     }
+  }
+  // the key as a .zkey: sections 1-9 (zkey.nim:6-91); coefficient values c R -> c R^2 as the format wants them
+  void write_zkey(const char* path) const {
+    FILE* f = fopen(path, "wb");
+    if (!f) die(std::string("cannot write ") + path);
+    auto put = [&](const void* p, size_t n) {
+      if (n && fwrite(p, 1, n, f) != n) die(std::string("cannot write ") + path);
+    };
+    auto put32 = [&](uint32_t x) { put(&x, 4); };
+    auto section = [&](uint32_t id, uint64_t len) {
+      put32(id);
+      put(&len, 8);
+    };
+    put("zkey", 4), put32(1), put32(9);
+    section(1, 4), put32(1);
+    section(2, 2 * 36 + 12 + spec.size());
+    put32(32), put(PRIME_P.v, 32), put32(32), put(PRIME_R.v, 32);
+    put32(rf.nwires), put32(rf.npubs()), put32(1u << log2n);
+    // alpha1 | beta1 | beta2 | gamma2 | delta1 | delta2
+    put(&spec[0], 64), put(&spec[64], 64), put(&spec[192], 128), put(&spec[320], 128), put(&spec[128], 64), put(&spec[448], 128);
+    section(3, ic.size()), put(ic.data(), ic.size());
+    section(4, 4 + 44 * (uint64_t)coeffs.size()), put32((uint32_t)coeffs.size());
+    for (const g16_coeff& c : coeffs) {
+      put32(c.matrix), put32(c.row), put32(c.col);
+      const U256 v = mont_mul(load((const uint8_t*)c.value), FR_R2, PRIME_R, R_NINV);
+      put(v.v, 32);
+    }
+    const size_t nc1 = 64 * ((size_t)rf.nwires - rf.npubs() - 1);
+    section(5, a1.size()), put(a1.data(), a1.size());
+    section(6, b1.size()), put(b1.data(), b1.size());
+    section(7, b2.size()), put(b2.data(), b2.size());
+    section(8, nc1), put(c1.data(), nc1);
+    section(9, h1.size()), put(h1.data(), h1.size());
+    if (fclose(f) != 0) die(std::string("cannot write ") + path);
   }
   g16_pkey_desc desc() const {
     g16_pkey_desc d;
@@ -164,7 +215,9 @@ int main(int argc, char** argv) {
   const char *acr = nullptr, *acp = nullptr;
   const char *zpath = nullptr, *wpath = nullptr, *rpath = nullptr, *opath = "proof.json", *ipath = "public.json";
   bool nomask = false, verify = false, timing = false, setup = false, audit = false;
-  uint64_t toxic_seed = 0;
+  const char* ptau_path = nullptr;
+  uint64_t toxic_seed = 0, delta_seed = 0;
+  bool have_delta = false;
   std::vector<int32_t> gpus;
   uint32_t table_stride = 0;
   for (int i = 1; i < argc; ++i) {
@@ -184,6 +237,14 @@ int main(int argc, char** argv) {
       const char* q = next();
       toxic_seed = strtoull(q, &end, 10);
       if (end == q || *end) die("--toxic-seed takes an unsigned 64-bit number");
+    }
+    else if (a == "--ptau") ptau_path = next();
+    else if (a == "--delta-seed") {
+      char* end = nullptr;
+      const char* q = next();
+      delta_seed = strtoull(q, &end, 10);
+      if (end == q || *end) die("--delta-seed takes an unsigned 64-bit number");
+      have_delta = true;
     }
     else if (a == "-n" || a == "--nomask") nomask = true;   // cli_main.nim -n
     else if (a == "-y" || a == "--verify") verify = true;   // cli_main.nim -y
@@ -207,11 +268,14 @@ int main(int argc, char** argv) {
       if (end == q || *end || s < 0 || s > 255) die("--table-stride takes a number from 0 to 255");
       table_stride = (uint32_t)s;
     }
-    else die("unknown option " + a + "\nusage: g16prove -z circuit.zkey -w witness.wtns [-o proof.json] [-i public.json] [-n] [-y] [-t] [--gpus 0,1,...] [--table-stride S] [--audit-key]\n       g16prove -u -r circuit.r1cs [--toxic-seed N] -w witness.wtns ...");
+    else die("unknown option " + a + "\nusage: g16prove -z circuit.zkey -w witness.wtns [-o proof.json] [-i public.json] [-n] [-y] [-t] [--gpus 0,1,...] [--table-stride S] [--audit-key]\n       g16prove -u -r circuit.r1cs [--toxic-seed N] -w witness.wtns ...\n       g16prove -u -r circuit.r1cs --ptau pot.ptau [--delta-seed N] [-z new.zkey] -w witness.wtns ...");
   }
-  if (setup ? (!rpath || zpath || !wpath) : (!zpath || rpath || !wpath))
+  if (setup ? (!rpath || (zpath && !ptau_path) || !wpath) : (!zpath || rpath || !wpath))
     die("usage: g16prove -z circuit.zkey -w witness.wtns [-o proof.json] [-i public.json] [-n] [-y] [-t]\n"
-        "       g16prove -u -r circuit.r1cs [--toxic-seed N] -w witness.wtns [-o proof.json] [-i public.json] [-n] [-y] [-t]");
+        "       g16prove -u -r circuit.r1cs [--toxic-seed N] -w witness.wtns [-o proof.json] [-i public.json] [-n] [-y] [-t]\n"
+        "       g16prove -u -r circuit.r1cs --ptau pot.ptau [--delta-seed N] [-z new.zkey] -w witness.wtns ...");
+  if ((ptau_path || have_delta) && !setup) die("--ptau and --delta-seed go together with -u -r circuit.r1cs");
+  if (have_delta && !ptau_path) die("--delta-seed goes together with --ptau");
 
   if (!acr != !acp) die("--audit-circuit-r1cs and --audit-circuit-ptau go together");
   const double t0 = now();
@@ -223,8 +287,12 @@ int main(int argc, char** argv) {
   chk(g16_selftest(ctx), "g16_selftest");
   std::unique_ptr<ZkeyFile> zfp;
   std::unique_ptr<SetupKey> skp;
-  if (setup) skp.reset(new SetupKey(rpath, toxic_seed, ctx));
-  else zfp.reset(new ZkeyFile(zpath));
+  if (setup) {
+    skp.reset(new SetupKey(rpath, toxic_seed, ctx, ptau_path, have_delta ? &delta_seed : nullptr));
+    if (zpath) skp->write_zkey(zpath);
+  } else {
+    zfp.reset(new ZkeyFile(zpath));
+  }
   const uint32_t nvars = setup ? skp->rf.nwires : zfp->nvars;
   const uint32_t npubs = setup ? skp->rf.npubs() : zfp->npubs;
   WtnsFile wf(wpath, nvars);

@@ -9,7 +9,15 @@ library's kernel times (HIP events) next to the wall time of the call.
 The host path's Lagrange cache is emptied before every repeat: each figure is one setup from nothing.  (bench.py builds
 its two keys from one toxic waste, so its second setup finds the values of the first: see the `warm` line.)
 
-  python tools/perf_setup.py [--log2n 20] [--repeats 3] [--out profiles/fake_setup_ab.txt]"""
+  python tools/perf_setup.py [--log2n 20] [--repeats 3] [--out profiles/fake_setup_ab.txt]
+
+--circuit-setup: the real setup instead -- circuitSetup (one g16_circuit_setup call: group inverse NTTs and sparse matrix x
+point vector products) from the circuit and a fakePtau of power log2n + 1, on the same two circuits, with the library's
+per-kernel times; beside it fakeCircuitSetup (g16_fake_setup) for the same (alpha, beta, gamma = 1, delta = 1, tau) as the
+only available yardstick -- it does one fixed-base multiplication where the real setup does a transform -- and the two
+keys compared byte for byte.
+
+  python tools/perf_setup.py --circuit-setup [--log2n 20] [--repeats 2] [--out profiles/circuit_setup_2p20.txt]"""
 import argparse
 import gc
 import os
@@ -57,12 +65,71 @@ def same_key(a, b):
             a.pPoints == b.pPoints and packCoeffs(a.coeffs) == packCoeffs(b.coeffs))
 
 
+def circuit_setup_main(args):
+    from nim_groth16_amd.setup import circuitSetup
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+
+    gc.disable()
+    ctx = Context(0)
+    ctx.selftest()
+    rng = SplitMix64(5)
+    alpha, beta, _, _, tau = (rng.fr() for _ in range(5))
+    tox = FS.ToxicWaste(alpha, beta, 1, 1, tau)
+    say(f"circuitSetup (g16_circuit_setup) beside fakeCircuitSetup (g16_fake_setup), 2^{args.log2n} constraints, snarkjs "
+        f"flavour, delta = 1, {args.repeats} repeats, one process ({time.strftime('%Y-%m-%d')})")
+    t0 = time.perf_counter()
+    pt = FS.fakePtau(tau, alpha, beta, args.log2n + 1, ctx)
+    say(f"fakePtau, power {args.log2n + 1}: {time.perf_counter() - t0:.1f} s")
+    small, _ = squaringChain((1 << 8) - 2, seed=4)
+    circuitSetup(small, pt, 1, None, ctx)                                  # warm-up: code objects
+    for name, make in (("squaring chain", lambda: squaringChain((1 << args.log2n) - 2, seed=4)),
+                       ("Poseidon shape", lambda: poseidonMerkle(args.log2n, seed=4))):
+        t0 = time.perf_counter()
+        r1cs, _ = make()
+        nnz = [len(m[0]) for m in FS._triplets(r1cs)[1:]]
+        say(f"\n{name}: nvars {r1cs.nWires}, entries A {nnz[0]} B {nnz[1]} C {nnz[2]}, circuit built in "
+            f"{time.perf_counter() - t0:.1f} s")
+        zf = FS.fakeCircuitSetup(r1cs, tox, 1, ctx, scalarSide="device")   # warm-up of the yardstick: fixed-base tables
+        for rep_i in range(args.repeats):
+            t0 = time.perf_counter()
+            zf = FS.fakeCircuitSetup(r1cs, tox, 1, ctx, scalarSide="device")
+            tf = time.perf_counter() - t0
+            ctx.profile(True)
+            ctx.profile_reset()
+            t0 = time.perf_counter()
+            zc = circuitSetup(r1cs, pt, 1, None, ctx)
+            tc = time.perf_counter() - t0
+            rep_k = ctx.profile_report()
+            ctx.profile(False)
+            say(f"  #{rep_i}: circuitSetup {tc:7.2f} s (call, with the host's entry sort and the copies)   fakeCircuitSetup {tf:7.2f} s")
+            for k, v in sorted(rep_k.items()):
+                say(f"        {k:<22} {v['calls']:>4} launches {v['total_ms']:>10.1f} ms")
+            say(f"        {'all kernels':<22} {sum(v['calls'] for v in rep_k.values()):>4} launches "
+                f"{sum(v['total_ms'] for v in rep_k.values()):>10.1f} ms")
+            if not same_key(zf, zc):
+                raise SystemExit("circuitSetup and fakeCircuitSetup built different keys")
+            del zc
+        say("  keys equal byte for byte")
+        del r1cs, zf
+    ctx.close()
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--circuit-setup", action="store_true", help="measure g16_circuit_setup (see the module text)")
     ap.add_argument("--log2n", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fake_setup_ab.txt"))
     args = ap.parse_args()
+    if args.circuit_setup:
+        return circuit_setup_main(args)
     lines = []
 
     def say(s=""):

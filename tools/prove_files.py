@@ -17,6 +17,9 @@ snarkjs, ptau or network).  Given external files the checked recipe is
       --audit-circuit R1CS PTAU  the same and more: the key must also belong to this circuit and this powers of tau
           (auditCircuit: the key's coefficients against the r1cs, every point array against the ptau -- what
           `snarkjs zkey verify` checks before the contribution chain); exit code 2 and no proof otherwise
+      --setup-ptau PTAU -r R1CS  first make the key: the circuit setup of `snarkjs zkey new` on the GPU (circuitSetup:
+          gamma = delta = 1, sound only after a phase-2 contribution) written to the --zkey path; without --wtns the
+          run ends there, with it the proof is made from the new key
     snarkjs groth16 verify verification_key.json public.json proof.json        # offline, wherever snarkjs exists
 (the reference's own recipe: groth16/example/prove.sh:52-59)."""
 import argparse
@@ -35,7 +38,11 @@ from nim_groth16_amd.files import exportProof, exportPublicIO, parseWitness, par
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("-z", "--zkey", required=True)
-    ap.add_argument("-w", "--wtns", required=True)
+    ap.add_argument("-w", "--wtns", default=None, help="required unless --setup-ptau only makes the key")
+    ap.add_argument("--setup-ptau", metavar="PTAU", default=None,
+                    help="make the key from -r R1CS and this powers of tau and write it to --zkey (then prove, if a "
+                         "witness is given)")
+    ap.add_argument("-r", "--r1cs", default=None, help="the circuit of --setup-ptau")
     ap.add_argument("-o", "--output", default="proof.json")
     ap.add_argument("-i", "--io", default="public.json")
     ap.add_argument("-n", "--nomask", action="store_true", help="trivial mask r = s = 0 (cli_main.nim -n)")
@@ -55,6 +62,20 @@ def main():
     args = ap.parse_args()
     ctx = Context(0)
     ctx.selftest()
+    if args.setup_ptau:
+        if not args.r1cs:
+            ap.error("--setup-ptau goes together with -r R1CS")
+        from nim_groth16_amd.files import parsePtau, parseR1CS, writeZKey
+        from nim_groth16_amd.setup import circuitSetup
+        ts = time.time()
+        writeZKey(args.zkey, circuitSetup(parseR1CS(args.r1cs), parsePtau(args.setup_ptau), ctx=ctx))
+        print(f"circuit setup: wrote {args.zkey}" + (f" ({time.time() - ts:.3f}s)" if args.time else ""))
+        if not args.wtns:
+            return
+    elif args.r1cs:
+        ap.error("-r R1CS goes together with --setup-ptau")
+    if not args.wtns:
+        ap.error("the following arguments are required: -w/--wtns")
     t0 = time.time()
     zkey, wtns = parseZKey(args.zkey, check=args.check, ctx=ctx, rawCoeffs=True), parseWitness(args.wtns)
     assert wtns.nvars == zkey.header.nvars, "wrong witness length"        # prover.nim:236
