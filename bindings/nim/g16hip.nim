@@ -49,6 +49,7 @@ proc g16_prove(ctx: ptr G16Ctx, key: ptr G16PKey, witness: pointer, flags: uint3
 # entry lists: snarkjs keys hold (0,0) for every wire absent from a matrix (curves.nim:95-107 accepts them)
 proc g16_pkey_inf_counts(key: ptr G16PKey, res: ptr array[8, csize_t]): int32 {.importc, header: "g16hip.h".}
 proc g16_pkey_b1_fold(key: ptr G16PKey, res: ptr array[3, csize_t]): int32 {.importc, header: "g16hip.h".}
+proc g16_pkey_b1_sparse(key: ptr G16PKey, res: ptr array[3, csize_t]): int32 {.importc, header: "g16hip.h".}
 
 var gctx: ptr G16Ctx
 

@@ -333,6 +333,12 @@ int32_t g16_pkey_inf_counts(const g16_pkey* key, size_t out[8]);
  *   0: pointsB1 as it is, otherwise and always under G16_B1_FOLD=0.
  * out[0] = that form, out[1] = live_b1, out[2] = live_delta.  Proofs are the same bytes in every form. */
 int32_t g16_pkey_b1_fold(const g16_pkey* key, size_t out[3]);
+/* How a key of form 2 runs its B1 job.  With at most out[2] (= 64) live differences over the key's WHOLE wire range it
+ * also keeps the list of its live wires, and the job forms its bucket sums from those wires' witness values alone (the
+ * sparse run) instead of reading the arrangement of all wires: out[0] = 1.  out[1] = the live differences inside THIS
+ * key's wire range (a shard may hold none).  Keys of the other forms, and of form 2 with more live differences: out[0] =
+ * out[1] = 0.  Proofs are the same bytes either way. */
+int32_t g16_pkey_b1_sparse(const g16_pkey* key, size_t out[3]);
 /* witness: nvars Fr values (flags: G16_SCALARS_MONT for Nim seq[Fr], G16_SCALARS_STD for raw .wtns,
  * | G16_SCALARS_DEVICE); mask_r / mask_s: Fr Montgomery (Mask, prover.nim:210-213), NULL = zero
  * (generateProofWithTrivialMask, prover.nim:308-310). */

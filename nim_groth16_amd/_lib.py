@@ -33,7 +33,7 @@ SYMBOLS = [
     "g16_pkey_create_zkey_lean", "g16_group_pkey_create_lean",
     "g16_setup_log2_domain", "g16_fake_setup", "g16_lagrange_fr", "g16_powers_fr",
     "g16_points_audit_g1", "g16_points_audit_g2", "g16_points_pairs_check", "g16_key_audit",
-    "g16_pkey_b1_fold", "g16_circuit_audit",
+    "g16_pkey_b1_fold", "g16_pkey_b1_sparse", "g16_circuit_audit",
     "g16_points_intt_g1", "g16_points_intt_g2", "g16_circuit_setup",
 ]
 VERIFY_SUBGROUP = 16
@@ -302,6 +302,7 @@ def load_library():
     lib.g16_points_inf_count.restype = sz
     lib.g16_pkey_inf_counts.argtypes = [vp, ctypes.POINTER(sz)]
     lib.g16_pkey_b1_fold.argtypes = [vp, ctypes.POINTER(sz)]
+    lib.g16_pkey_b1_sparse.argtypes = [vp, ctypes.POINTER(sz)]
     lib.g16_points_info.argtypes = [vp, ctypes.POINTER(u32), ctypes.POINTER(u32)]
     lib.g16_msm_points.argtypes = [vp, vp, vp, u32, vp]
     lib.g16_points_check_g1.argtypes = [vp, vp, sz, ctypes.POINTER(sz)]
@@ -827,6 +828,13 @@ class ProvingKey:
         out = (ctypes.c_size_t * 3)()
         self.ctx._check(self.ctx._lib.g16_pkey_b1_fold(self._h, out))
         return {"form": ("PLAIN", "EMPTY", "DELTA")[out[0]], "live_b1": out[1], "live_delta": out[2]}
+
+    def b1_sparse(self) -> dict:
+        """how a DELTA key runs its B1 job (g16_pkey_b1_sparse): `sparse` if from the witness values of its live wires
+        alone (at most `max` live differences over the whole wire range), and the live differences in this key's range"""
+        out = (ctypes.c_size_t * 3)()
+        self.ctx._check(self.ctx._lib.g16_pkey_b1_sparse(self._h, out))
+        return {"sparse": bool(out[0]), "live": out[1], "max": out[2]}
 
     def abc_info(self) -> dict:
         """shape of the A / B matrices as buildABC runs them (g16_pkey_abc_info)"""

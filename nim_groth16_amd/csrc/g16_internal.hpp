@@ -251,8 +251,16 @@ int32_t g16_msm_sort(g16_ctx* ctx, hipStream_t stream, const void* d_scalars, ui
 //   n_accum jobs are accumulated (+ split buckets combined); the first n_tail <= n_accum of them are reduced and folded
 //   init_partial: the bucket sums (after `after_heavy`) of another job over the same bucket set, to continue from
 //   after_heavy (optional): recorded on the stream once every job's bucket sums are final
+// What a sparse run reads in place of an arrangement (msm_sparse_accum, msm.cuh; G1 only): the set holds live points at
+// the `nlive` ascending pair indices d_wires alone, and its bucket sums are formed from those pairs' scalars.
+struct g16_msm_sparse {
+  const void* d_scalars;     // the scalars the run's `sort` arranged (same n, same form: the sort's MsmParams hold both)
+  const uint32_t* d_wires;   // device; never null
+  uint32_t nlive;
+  const uint32_t* d_info;    // >= 3 zero words on the device: the job's view of the arrangement's counters (MsmJob::info)
+};
 struct g16_msm_run {
-  const g16_ctx::MsmSort* sort;
+  const g16_ctx::MsmSort* sort;   // (a sparse run takes its launch parameters from it and nothing else)
   g16_ctx::Buf* acc;            // workspace of this job (bucket sums first: see g16_msm_partial_ptr)
   const void* d_points;         // the tables of a registered set, or reduced-radix entries (to29_device); null = a set
                                 // that is infinity throughout: msm_accum (msm.cuh) then writes infinity to every bucket
@@ -261,6 +269,7 @@ struct g16_msm_run {
   void* d_out_aff;              // either may be null
   void* d_out_acc;
   const void* init_partial;
+  const g16_msm_sparse* sparse = nullptr;   // the accumulation is the sparse run (needs a table, takes no init_partial)
 };
 // `group` (1 / 2) is data to the prover, which walks its MSMs in a table: the one run-time choice of the curve below the C ABI
 int32_t g16_msm_batch(g16_ctx* ctx, hipStream_t stream, int group, const g16_msm_run* runs, int n_accum, int n_tail,
@@ -288,6 +297,11 @@ int32_t msm_device(g16_ctx* ctx, const void* d_scalars, uint32_t flags, const vo
 // the stages of phase 2 over the first `ny` jobs of a batch
 template <class C>
 int32_t stage_accum(g16_ctx* ctx, hipStream_t st, const g16::MsmParams& P, const g16::MsmBatch<C>& B, uint32_t ny);
+// the sparse run of one job (G1; msm_g1_misc.hip).  `own_entry`: the launch is the accumulate stage of its batch and goes
+// into the profile under that stage's name; otherwise it rides behind the stage's msm_accum launch, unlisted
+template <class C>
+int32_t stage_accum_sparse(g16_ctx* ctx, hipStream_t st, const g16::MsmParams& P, const g16_msm_sparse& sp,
+                           const void* d_points, void* d_partial, bool own_entry);
 // T: the tail plan of the batch (msm_plan.hpp), built once by msm_batch
 template <class C>
 int32_t stage_heavy(g16_ctx* ctx, hipStream_t st, const g16::MsmParams& P, const g16::MsmTailPlan& T,

@@ -44,7 +44,8 @@ inline bool points_sparse(size_t n_inf, size_t n, const G16Env& env) {
 //   DELTA  D in place of B1, where D holds few enough live points that dropping the others would pay against B1 as it
 //          stands by the rule of points_sparse: live_delta * 100 <= live_b1 * (100 - G16_INF_COMPACT) -- and where D's
 //          run costs no more than B1's did.  D has no arrangement of its own: its run reads the arrangement of all n
-//          pairs (ProofPlan::sort_b1), where an addition is skipped only if all 64 lanes of a wave meet infinity, so it
+//          pairs (ProofPlan::sort_b1; or, with a handful of live points, none at all: b1_sparse_run below), where an
+//          addition is skipped only if all 64 lanes of a wave meet infinity, so it
 //          costs up to min(n, 64 * live_delta) wave-level additions.  B1 as it stands costs n of them, or live_b1 where
 //          the key's B sets run on their compacted arrangement (points_sparse over the B1 points at infinity).  Against
 //          n, D never loses; against a compacted B1 it must have most waves empty: 64 * live_delta <= live_b1.
@@ -60,6 +61,14 @@ inline B1Form b1_fold_form(size_t live_b1, size_t live_delta, size_t n, const G1
   if (b1_compacted && live_delta * 64 > live_b1) return B1_PLAIN;
   return B1_DELTA;
 }
+// How a DELTA key's B1 job accumulates.  Through the arrangement of all n pairs the run still costs one table gather per
+// entry of that arrangement, whatever it finds.  With at most B1_SPARSE_MAX live differences over the whole wire range the
+// key also keeps the list of its live wires, and the job's bucket sums come from the sparse run (msm_sparse_accum,
+// msm.cuh), which reads those wires' scalars and nothing else: 64 wires x 13 windows of hits are a few KB of LDS.  Decided
+// once per key, from the same whole-range count as the form, so every shard of a key reaches the same answer.  (0: no
+// live difference -- such a key is EMPTY and has nothing to run.)
+constexpr size_t B1_SPARSE_MAX = 64;
+inline bool b1_sparse_run(size_t live_delta) { return live_delta != 0 && live_delta <= B1_SPARSE_MAX; }
 
 // ---- the entry lists of the B sets ---------------------------------------------------------------------------------------
 // B1 and B2 share one arrangement of the witness, so what it may leave out are the wires dead in BOTH sets.  Where that

@@ -9,6 +9,8 @@
 //          offsets, split-bucket segment list, buckets ordered by size.  (msm_count / msm_scatter / scan_* / perm_hist:
 //          the global-atomic variant, used when the partition count exceeds the LDS histogram and by G16_MSM_SORT=a)
 //   accum  msm_accum      one thread per bucket *segment* (<= L entries): XYZZ += affine table point, 9x29 field
+//          (msm_sparse_accum in its place for a set with a handful of live points: no arrangement read, the hits of the
+//          live pairs' digits from LDS)
 //   heavy  msm_heavy      buckets that were split in >1 segment: one thread (few segments) / LDS tree (many)
 //   reduce msm_reduce1/2  sum_k k*B_k: 16-bucket chunk running sums, then per slice an LDS suffix scan + tree; a slot
 //          of msm_reduce2 is one lane or a cooperating quad (Lane / Quad)
@@ -44,8 +46,9 @@ constexpr int MSM_BATCH_MAX = 3;
 template <class C>
 struct MsmJob {
   const typename Ec29<C>::Tab* points;   // window tables (registered set) or reduced-radix entries (one-shot)
-  const uint32_t* entries;               // the bucket arrangement it runs against (g16_ctx::MsmSort)
-  const uint32_t* offset;
+  const uint32_t* entries;               // the bucket arrangement it runs against (g16_ctx::MsmSort).  A sparse run
+  const uint32_t* offset;                // (msm_sparse_accum) read none: its view is `info` = zero words -- no extra
+                                         // segment, no split bucket -- and the other six null (reduce1: every bucket)
   const uint2* xseg;
   const uint32_t* info;
   const uint32_t* perm;
@@ -86,10 +89,14 @@ __device__ __forceinline__ void job_finish(typename C::Acc* out_acc, typename C:
 // (msm_class_bucket itself, and msm_class_slice -- the same layout seen from a slice, for the folds -- live in
 // msm_params.hpp: host and device code, and CPU tests, share them)
 
-// signed c-bit digits of a scalar, least significant window first.  The canonical scalar stays in its 8 registers
-// and is shifted right by c bits per window (8 funnel shifts with static register indices, c <= 22 < 32): no LDS
-// staging, no dynamic limb indexing, and any workgroup size.  (Rounds 1-2 staged the limbs in LDS and indexed them by
-// window: 36 KB of LDS per 1024 threads and two LDS reads per digit.)
+// the scalar of pair i in the canonical form the digit walk takes (`scalars_mont`: the witness came as Montgomery limbs)
+__device__ __forceinline__ u256 msm_scalar(const u256* __restrict__ scalars, uint32_t i, const MsmParams& P) {
+  u256 s = scalars[i];
+  if (P.scalars_mont) s = Fr::from_mont(s);
+  return s;
+}
+// signed c-bit digits of scalar i, least significant window first (msm_digit_walk, msm_params.hpp: the walk itself, which
+// host code and the sparse run share).
 // `live` (optional): bitmap over the pairs; a cleared bit drops the pair before its scalar is even read -- the entry
 // lists of point sets with many points at infinity ((0,0) for every wire absent from a matrix, curves.nim:95-107)
 // then hold only the points that can contribute.
@@ -97,48 +104,11 @@ template <class EMIT>
 __device__ __forceinline__ void msm_digits(const u256* __restrict__ scalars, const uint32_t* __restrict__ live, uint32_t i,
                                            const MsmParams& P, EMIT&& emit) {
   if (live && !((live[i >> 5] >> (i & 31)) & 1u)) return;
-  u256 s = scalars[i];
-  if (P.scalars_mont) s = Fr::from_mont(s);
+  u256 s = msm_scalar(scalars, i, P);
   if (Fr::is_zero(s)) return;
-  const uint32_t c = P.c, half = 1u << (c - 1), mask = (1u << c) - 1;
-  uint32_t carry = 0;
-  for (uint32_t w = 0; w < P.nwin; ++w) {
-    uint32_t raw = (s.v[0] & mask) + carry;
-    uint32_t neg = raw > half ? 1u : 0u;
-    uint32_t mag = neg ? (1u << c) - raw : raw;
-    carry = neg;
-    if (mag) {
-      if (P.mtab == 2) {   // (window + table selector, class bucket): the entry then indexes table [s][w]
-        uint32_t sel;
-        const uint32_t b = msm_class_bucket(mag, c, sel);
-        emit(w + sel * P.nwin, b, neg);
-      } else {
-        emit(w, mag - 1, neg);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 7; ++j) s.v[j] = __builtin_amdgcn_alignbit(s.v[j + 1], s.v[j], c);
-    s.v[7] >>= c;
-  }
+  msm_digit_walk(s.v, P, emit);
 }
-
-// Where the entry of digit (window w, pair i) goes: the offset of its bucket set, in units of 1 << shift buckets, and the
-// table-major index of its point.  LEAN: a set with tables at a stride >= 2 (msm_window_slot divides).  The two ends of
-// the family -- no tables, a table per window -- divide nothing and keep the expressions they always had; the host picks
-// the instantiation (g16_msm_sort).
-template <bool LEAN>
-__device__ __forceinline__ void msm_entry_place(const MsmParams& P, uint32_t w, uint32_t i, uint32_t shift,
-                                                uint32_t& set_off, uint32_t& pidx) {
-  if (LEAN) {
-    uint32_t table, set;
-    msm_window_slot(w, P.tstride, table, set);
-    set_off = set << shift;
-    pidx = table * P.n + i;
-  } else {
-    set_off = P.tables ? 0u : (w << shift);
-    pidx = P.tables ? (w * P.n + i) : i;
-  }
-}
+// (msm_entry_place -- where the entry of digit (window w, pair i) goes -- lives in msm_params.hpp beside the walk)
 
 template <bool LEAN>
 static __global__ void __launch_bounds__(MSM_BLOCK) msm_count(const u256* __restrict__ scalars,
@@ -613,6 +583,49 @@ msm_accum(const MsmBatch<C> B, MsmParams P, unsigned long long* __restrict__ clk
   }
 }
 
+// ---- K4s: the sparse run -- bucket sums of a set that holds only a handful of live points -----------------------------
+// The difference set D of a key with pointsB1 folded into pointsA1 (b1_fold_form, key_plan.hpp) is registered over all n
+// wires, and run through msm_accum it costs a 64-byte table gather per entry of the WHOLE arrangement -- 13.6 M of them at
+// 2^20, 0.87 GB -- to find infinity everywhere but on its few live wires.  This kernel reads no arrangement.  `wires` lists
+// the live pairs, ascending (at most B1_SPARSE_MAX of them, b1_sparse_run); every workgroup walks their scalars' digits
+// itself (msm_hit_list: the sort's own walk and placement, so a hit is exactly the entry the sort would have placed) into a
+// list in LDS, and every thread owns one bucket slot, scans the list in list order and adds the hits on its slot.  No
+// global atomic, no cleared buffer, no ordering between workgroups, a fixed addition order -- and every slot of the
+// nbuckets bucket sums is written, infinity where nothing hit, so the tail reads a fully written array.  There are no
+// extra segments: the job's view of the arrangement says so (msm_batch, msm_sort.hip).
+// The list is built SPARSE_HITS entries at a time -- whole wires, nwin slots each, MSM_HIT_NONE where a digit is 0 -- so
+// that any window count fits: one round for 64 wires of the 13 windows of c = 20.
+constexpr uint32_t SPARSE_HITS = 1024;
+template <class C>
+__global__ void __launch_bounds__(ACC_BLOCK) msm_sparse_accum(const typename Ec29<C>::Tab* __restrict__ points,
+                                                              const u256* __restrict__ scalars,
+                                                              const uint32_t* __restrict__ wires, uint32_t nlive,
+                                                              MsmParams P,
+                                                              typename Ec29<C>::Acc* __restrict__ partial) {
+  using E = Ec29<C>;
+  __shared__ MsmHit hits[SPARSE_HITS];
+  const uint32_t slot = blockIdx.x * ACC_BLOCK + threadIdx.x;
+  const uint32_t per = SPARSE_HITS / P.nwin;   // wires per round (nwin <= 255)
+  typename E::Acc acc = E::acc_inf();
+  for (uint32_t base = 0; base < nlive; base += per) {
+    const uint32_t m = nlive - base < per ? nlive - base : per;
+    for (uint32_t t = threadIdx.x; t < m; t += ACC_BLOCK) {
+      const uint32_t i = wires[base + t];
+      u256 s = msm_scalar(scalars, i, P);
+      MsmHit* h = hits + t * P.nwin;
+      for (uint32_t k = msm_hit_list(s.v, i, P, h); k < P.nwin; ++k) h[k].slot = MSM_HIT_NONE;
+    }
+    __syncthreads();
+    const uint32_t nh = m * P.nwin;
+    for (uint32_t e = 0; e < nh; ++e) {
+      const MsmHit h = hits[e];   // the same address on every lane: a broadcast
+      if (h.slot == slot) E::madd(acc, points + (h.entry & 0x7fffffffu), h.entry >> 31);
+    }
+    __syncthreads();   // the next round overwrites the list
+  }
+  if (slot < P.nbuckets) partial[slot] = acc;
+}
+
 // affine points in the reference layout (64 / 128 B, Montgomery R = 2^256) -> reduced-radix table entries
 template <class C>
 __global__ void __launch_bounds__(MSM_BLOCK) points_to29(const typename C::Aff* __restrict__ points, uint32_t n,
@@ -839,7 +852,7 @@ __global__ void __launch_bounds__(MSM_BLOCK, 1) msm_reduce1(const MsmBatch<C> B,
   const MsmJob<C>& J = B.job[blockIdx.y];
   const typename E::Acc* __restrict__ partial = J.partial;
   const uint32_t* __restrict__ offset = J.offset;
-  const bool always = J.init != nullptr;
+  const bool always = J.init != nullptr || offset == nullptr;   // (no offsets: a sparse run, which wrote every bucket)
   uint32_t j = blockIdx.x * MSM_BLOCK + threadIdx.x;
   uint32_t b0 = j * rc;
   if (b0 >= nbuckets) return;

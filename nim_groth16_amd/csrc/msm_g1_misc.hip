@@ -1,4 +1,6 @@
-// G1 registration-time tables, fixed-base multiples of gen1, on-curve check
+// G1 registration-time tables, fixed-base multiples of gen1, on-curve check; the sparse run of the accumulate stage
+// (msm_sparse_accum: built here, in the plain arithmetic configuration, and not beside msm_accum -- msm_g1_accum.o holds
+// the one hot loop that the instruction budgets are counted on)
 #include "msm_stage.cuh"
 template <>
 struct CurveConsts<G1> {
@@ -12,6 +14,8 @@ template int32_t precompute_device<G1>(g16_ctx*, const void*, size_t, uint32_t, 
 template int32_t fixed_base_device<G1>(g16_ctx*, void*, bool, const void*, uint32_t, size_t, void*);
 template int32_t on_curve_device<G1>(g16_ctx*, const void*, size_t, uint32_t*);
 template int32_t live_bitmap_device<G1>(g16_ctx*, const void*, size_t, uint32_t*, uint32_t*);
+template int32_t stage_accum_sparse<G1>(g16_ctx*, hipStream_t, const MsmParams&, const g16_msm_sparse&, const void*, void*,
+                                        bool);
 
 // the OR of two live bitmaps looks at no point: it sits here beside the kernel that makes them
 int32_t g16_bitmap_or_device(g16_ctx* ctx, uint32_t* d_out, const uint32_t* d_a, const uint32_t* d_b, size_t n,

@@ -96,6 +96,83 @@ G16_MSMP_HD uint32_t msm_class_bucket(uint32_t t, uint32_t c, uint32_t& s) {
   const uint32_t base = z == 0 ? 0u : z == 1 ? h / 2 : h / 2 + h / 8;
   return base + v;
 }
+// ---- the digits of a scalar and where they go: ONE definition, for the sort and for the sparse run ---------------------
+// Signed c-bit digits of a canonical scalar, least significant window first.  The scalar stays in its 8 words and is
+// shifted right by c bits per window (on the device: 8 funnel shifts with static register indices, c <= 22 < 32): no LDS
+// staging, no dynamic limb indexing, and any workgroup size.  (Rounds 1-2 staged the limbs in LDS and indexed them by
+// window: 36 KB of LDS per 1024 threads and two LDS reads per digit.)  A window value above 2^(c-1), carry included,
+// becomes the negative digit value - 2^c with a carry into the next window; digit 0 emits nothing.
+//   emit(w + table selector * nwin, bucket, negative)   class bucket set (mtab == 2): the entry then indexes table [s][w]
+//   emit(w, magnitude - 1, negative)                    every other set
+// `s` is consumed.
+template <class EMIT>
+G16_MSMP_HD void msm_digit_walk(uint32_t (&s)[8], const MsmParams& P, EMIT&& emit) {
+  const uint32_t c = P.c, half = 1u << (c - 1), mask = (1u << c) - 1;
+  uint32_t carry = 0;
+  for (uint32_t w = 0; w < P.nwin; ++w) {
+    uint32_t raw = (s[0] & mask) + carry;
+    uint32_t neg = raw > half ? 1u : 0u;
+    uint32_t mag = neg ? (1u << c) - raw : raw;
+    carry = neg;
+    if (mag) {
+      if (P.mtab == 2) {
+        uint32_t sel;
+        const uint32_t b = msm_class_bucket(mag, c, sel);
+        emit(w + sel * P.nwin, b, neg);
+      } else {
+        emit(w, mag - 1, neg);
+      }
+    }
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+    for (int j = 0; j < 7; ++j) s[j] = __builtin_amdgcn_alignbit(s[j + 1], s[j], c);
+#else
+    for (int j = 0; j < 7; ++j) s[j] = (s[j] >> c) | (s[j + 1] << (32 - c));
+#endif
+    s[7] >>= c;
+  }
+}
+// Where the entry of digit (window w, pair i) goes: the offset of its bucket set, in units of 1 << shift buckets, and the
+// table-major index of its point.  LEAN: a set with tables at a stride >= 2 (msm_window_slot divides).  The two ends of
+// the family -- no tables, a table per window -- divide nothing and keep the expressions they always had; the host picks
+// the instantiation (g16_msm_sort).
+template <bool LEAN>
+G16_MSMP_HD void msm_entry_place(const MsmParams& P, uint32_t w, uint32_t i, uint32_t shift, uint32_t& set_off,
+                                 uint32_t& pidx) {
+  if (LEAN) {
+    uint32_t table, set;
+    msm_window_slot(w, P.tstride, table, set);
+    set_off = set << shift;
+    pidx = table * P.n + i;
+  } else {
+    set_off = P.tables ? 0u : (w << shift);
+    pidx = P.tables ? (w * P.n + i) : i;
+  }
+}
+// The sparse run of a point set with a handful of live points (msm_sparse_accum, msm.cuh) reads no arrangement: it forms
+// the entries of its live pairs itself.  A hit is what the sort would have placed for one digit -- the bucket, which is
+// also the slot of its sum, and the entry, the table-major point index | sign << 31 -- and the hits of pair i with the
+// canonical scalar s (consumed) come out in window order: out has room for P.nwin of them.  -> their number
+struct MsmHit {
+  uint32_t slot, entry;
+};
+constexpr uint32_t MSM_HIT_NONE = 0xffffffffu;   // in `slot`: no hit
+G16_MSMP_HD uint32_t msm_hit_list(uint32_t (&s)[8], uint32_t i, const MsmParams& P, MsmHit* out) {
+  uint32_t k = 0;
+  const uint32_t shift = P.c - 1;
+  msm_digit_walk(s, P, [&](uint32_t w, uint32_t b, uint32_t neg) {
+    uint32_t set_off, pidx;
+    if (P.tstride >= 2)
+      msm_entry_place<true>(P, w, i, shift, set_off, pidx);
+    else
+      msm_entry_place<false>(P, w, i, shift, set_off, pidx);
+    out[k].slot = set_off + b;
+    out[k].entry = pidx | (neg << 31);
+    ++k;
+  });
+  return k;
+}
+
 // Slice v of the class set (MSM_CLASS_SLICES slices of 2^(c-7) buckets, in msm_class_bucket's bucket order): its class
 // z (0, 1, 2; 3 = X), the slices [first, end) of that class, and the doublings that scale the slice's two terms in the
 // fold by 4^z (msm_fold_classes, msm.cuh): y_v = 4^z (2 W_v - T_v) starts from 2 W_v, so that X's 64 W_v takes 5;

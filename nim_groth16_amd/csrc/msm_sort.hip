@@ -121,9 +121,30 @@ static int32_t msm_batch(g16_ctx* ctx, hipStream_t st, const g16_msm_run* runs, 
     J.init = (const typename Ec29<C>::Acc*)runs[j].init_partial;
     J.out_aff = (typename C::Aff*)runs[j].d_out_aff;
     J.out_acc = (typename C::Acc*)runs[j].d_out_acc;
+    if (runs[j].sparse) {
+      // the job read no arrangement: no extra segment and no split bucket (zero counters), slot = bucket, every bucket
+      // written -- a view of its own, so that nothing of the tail looks into the sort the other jobs share
+      J.entries = J.offset = J.perm = J.heavy = J.xoff = nullptr;
+      J.xseg = nullptr;
+      J.info = runs[j].sparse->d_info;
+    }
   }
+  // the accumulate stage: msm_accum over the jobs that run against their arrangement -- the batch without the sparse
+  // ones, in order -- and the sparse run of each of the others.  One profile entry for the stage either way.
+  MsmBatch<C> D = B;
+  int n_dense = 0;
+  for (int j = 0; j < n_accum; ++j)
+    if (!runs[j].sparse) D.job[n_dense++] = B.job[j];
   int32_t rc;
-  if ((rc = stage_accum<C>(ctx, st, P, B, n_accum))) return rc;
+  if (n_dense && (rc = stage_accum<C>(ctx, st, P, D, n_dense))) return rc;
+  bool listed = n_dense != 0;
+  for (int j = 0; j < n_accum; ++j) {
+    if (!runs[j].sparse) continue;
+    if constexpr (sizeof(typename C::Aff) == 64) {
+      if ((rc = stage_accum_sparse<C>(ctx, st, P, *runs[j].sparse, runs[j].d_points, B.job[j].partial, !listed))) return rc;
+      listed = true;
+    }
+  }
   if ((rc = stage_heavy<C>(ctx, st, P, T, B, n_accum))) return rc;
   if (after_heavy) HIPCHK(ctx, hipEventRecord(after_heavy, st));
   if (!n_tail) return G16_OK;
@@ -136,6 +157,13 @@ int32_t g16_msm_batch(g16_ctx* ctx, hipStream_t stream, int group, const g16_msm
   for (int i = 0; i < n_accum; ++i)
     if (!runs[i].d_points && runs[i].init_partial) {
       ctx->err = "an MSM run without a table cannot continue another run's bucket sums";
+      return G16_EINVAL;
+    }
+  // the sparse run is G1's, gathers from a table and starts every bucket from infinity
+  for (int i = 0; i < n_accum; ++i)
+    if (runs[i].sparse && (group != 1 || !runs[i].d_points || runs[i].init_partial || !runs[i].sparse->d_wires ||
+                           !runs[i].sparse->d_info || !runs[i].sparse->d_scalars)) {
+      ctx->err = "a sparse MSM run needs a G1 table, its scalars and wire list, and continues no other run";
       return G16_EINVAL;
     }
   return group == 1 ? msm_batch<G1>(ctx, stream, runs, n_accum, n_tail, after_heavy)

@@ -19,6 +19,25 @@ int32_t stage_accum(g16_ctx* ctx, hipStream_t st, const MsmParams& P, const MsmB
   return G16_OK;
 }
 
+// The sparse run of one job: the same grid over the bucket slots as msm_accum's, without the extra segments -- the run has
+// none.  Under the profile name of the accumulate stage it stands for (one launch of a proof, as ever).
+template <class C>
+int32_t stage_accum_sparse(g16_ctx* ctx, hipStream_t st, const MsmParams& P, const g16_msm_sparse& sp, const void* d_points,
+                           void* d_partial, bool own_entry) {
+  static_assert(sizeof(typename C::Aff) == 64, "the sparse run is instantiated for G1");
+  const dim3 grid((P.nbuckets + ACC_BLOCK - 1) / ACC_BLOCK);
+  const auto* points = (const typename Ec29<C>::Tab*)d_points;
+  auto* partial = (typename Ec29<C>::Acc*)d_partial;
+  if (own_entry)
+    KLAUNCH_ON(ctx, st, "msm_accum_g1", msm_sparse_accum<C>, grid, ACC_BLOCK, 0, points, (const u256*)sp.d_scalars, sp.d_wires,
+               sp.nlive, P, partial);
+  else
+    hipLaunchKernelGGL(msm_sparse_accum<C>, grid, dim3(ACC_BLOCK), 0, st, points, (const u256*)sp.d_scalars, sp.d_wires,
+                       sp.nlive, P, partial);
+  HIPCHK(ctx, hipGetLastError());
+  return G16_OK;
+}
+
 template <class C>
 int32_t stage_heavy(g16_ctx* ctx, hipStream_t st, const MsmParams& P, const MsmTailPlan& T, const MsmBatch<C>& B,
                     uint32_t ny) {

@@ -40,6 +40,14 @@ extern "C" int32_t g16_pkey_b1_fold(const g16_pkey* k, size_t out[3]) {
   return G16_OK;
 }
 
+// out[0] = 1 if the key's B1 job takes the sparse run (a DELTA key with at most out[2] = B1_SPARSE_MAX live differences
+// over its whole wire range), out[1] = the live differences in THIS key's wire range
+extern "C" int32_t g16_pkey_b1_sparse(const g16_pkey* k, size_t out[3]) {
+  if (!k || !out) return G16_EINVAL;
+  out[0] = k->b1_sparse ? 1 : 0, out[1] = k->b1_nlive, out[2] = B1_SPARSE_MAX;
+  return G16_OK;
+}
+
 extern "C" int32_t g16_pkey_abc_info(const g16_pkey* k, size_t out[11]) {
   if (!k || !out) return G16_EINVAL;
   out[0] = k->ncoeffs;
@@ -154,6 +162,30 @@ static int32_t b1_form_of_whole_arrays(g16_ctx* ctx, const g16_pkey_desc* d, g16
   return G16_OK;
 }
 
+// ... and, for a DELTA key with few enough live differences (b1_sparse_run: the whole-range count decides for every
+// shard), the live wires of this shard's range, read off the bitmap the registration of D has just made.  A shard whose
+// range holds none keeps an empty list: its sparse run writes infinity throughout.
+static int32_t b1_live_wires(g16_ctx* ctx, g16_pkey* k) {
+  if (!b1_sparse_run(k->live_delta)) return G16_OK;
+  const size_t nw = k->w.size(), words = (nw + 31) / 32;
+  std::vector<uint32_t> bitmap(words), list(g16_pkey::B1_VIEW_WORDS, 0u);
+  HIPCHK(ctx, hipMemcpyAsync(bitmap.data(), k->B1->d_live.get(), words * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  for (size_t i = 0; i < nw; ++i)
+    if ((bitmap[i >> 5] >> (i & 31)) & 1u) list.push_back((uint32_t)i);
+  const size_t nlive = list.size() - g16_pkey::B1_VIEW_WORDS;
+  if (nlive > B1_SPARSE_MAX || nlive != nw - k->B1->n_inf) {
+    ctx->err = "the live differences of pointsB1 do not match their count";
+    return G16_EINVAL;
+  }
+  list.push_back(0u);   // (an empty list still has an address)
+  HIPCHK(ctx, dev_alloc(k->b1_sparse, list.size() * 4));
+  HIPCHK(ctx, hipMemcpyAsync(k->b1_sparse.get(), list.data(), list.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  k->b1_nlive = (uint32_t)nlive;
+  return G16_OK;
+}
+
 // 3. pointsB1 of this shard's wires, or what stands in for it
 static int32_t register_b1(g16_ctx* ctx, const g16_pkey_desc* d, uint32_t table_stride, g16_pkey* k) {
   const size_t nw = k->w.size();
@@ -187,7 +219,8 @@ static int32_t register_b1(g16_ctx* ctx, const g16_pkey_desc* d, uint32_t table_
   });
   if (rc) return rc;
   k->b1_inf = n_inf;
-  return g16_points_register_g1_lean_dev(ctx, d_b1.get(), nw, table_stride, &k->B1);
+  if ((rc = g16_points_register_g1_lean_dev(ctx, d_b1.get(), nw, table_stride, &k->B1))) return rc;
+  return b1_live_wires(ctx, k);
 }
 
 // pointsC1 covers wires npubs+1 .. nvars-1 (zkey_types.nim:40; zs = witness[npubs+1..], prover.nim:262-264).

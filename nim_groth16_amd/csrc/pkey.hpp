@@ -34,4 +34,10 @@ struct g16_pkey {
   int b1_form = g16::B1_PLAIN;
   size_t b1_inf = 0;              // (0,0) points of pointsB1 itself in this key's wire range
   size_t live_b1 = 0, live_delta = 0;   // over the WHOLE wire range: what the form was decided from
+  // B1_DELTA with few enough live differences (b1_sparse_run): the B1 job runs sparse.  One allocation: B1_VIEW_WORDS
+  // zero words -- the job's view of an arrangement's counters, MsmJob::info: no extra segment, no split bucket -- then the
+  // live wires of this shard's range, ascending and relative to its first wire (b1_nlive of them; a shard may hold none)
+  static constexpr size_t B1_VIEW_WORDS = 16;
+  DevMem<uint32_t> b1_sparse;   // empty: the run reads the arrangement of all pairs
+  uint32_t b1_nlive = 0;
 };

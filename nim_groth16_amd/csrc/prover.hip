@@ -89,6 +89,14 @@ static int32_t run_plan(g16_ctx* ctx, const g16_pkey* k, ProofEntry entry, uint3
       {&ctx->sort[SORT_W], &L[3].acc, k->C1->d_tables.get(), nullptr, slots + PART_C, nullptr},
       {&ctx->sort[plan.sort_b], &L[1].acc, k->B2->d_tables.get(), nullptr, slots + PART_B2, nullptr},
       {&ctx->sort[SORT_H], &L[4].acc, k->H1->d_tables.get(), nullptr, slots + PART_H, nullptr}};
+  // A DELTA key with a handful of live differences (b1_sparse_run, decided when the key was made): the B1 job forms its
+  // bucket sums from the witness values of those wires alone.  It keeps its place in the plan -- same step, same stream,
+  // same waits -- and takes from the witness arrangement only the launch parameters, which every job of the witness shares.
+  g16_msm_sparse b1_sparse{d_wr, nullptr, k->b1_nlive, k->b1_sparse.get()};
+  if (k->b1_sparse) {
+    b1_sparse.d_wires = k->b1_sparse.get() + g16_pkey::B1_VIEW_WORDS;
+    runs[RUN_B1].sparse = &b1_sparse;
+  }
   auto event = [&](int e) { return e == EV_NONE ? nullptr : e < EV_COUNT ? ctx->ev[e].get() : L[e - EV_DONE0].done.get(); };
   for (int i = 0; i < plan.count; ++i) {
     const ProofStep& s = plan.steps[i];
