@@ -508,3 +508,33 @@ proc circuitSetup*(r1cs: R1CS, ptau: G16PtauDesc, flavour = Snarkjs, delta: ptr 
                            domainSize: domSize, logDomainSize: logDom)
   return ZKey(header: header, specPoints: spec, vPoints: VerifierPoints(pointsIC: ic), pPoints: pts,
               coeffs: r1csToCoeffs(r1cs))
+
+# --- phase-2 contribution (include/g16hip.h "scaling an array of points", "phase-2 contribution") -------------------------
+# Declarations only.  g16_key_contribute turns the key of circuitSetup (delta = 1) into a sound one; the library hashes and
+# draws nothing: the secrets and the challenge point are the caller's, and the transcript rule of the Python package
+# (nim_groth16_amd/phase2.py) is the project's own, not snarkjs's.
+type
+  G16Phase2Key* {.importc: "g16_phase2_key", header: "g16hip.h", bycopy.} = object
+    delta1*, delta2*, pointsC1*, pointsH1*: pointer
+    nc1*, nh1*: csize_t
+  G16Contribution* {.importc: "g16_contribution", header: "g16hip.h", bycopy.} = object
+    delta_after*, g1_s*, g1_sx*: array[64, uint8]
+    g2_spx*: array[128, uint8]
+  G16Phase2Out* {.importc: "g16_phase2_out", header: "g16hip.h", bycopy.} = object
+    delta1*, delta2*, pointsC1*, pointsH1*: pointer
+    record*: ptr G16Contribution
+  G16ChainReport* {.importc: "g16_chain_report", header: "g16hip.h", bycopy.} = object
+    failed*: uint32
+    relation*: array[7, int32]
+    first_record*: array[2, csize_t]
+    first_bad*, bad_count*: array[9, array[3, csize_t]]
+    first_infinity*: array[9, csize_t]
+proc g16_points_scale_g1(ctx: ptr G16Ctx, points: pointer, n: csize_t, k: pointer, flags: uint32,
+                         res: pointer): int32 {.importc, header: "g16hip.h".}
+proc g16_points_scale_g2(ctx: ptr G16Ctx, points: pointer, n: csize_t, k: pointer, flags: uint32,
+                         res: pointer): int32 {.importc, header: "g16hip.h".}
+proc g16_key_contribute(ctx: ptr G16Ctx, key: ptr G16Phase2Key, d, s: pointer, flags: uint32, challenge_g2: pointer,
+                        res: ptr G16Phase2Out): int32 {.importc, header: "g16hip.h".}
+proc g16_contributions_verify(ctx: ptr G16Ctx, initial, final: ptr G16Phase2Key, records: ptr G16Contribution,
+                              challenges_g2: pointer, count: csize_t, c1_multipliers, h1_multipliers: pointer,
+                              res: ptr G16ChainReport): int32 {.importc, header: "g16hip.h".}

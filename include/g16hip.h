@@ -236,10 +236,12 @@ int32_t g16_points_intt_g2(g16_ctx* ctx, const void* points, uint32_t log2n, voi
  * the powers of that tau, byte for byte, and it passes g16_circuit_audit against the same r1cs and ptau.
  * SOUNDNESS: gamma = 1 always, and with delta == NULL delta = 1 as well -- exactly the key of `snarkjs zkey new`.  Such a
  * key is NOT fit for production: anyone can forge proofs for it.  It becomes sound only after a phase-2 contribution
- * (`snarkjs zkey contribute`: delta replaced by a secret, pointsC1 / pointsH1 rescaled).  A caller-supplied delta is that
- * step for a caller who may know delta; it is toxic waste of the caller's.
- * Out of scope: the contribution transcript of a .zkey (section 10 and its hashes); the pre-computed Lagrange sections
- * 12-15 of a "prepared" .ptau -- the call always works from the monomial sections 2-6.
+ * (`snarkjs zkey contribute`: delta replaced by a secret, pointsC1 / pointsH1 rescaled): g16_key_contribute, below, and
+ * g16_contributions_verify for whoever receives the key.  A caller-supplied delta is that step for a caller who may know
+ * delta; it is toxic waste of the caller's.
+ * Not part of this call: the contribution transcript of a .zkey (section 10 and its hashes) -- the contribution calls
+ * below make and check its records, the hashes stay with the caller; the pre-computed Lagrange sections
+ * 12-15 of a "prepared" .ptau are out of scope -- the call always works from the monomial sections 2-6.
  * Before any arithmetic the element passes of g16_circuit_audit run over the ptau elements the call reads (tauG1[0 .. 2n),
  * tauG2 / alphaTauG1 / betaTauG1 [0 .. n), betaG2): canonical and on the curve for every element, the order-r subgroup
  * for the G2 arrays.  An element that fails is G16_EINVAL; g16_last_error names section, index and check in the words
@@ -667,12 +669,102 @@ typedef struct {
  * 2^(power+1) - 1 powers); a sharded key description; everything g16_key_audit rejects.
  * What the call does NOT cover:
  *   - the ptau is the trusted anchor: its self-consistency (`snarkjs powersoftau verify`) is out of scope;
- *   - the phase-2 contribution chain and its hashes (section 10 of a .zkey) are out of scope;
+ *   - the phase-2 contribution chain (section 10 of a .zkey) is not walked here: g16_contributions_verify, below, checks
+ *     its records against an initial key that this call has tied to the circuit; the hashes stay with the caller;
  *   - gamma and delta are taken from the key: a legitimately contributed key (delta changed, pointsC1 and pointsH1
  *     rescaled) passes, as it should. */
 int32_t g16_circuit_audit(g16_ctx* ctx, const g16_pkey_desc* desc, const g16_vkey_desc* vk, const void* section4,
                           size_t section4_bytes, const g16_r1cs_desc* r1cs, const g16_ptau_desc* ptau,
                           const void* wire_multipliers, const void* h_multipliers, g16_circuit_report* out);
+
+/* ---- scaling an array of points by ONE scalar ------------------------------------------------------------------------
+ * out[i] = k * points[i]; host pointers, affine Montgomery in and out, (0,0) legal anywhere; k: 32 bytes, canonical,
+ * flags = G16_SCALARS_MONT or G16_SCALARS_STD; k == 0 is legal (all infinity); n < 2^31.  out may be points.
+ * The points must be on the curve (g16_points_audit_*): the G1 path multiplies through the endomorphism
+ * (x, y) -> (beta x, y), which is only the multiplication by lambda on the curve itself.  G1: the scalar is split as
+ * k = k1 + k2 lambda with halves below 2^128 on the host and every lane walks the same joint-sparse-form schedule (~127
+ * doublings, ~64 mixed additions); G2: the plain 254-bit ladder.  Both share one field inversion among the four points of
+ * a lane for the affine output.  Outputs are canonical affine bytes.  The call changes no context state. */
+int32_t g16_points_scale_g1(g16_ctx* ctx, const void* points, size_t n, const void* k, uint32_t flags, void* out);
+int32_t g16_points_scale_g2(g16_ctx* ctx, const void* points, size_t n, const void* k, uint32_t flags, void* out);
+
+/* ---- phase-2 contribution: what makes the key of g16_circuit_setup(delta = NULL) sound ------------------------------
+ * `snarkjs zkey contribute` and the walk of `snarkjs zkey verify` over the contribution chain, as arithmetic: the library
+ * hashes nothing and draws nothing.  The secret d, the proof-of-knowledge secret s and the challenge point of a
+ * contribution are the CALLER's, like every multiplier in this ABI (Python: nim_groth16_amd/phase2.py derives the
+ * challenges from a BLAKE2b transcript -- the project's own rule, NOT snarkjs's: see there).  Host pointers, affine
+ * Montgomery points throughout. */
+typedef struct {                      /* the part of a key a contribution touches */
+  const void *delta1, *delta2;        /* 64 B, 128 B */
+  const void *pointsC1, *pointsH1;    /* nc1 and nh1 G1 points (nc1 == 0: pointsC1 may be NULL) */
+  size_t nc1, nh1;
+} g16_phase2_key;
+typedef struct {                      /* one record of the chain: 320 bytes */
+  uint8_t delta_after[64];            /* delta1 after this contribution */
+  uint8_t g1_s[64], g1_sx[64];        /* s gen1, d s gen1 */
+  uint8_t g2_spx[128];                /* d * challenge */
+} g16_contribution;
+typedef struct {                      /* host buffers the caller owns, sized as the input key's; may not overlap it */
+  void *delta1, *delta2, *pointsC1, *pointsH1;
+  g16_contribution* record;
+} g16_phase2_out;
+/* delta1' = d delta1, delta2' = d delta2, pointsC1' = d^-1 pointsC1, pointsH1' = d^-1 pointsH1 (the two arrays through the
+ * kernel of g16_points_scale_g1), record = { delta1', s gen1, d s gen1, d challenge_g2 }.
+ * d, s: 32 bytes each, canonical, non-zero, in the form `flags` names (G16_SCALARS_MONT or G16_SCALARS_STD).
+ * Before any arithmetic the key's elements go through the element passes of g16_points_audit_*: canonical and on the
+ * curve for delta1, pointsC1, pointsH1; also the order-r subgroup for delta2 and the challenge.  An element that fails
+ * is G16_EINVAL; g16_last_error names section, index and check in the audit's words ("pointsH1[3] is not on the curve").
+ * G16_EINVAL also: a null pointer; flags other than the two; d or s zero or >= r; delta1, delta2 or the challenge (0,0).
+ * No output is promised after a failure.  The call changes no context state (a context proves the same bytes before and
+ * after) and runs on the context's stream with one wait after the element passes and one at the end. */
+int32_t g16_key_contribute(g16_ctx* ctx, const g16_phase2_key* key, const void* d, const void* s, uint32_t flags,
+                           const void* challenge_g2, g16_phase2_out* out);
+
+/* The chain.  `initial` is the ANCHOR: the key before any contribution, which the caller built with g16_circuit_setup or
+ * established with g16_circuit_audit -- it is trusted here and not examined.  `final_` is the key under test, `records`
+ * the `count` contributions between them in order, challenges_g2[j] the G2 challenge point sp_j of record j (128 B each;
+ * the caller re-derives them from its transcript).  The arrays of a report, in order: */
+#define G16_CHAIN_ARRAYS 9
+enum {
+  G16_CHAIN_DELTA_AFTER = 0, G16_CHAIN_G1_S, G16_CHAIN_G1_SX, G16_CHAIN_G2_SPX, G16_CHAIN_CHALLENGES,   /* count elements */
+  G16_CHAIN_FINAL_DELTA1, G16_CHAIN_FINAL_DELTA2, G16_CHAIN_FINAL_POINTS_C1, G16_CHAIN_FINAL_POINTS_H1
+};
+#define G16_CHAIN_RELATIONS 7
+enum {
+  G16_CHAIN_ELEMENTS = 0, G16_CHAIN_POK, G16_CHAIN_STEP, G16_CHAIN_LAST, G16_CHAIN_DELTA, G16_CHAIN_C1, G16_CHAIN_H1
+};
+typedef struct {
+  uint32_t failed;                          /* bit k set: relation k (G16_CHAIN_*) is 0; 0 = the chain leads from initial to final */
+  int32_t relation[G16_CHAIN_RELATIONS];    /* 1 = holds, 0 = fails, -1 = not run */
+  size_t first_record[2];                   /* the first record whose POK / STEP fails, (size_t)-1: none */
+  size_t first_bad[G16_CHAIN_ARRAYS][3];    /* per array and check, as g16_points_audit_* */
+  size_t bad_count[G16_CHAIN_ARRAYS][3];
+  size_t first_infinity[G16_CHAIN_ARRAYS];  /* first (0,0) element of the five record arrays and of final delta1 / delta2, (size_t)-1: none */
+} g16_chain_report;
+/*   ELEMENTS  every point of the nine arrays is canonical and on its curve, the G2 ones (g2_spx, challenges, final delta2)
+ *             in the order-r subgroup, and no delta_after, g1_s, g1_sx, g2_spx, challenge, final delta1 or delta2 is (0,0)
+ *   POK       for every record j: e(g1_s, g2_spx) == e(g1_sx, sp_j)             (the contributor knew d: g2_spx = d sp_j)
+ *   STEP      for every record j: e(delta_(j-1), g2_spx) == e(delta_after_j, sp_j), delta_0 = initial->delta1
+ *   LAST      final->delta1 == records[count-1].delta_after byte for byte; count == 0: == initial->delta1
+ *   DELTA     e(final.delta1, gen2) == e(gen1, final.delta2)
+ *   C1        e(MSM(z, C1_initial), delta2_initial) == e(MSM(z, C1_final), delta2_final); nc1 == 0: holds trivially
+ *   H1        the same with y over pointsH1
+ * A relation is -1 when an array it reads failed ELEMENTS (POK: g1_s, g1_sx, g2_spx, challenges; STEP: delta_after,
+ * g2_spx, challenges; LAST: delta_after, final delta1; DELTA: final delta1, delta2; C1 / H1: final delta2 and the
+ * array).  Every pairing equation is one product of two Miller loops and one final exponentiation in the kernel of the
+ * circuit audit's point relations, all of them side by side in ONE launch (a record costs two such products: four Miller
+ * loops, two final exponentiations); the four sums are the one-shot MSM; no new arithmetic.
+ * c1_multipliers: nc1 x 16 bytes, h1_multipliers: nh1 x 16 bytes, under the rules of g16_verify_batch: little-endian
+ * 128-bit integers, every one non-zero, drawn by the CALLER from a CSPRNG after every input is fixed.  A zero multiplier
+ * is G16_EINVAL and g16_last_error names its index.  Soundness of C1 / H1 as there: if the final array is not one
+ * multiple (delta_initial / delta_final) of the initial one, the relation is a non-zero linear form in the multipliers
+ * and holds with probability at most 1/(2^128 - 1).  POK, STEP, LAST and DELTA are exact.
+ * G16_EINVAL also: a null pointer; initial->nc1 != final_->nc1 or nh1 likewise; count >= 2^20; nc1 or nh1 >= 2^27 (the
+ * limit of the one-shot MSM, as for g16_points_pairs_check).
+ * The call changes no context state; one wait after the element passes and one at the end. */
+int32_t g16_contributions_verify(g16_ctx* ctx, const g16_phase2_key* initial, const g16_phase2_key* final_,
+                                 const g16_contribution* records, const void* challenges_g2, size_t count,
+                                 const void* c1_multipliers, const void* h1_multipliers, g16_chain_report* out);
 
 /* ---- profiling ---------------------------------------------------------------------------------- */
 /* on = 1: every kernel launch is bracketed by HIP events on the stream it is launched on; on = 2: only the

@@ -35,6 +35,7 @@ SYMBOLS = [
     "g16_points_audit_g1", "g16_points_audit_g2", "g16_points_pairs_check", "g16_key_audit",
     "g16_pkey_b1_fold", "g16_pkey_b1_sparse", "g16_circuit_audit",
     "g16_points_intt_g1", "g16_points_intt_g2", "g16_circuit_setup",
+    "g16_points_scale_g1", "g16_points_scale_g2", "g16_key_contribute", "g16_contributions_verify",
 ]
 VERIFY_SUBGROUP = 16
 GT_BYTES = 384
@@ -211,6 +212,98 @@ class CircuitReport:
         return "circuit audit: FAILED\n" + "\n".join("  " + f for f in self.findings())
 
 
+class Phase2Key(ctypes.Structure):
+    """g16_phase2_key (include/g16hip.h): the part of a key a contribution touches"""
+    _fields_ = [("delta1", ctypes.c_void_p), ("delta2", ctypes.c_void_p), ("pointsC1", ctypes.c_void_p),
+                ("pointsH1", ctypes.c_void_p), ("nc1", ctypes.c_size_t), ("nh1", ctypes.c_size_t)]
+
+
+class ContributionC(ctypes.Structure):
+    """g16_contribution (include/g16hip.h): 320 bytes"""
+    _fields_ = [("delta_after", ctypes.c_uint8 * 64), ("g1_s", ctypes.c_uint8 * 64), ("g1_sx", ctypes.c_uint8 * 64),
+                ("g2_spx", ctypes.c_uint8 * 128)]
+
+
+CONTRIBUTION_BYTES = 320
+assert ctypes.sizeof(ContributionC) == CONTRIBUTION_BYTES
+
+
+class Phase2Out(ctypes.Structure):
+    """g16_phase2_out (include/g16hip.h)"""
+    _fields_ = [("delta1", ctypes.c_void_p), ("delta2", ctypes.c_void_p), ("pointsC1", ctypes.c_void_p),
+                ("pointsH1", ctypes.c_void_p), ("record", ctypes.POINTER(ContributionC))]
+
+
+# contribution chain (include/g16hip.h): the arrays and the relations of a report in order
+CHAIN_ARRAYS = ("delta_after", "g1_s", "g1_sx", "g2_spx", "challenges", "final delta1", "final delta2", "final pointsC1",
+                "final pointsH1")
+CHAIN_RELATIONS = ("ELEMENTS", "POK", "STEP", "LAST", "DELTA", "C1", "H1")
+
+
+class ChainReportC(ctypes.Structure):
+    """g16_chain_report (include/g16hip.h)"""
+    _fields_ = [("failed", ctypes.c_uint32), ("relation", ctypes.c_int32 * len(CHAIN_RELATIONS)),
+                ("first_record", ctypes.c_size_t * 2),
+                ("first_bad", (ctypes.c_size_t * 3) * len(CHAIN_ARRAYS)),
+                ("bad_count", (ctypes.c_size_t * 3) * len(CHAIN_ARRAYS)),
+                ("first_infinity", ctypes.c_size_t * len(CHAIN_ARRAYS))]
+
+
+class ChainReport:
+    """What g16_contributions_verify found: relation[k] = 1 (holds), 0 (fails) or -1 (not run) for CHAIN_RELATIONS[k];
+    first_record = the first record whose POK / STEP fails, or None; first_bad / bad_count [array][check] for
+    CHAIN_ARRAYS as in a KeyReport; first_infinity[array] = the first (0,0) element, or None.  `transcript`: None from
+    the C call, which hashes nothing; setup.verifyContributions sets it to 1 / 0: the key's cs_hash is the initial key's
+    and every stored transcript hash is the one its predecessors give (the challenges are always re-derived)."""
+
+    def __init__(self, failed, relation, first_record, first_bad, bad_count, first_infinity, transcript=None):
+        self.failed, self.relation, self.first_record = failed, list(relation), list(first_record)
+        self.first_bad, self.bad_count, self.first_infinity = first_bad, bad_count, list(first_infinity)
+        self.transcript = transcript
+
+    @property
+    def ok(self) -> bool:
+        """the records lead from the initial key to the final one"""
+        return self.failed == 0 and self.transcript != 0
+
+    def as_dict(self) -> dict:
+        return {"failed": self.failed, "relation": self.relation, "first_record": self.first_record,
+                "first_bad": self.first_bad, "bad_count": self.bad_count, "first_infinity": self.first_infinity,
+                "transcript": self.transcript}
+
+    def findings(self):
+        out = []
+        if self.transcript == 0:
+            out.append("the transcript hashes are not those of the initial key and the records")
+        for a, name in enumerate(CHAIN_ARRAYS):
+            for k, check in enumerate(AUDIT_CHECKS):
+                if self.bad_count[a][k]:
+                    what = {"canonical": "is not a canonical encoding", "curve": "is not on the curve",
+                            "subgroup": "is not in the order-r subgroup"}[check]
+                    more = self.bad_count[a][k] - 1
+                    out.append(f"{name}[{self.first_bad[a][k]}] {what}" + (f" (and {more} more)" if more else ""))
+            if self.first_infinity[a] is not None:
+                out.append(f"{name}[{self.first_infinity[a]}] is the point at infinity")
+        if self.relation[1] == 0:
+            out.append(f"record {self.first_record[0]}: the proof of knowledge does not hold")
+        if self.relation[2] == 0:
+            out.append(f"record {self.first_record[1]}: delta_after is not the contribution's multiple of the delta before")
+        if self.relation[3] == 0:
+            out.append("the final delta1 is not the last record's delta_after")
+        if self.relation[4] == 0:
+            out.append("the final delta1 / delta2 are not the same multiple of the two generators")
+        for k in (5, 6):
+            if self.relation[k] == 0:
+                out.append(f"the final points{CHAIN_RELATIONS[k]} is not the initial one rescaled by the deltas")
+        return out
+
+    def __str__(self):
+        if self.ok:
+            skipped = [CHAIN_RELATIONS[k] for k in range(len(CHAIN_RELATIONS)) if self.relation[k] < 0]
+            return "contribution chain: ok" + (f" (not run: {', '.join(skipped)})" if skipped else "")
+        return "contribution chain: FAILED\n" + "\n".join("  " + f for f in self.findings())
+
+
 class G16Error(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"g16hip error {code}: {msg}")
@@ -373,6 +466,11 @@ def load_library():
     lib.g16_points_intt_g2.argtypes = [vp, vp, u32, vp]
     lib.g16_circuit_setup.argtypes = [vp, ctypes.POINTER(R1csDesc), ctypes.POINTER(PtauDesc), vp,
                                       ctypes.POINTER(SetupPoints)]
+    lib.g16_points_scale_g1.argtypes = [vp, vp, sz, vp, u32, vp]
+    lib.g16_points_scale_g2.argtypes = [vp, vp, sz, vp, u32, vp]
+    lib.g16_key_contribute.argtypes = [vp, ctypes.POINTER(Phase2Key), vp, vp, u32, vp, ctypes.POINTER(Phase2Out)]
+    lib.g16_contributions_verify.argtypes = [vp, ctypes.POINTER(Phase2Key), ctypes.POINTER(Phase2Key),
+                                             ctypes.POINTER(ContributionC), vp, sz, vp, vp, ctypes.POINTER(ChainReportC)]
     for name in SYMBOLS:
         if name not in ("g16_ctx_destroy", "g16_last_error", "g16_points_release", "g16_points_count",
                         "g16_points_inf_count",
@@ -670,6 +768,76 @@ class Context:
         self._check(self._lib.g16_circuit_setup(self._h, ctypes.byref(r1cs), ctypes.byref(ptau),
                                                 _buf(bytes(delta)) if delta is not None else None, ctypes.byref(o)))
         return log2, {name: bufs[name].raw[: sizes[name]] for name in SETUP_POINTS}
+
+    def points_scale(self, group: int, points: bytes, k: bytes, mont: bool = True) -> bytes:
+        """g16_points_scale_g1/g2: out[i] = k * points[i] for one 32-byte scalar k (canonical; zero is legal) and affine
+        points of the curve, (0,0) anywhere"""
+        psz = 64 if group == 1 else 128
+        assert len(points) % psz == 0 and len(k) == 32, f"points of {psz} bytes and a 32-byte scalar"
+        out = ctypes.create_string_buffer(max(1, len(points)))
+        fn = self._lib.g16_points_scale_g1 if group == 1 else self._lib.g16_points_scale_g2
+        self._check(fn(self._h, _buf(bytes(points)), len(points) // psz, _buf(bytes(k)),
+                       SCALARS_MONT if mont else SCALARS_STD, out))
+        return out.raw[: len(points)]
+
+    @staticmethod
+    def _phase2_key(key: dict):
+        """{delta1, delta2, pointsC1, pointsH1: bytes} -> (Phase2Key, the buffers it points into)"""
+        assert len(key["delta1"]) == 64 and len(key["delta2"]) == 128, "delta1: 64 bytes, delta2: 128 bytes"
+        assert len(key["pointsC1"]) % 64 == 0 and len(key["pointsH1"]) % 64 == 0, "G1 points of 64 bytes"
+        keep = {name: bytes(key[name]) for name in ("delta1", "delta2", "pointsC1", "pointsH1")}
+        pk = Phase2Key()
+        for name, b in keep.items():
+            setattr(pk, name, ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p).value if b else None)
+        pk.nc1, pk.nh1 = len(keep["pointsC1"]) // 64, len(keep["pointsH1"]) // 64
+        return pk, keep
+
+    def key_contribute(self, key: dict, d: bytes, s: bytes, challenge_g2: bytes, mont: bool = True):
+        """g16_key_contribute.  key: {delta1, delta2, pointsC1, pointsH1: bytes}; d, s: 32-byte secrets, non-zero;
+        challenge_g2: the 128-byte challenge point of this contribution (the caller derives it: phase2.py).
+        -> ({delta1, delta2, pointsC1, pointsH1} of the contributed key, the 320-byte record)"""
+        assert len(d) == 32 and len(s) == 32 and len(challenge_g2) == 128
+        pk, keep = self._phase2_key(key)
+        bufs = {name: ctypes.create_string_buffer(max(1, len(b))) for name, b in keep.items()}
+        rec = ContributionC()
+        o = Phase2Out()
+        for name in bufs:
+            setattr(o, name, ctypes.cast(bufs[name], ctypes.c_void_p).value)
+        o.record = ctypes.pointer(rec)
+        self._check(self._lib.g16_key_contribute(self._h, ctypes.byref(pk), _buf(bytes(d)), _buf(bytes(s)),
+                                                 SCALARS_MONT if mont else SCALARS_STD, _buf(bytes(challenge_g2)),
+                                                 ctypes.byref(o)))
+        return {name: bufs[name].raw[: len(keep[name])] for name in keep}, bytes(rec)
+
+    def contributions_verify(self, initial: dict, final: dict, records, challenges_g2, c1_multipliers,
+                             h1_multipliers) -> ChainReport:
+        """g16_contributions_verify.  initial (the trusted anchor) / final: {delta1, delta2, pointsC1, pointsH1: bytes};
+        records: the 320-byte records in order; challenges_g2: one 128-byte point per record; the multipliers: ints in
+        [1, 2^128) (or their 16-byte encodings, joined), one per point of pointsC1 / pointsH1, drawn by the caller
+        after every input is fixed."""
+        def enc(zs, n, what):
+            if isinstance(zs, (bytes, bytearray)):
+                assert len(zs) == 16 * n, f"one {what} multiplier of 16 bytes each"
+                return bytes(zs)
+            assert len(zs) == n, f"{n} {what} multipliers"
+            return b"".join(int(z).to_bytes(16, "little") for z in zs)
+        records, challenges_g2 = list(records), list(challenges_g2)
+        assert len(records) == len(challenges_g2) and all(len(r) == CONTRIBUTION_BYTES for r in records) and \
+            all(len(c) == 128 for c in challenges_g2), "one 320-byte record and one 128-byte challenge per contribution"
+        ki, keep_i = self._phase2_key(initial)
+        kf, keep_f = self._phase2_key(final)
+        zc, zh = enc(c1_multipliers, kf.nc1, "c1"), enc(h1_multipliers, kf.nh1, "h1")
+        recs = (ContributionC * max(1, len(records))).from_buffer_copy(b"".join(records) or bytes(CONTRIBUTION_BYTES))
+        ch = b"".join(challenges_g2)
+        rep = ChainReportC()
+        self._check(self._lib.g16_contributions_verify(self._h, ctypes.byref(ki), ctypes.byref(kf), recs,
+                                                       _buf(ch) if ch else None, len(records),
+                                                       _buf(zc) if zc else None, _buf(zh) if zh else None,
+                                                       ctypes.byref(rep)))
+        none = ctypes.c_size_t(-1).value
+        opt = lambda row: [None if f == none else f for f in row]     # noqa: E731
+        return ChainReport(rep.failed, list(rep.relation), opt(rep.first_record), [opt(row) for row in rep.first_bad],
+                           [list(row) for row in rep.bad_count], opt(rep.first_infinity))
 
     def quotient(self, Az, Bz, Cz, log2n: int, flavour: int, out=None, device: bool = False):
         if device:

@@ -13,6 +13,17 @@ using namespace g16;
 
 void g16_curve_consts_g2(void* gen2, void* twist_b);   // msm_g2_misc.hip: gen2 (128 B), twistCoeffB (64 B)
 
+// `count` pairing products of four pairs each, one workgroup per product (pairing_product<4>, circuit_audit.cuh); shared
+// with the contribution chain (contribute.hip)
+int32_t g16_pairing_products4(g16_ctx* ctx, const void* d_P, const void* d_Q, uint32_t count, uint32_t neg_mask,
+                              int32_t* d_result) {
+  if (!count) return G16_OK;
+  KLAUNCH(ctx, "pairing_product4", pairing_product<4>, count, 64, 0, (const g1_aff*)d_P, (const g2_aff*)d_Q, neg_mask,
+          d_result);
+  HIPCHK(ctx, hipGetLastError());
+  return G16_OK;
+}
+
 namespace {
 
 constexpr size_t NONE = (size_t)-1;
@@ -311,11 +322,9 @@ int32_t circuit_audit(g16_ctx* ctx, const g16_pkey_desc* d, const g16_vkey_desc*
   // 8. the pairing products, e(-L, delta2 / gamma2) * prod e(R_k, gen2) == 1, as ONE launch of three workgroups: each is
   //    the latency of one lane's Miller loop and final exponentiation, so side by side they cost what one does.  A pair
   //    that is not used, and a product that is not run, keeps (0,0): its lane returns one.
-  if (pair4[0] || pair4[1] || run[G16_REL_H1]) {
-    KLAUNCH(ctx, "pairing_product4", pairing_product<4>, 3, 64, 0, (const g1_aff*)&pb->P4[0][0],
-            (const g2_aff*)&pb->Q4[0][0], 1u, pb->result);
-    HIPCHK(ctx, hipGetLastError());
-  }
+  if ((pair4[0] || pair4[1] || run[G16_REL_H1]) &&
+      (rc = g16_pairing_products4(ctx, &pb->P4[0][0], &pb->Q4[0][0], 3, 1u, pb->result)))
+    return rc;
   PairBuf got;
   HIPCHK(ctx, hipMemcpyAsync(&got, pb, sizeof got, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));

@@ -369,6 +369,11 @@ struct g16_audit_section {
 int32_t g16_audit_sections(g16_ctx* ctx, const g16_audit_section* sec, int nsec, size_t (*first_bad)[3],
                            size_t (*bad_count)[3]);
 
+// d_result[j] = ( prod_{k<4} e(+-d_P[4j+k], d_Q[4j+k]) == 1 ), j < count; bit k of neg_mask negates pair k; a pair with (0,0)
+// on either side contributes one (circuit_audit.hip: the kernel of the circuit audit's point relations)
+int32_t g16_pairing_products4(g16_ctx* ctx, const void* d_P, const void* d_Q, uint32_t count, uint32_t neg_mask,
+                              int32_t* d_result);
+
 // ---- circuit setup (circuit_setup.hip); kernels and launcher bodies in circuit_setup.cuh, instantiated per curve in
 // circuit_setup_g1.hip / circuit_setup_g2.hip.  Device pointers, the context's stream, nothing waits. ----------------------
 namespace g16 {
@@ -393,6 +398,19 @@ int32_t cs_to_affine_device(g16_ctx* ctx, const void* d_acc, size_t count, void*
 template <class C>
 int32_t cs_diff_device(g16_ctx* ctx, const void* d_p, const void* d_q, size_t count, void* d_out_aff);
 }  // namespace g16
+
+// ---- one scalar times an array of points (scale.hip); kernel and launcher body in scale.cuh, instantiated per curve in
+// scale_g1.hip / scale_g2.hip.  Device pointers, the context's stream, nothing waits. --------------------------------------
+namespace g16 {
+struct ScalePlan;   // scale_plan.hpp
+struct ScaleJob;
+// d_out_aff[i] = k * d_pts[i], canonical affine; d_out_aff may be d_pts
+template <class C>
+int32_t scale_uniform_device(g16_ctx* ctx, const void* d_pts, size_t n, const ScaleJob& job, void* d_out_aff);
+}  // namespace g16
+// the job of k (standard form, < r): its plan into `plan` (the host copy the upload reads: it must outlive the stream's
+// work) and into d_steps (ScalePlan::MAX_STEPS words of device memory)
+int32_t g16_scale_job(g16_ctx* ctx, const g16::u256& k_std, g16::ScalePlan& plan, uint32_t* d_steps, g16::ScaleJob& job);
 
 // ---- the two halves of g16_prove_combine (prover.hip), shared with the prover pool (pool.hip) ----------------------
 // What the finish half needs from the enqueue half: the mask in standard form and the mask-only parts of the proof

@@ -2,7 +2,7 @@
 circom / snarkjs ecosystem, plus the JSON export.  Writers (absent from the reference, which only reads) exist
 so that fixtures and benchmark keys can be produced without circom/snarkjs."""
 from .container import parseContainer, writeContainer  # noqa: F401
-from .zkey import auditCircuit, auditZKey, parseZKey, writeZKey  # noqa: F401
+from .zkey import auditCircuit, auditZKey, parseContributions, parseZKey, writeZKey  # noqa: F401
 from .ptau import Ptau, parsePtau, writePtau  # noqa: F401
 from .witness import parseWitness, writeWitness  # noqa: F401
 from .r1cs import parseR1CS, writeR1CS  # noqa: F401

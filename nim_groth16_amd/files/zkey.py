@@ -175,18 +175,81 @@ def parseZKey(fname: str, check: bool = False, ctx=None, rawCoeffs: bool = False
     return zk
 
 
-def writeZKey(fname: str, zk: ZKey) -> None:
-    """Inverse of parseZKey (sections 1-9 of zkey.nim:6-91; section 10, the ceremony contributions, is not
-    needed for proving and is omitted)."""
+def zkeySections(zk: ZKey):
+    """sections 1-9 of the .zkey of a key, [(id, data)] in file order (zkey.nim:6-91)"""
     h, sp, pp = zk.header, zk.specPoints, zk.pPoints
     le32 = lambda x: int(x).to_bytes(32, "little")                       # noqa: E731
     s2 = (struct.pack("<I", 32) + le32(F.primeP) + struct.pack("<I", 32) + le32(F.primeR) +
           struct.pack("<III", h.nvars, h.npubs, h.domainSize) +
           sp.alpha1 + sp.beta1 + sp.beta2 + sp.gamma2 + sp.delta1 + sp.delta2)
-    s4 = bytearray(struct.pack("<I", len(zk.coeffs)))
-    for (m, r, c, v) in zk.coeffs:
-        x = int.from_bytes(v, "little") * F.frMontR % _R                 # c*R -> c*R^2
-        s4 += struct.pack("<III", m, r, c) + x.to_bytes(32, "little")
-    writeContainer("zkey", 1, fname, [(1, struct.pack("<I", 1)), (2, s2), (3, zk.pointsIC), (4, bytes(s4)),
-                                      (5, pp.pointsA1), (6, pp.pointsB1), (7, pp.pointsB2), (8, pp.pointsC1),
-                                      (9, pp.pointsH1)])
+    if zk.coeffsSection4 is not None and not zk.coeffs:
+        s4 = bytes(zk.coeffsSection4)
+    else:
+        s4 = bytearray(struct.pack("<I", len(zk.coeffs)))
+        for (m, r, c, v) in zk.coeffs:
+            x = int.from_bytes(v, "little") * F.frMontR % _R             # c*R -> c*R^2
+            s4 += struct.pack("<III", m, r, c) + x.to_bytes(32, "little")
+    return [(1, struct.pack("<I", 1)), (2, s2), (3, zk.pointsIC), (4, bytes(s4)), (5, pp.pointsA1), (6, pp.pointsB1),
+            (7, pp.pointsB2), (8, pp.pointsC1), (9, pp.pointsH1)]
+
+
+def contributionsSection(log) -> bytes:
+    """Section 10 of a .zkey from a phase2.Contributions: csHash (64 B) | u32 count | per record deltaAfter | g1_s | g1_sx
+    (64 B each) | g2_spx (128 B) | transcript (64 B) | u32 type = 0 | u32 params length | params (the name, UTF-8).
+    The maintainers' reading of snarkjs's layout, UNPINNED: no snarkjs-written file was at hand to hold it to; and the
+    hashes in it follow this project's own rule (phase2.py), not snarkjs's."""
+    assert len(log.cs_hash) == 64 and len(log.records) == len(log.transcripts) == len(log.names)
+    out = bytearray(log.cs_hash) + struct.pack("<I", len(log.records))
+    for rec, tr, name in zip(log.records, log.transcripts, log.names):
+        assert len(rec) == 320 and len(tr) == 64
+        params = name.encode("utf-8")
+        out += rec + tr + struct.pack("<II", 0, len(params)) + params
+    return bytes(out)
+
+
+def parseContributions(fname: str):
+    """Section 10 of a .zkey written by writeZKey -> phase2.Contributions; None when the file has no section 10.  Raises
+    ValueError on a section that is not laid out as contributionsSection writes it (parseZKey itself never reads the
+    section: a prover has no use for it)."""
+    from ..phase2 import Contributions
+    sec = parseContainer("zkey", 1, fname)
+    if 10 not in sec:
+        return None
+    s = bytes(sec[10][0])
+    if len(s) < 68:
+        raise ValueError("section 10: shorter than csHash and the record count")
+    (count,) = struct.unpack_from("<I", s, 64)
+    log, pos = Contributions(cs_hash=s[:64]), 68
+    for j in range(count):
+        if pos + 320 + 64 + 8 > len(s):
+            raise ValueError(f"section 10: record {j} is truncated")
+        rec, tr = s[pos:pos + 320], s[pos + 320:pos + 384]
+        typ, plen = struct.unpack_from("<II", s, pos + 384)
+        pos += 392
+        if typ != 0:
+            raise ValueError(f"section 10: record {j} has contribution type {typ} (only 0 is written here)")
+        if pos + plen > len(s):
+            raise ValueError(f"section 10: the params of record {j} are truncated")
+        try:
+            name = s[pos:pos + plen].decode("utf-8")
+        except UnicodeDecodeError:
+            raise ValueError(f"section 10: the name of record {j} is not UTF-8") from None
+        pos += plen
+        log.records.append(rec)
+        log.transcripts.append(tr)
+        log.names.append(name)
+    if pos != len(s):
+        raise ValueError("section 10: bytes left over after the last record")
+    return log
+
+
+def writeZKey(fname: str, zk: ZKey) -> None:
+    """Inverse of parseZKey (sections 1-9 of zkey.nim:6-91).  Section 10, the ceremony contributions, is not needed for
+    proving; it is written when the key carries a contribution log (zk.contributions, contributionsSection).
+    A key parsed with rawCoeffs (coeffsSection4 set, `coeffs` empty) is written with that section as it lay in its file;
+    before the contribution log existed such a key was written with an EMPTY coefficient section, which made a file
+    nothing could prove from, and its cs_hash would have differed from the same key parsed entry by entry."""
+    sections = zkeySections(zk)
+    if getattr(zk, "contributions", None) is not None:
+        sections.append((10, contributionsSection(zk.contributions)))
+    writeContainer("zkey", 1, fname, sections)

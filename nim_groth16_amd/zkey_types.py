@@ -50,6 +50,9 @@ class ZKey:                          # zkey_types.nim:54-59
     # double-Montgomery form of io.nim:134-139): parseZKey(rawCoeffs=True) keeps it, loadProvingKey hands it to
     # g16_pkey_create_zkey unparsed, and `coeffs` stays empty
     coeffsSection4: bytes = None
+    # the contribution log of a phase-2 ceremony (phase2.Contributions: records, transcript hashes, names, cs_hash), or
+    # None for a key without one; files.zkey.writeZKey writes it as section 10
+    contributions: object = None
 
 
 class _Coeff(ctypes.Structure):      # g16_coeff (include/g16hip.h)

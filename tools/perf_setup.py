@@ -17,7 +17,14 @@ per-kernel times; beside it fakeCircuitSetup (g16_fake_setup) for the same (alph
 only available yardstick -- it does one fixed-base multiplication where the real setup does a transform -- and the two
 keys compared byte for byte.
 
-  python tools/perf_setup.py --circuit-setup [--log2n 20] [--repeats 2] [--out profiles/circuit_setup_2p20.txt]"""
+  python tools/perf_setup.py --circuit-setup [--log2n 20] [--repeats 2] [--out profiles/circuit_setup_2p20.txt]
+
+--contribute: the phase-2 contribution instead -- the whole g16_key_contribute and g16_contributions_verify (a chain of 3
+records) on the part of a key a contribution touches at 2^log2n: pointsC1 and pointsH1 of 2^log2n points each (random
+multiples of gen1; no circuit is needed: the two calls read nothing else of a key), wall time of the Python call and the
+library's per-kernel times.  The chain is checked to verify, and to fail once a point of the final key is moved.
+
+  python tools/perf_setup.py --contribute [--log2n 20] [--repeats 3] [--out FILE]"""
 import argparse
 import gc
 import os
@@ -121,15 +128,93 @@ def circuit_setup_main(args):
         f.write("\n".join(lines) + "\n")
 
 
+def contribute_main(args):
+    import numpy as np
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+
+    from nim_groth16_amd._lib import device_code_sha16
+    ctx = Context(0)
+    ctx.selftest()
+    n = 1 << args.log2n
+    rs = np.random.default_rng(20)
+
+    def scalars(count):                                   # standard form, below 2^253, never zero
+        a = rs.integers(0, 1 << 63, size=(count, 4), dtype=np.uint64)
+        a[:, 3] &= np.uint64((1 << 61) - 1)
+        a[:, 0] |= np.uint64(1)
+        return a.tobytes()
+
+    def multipliers(count):
+        a = rs.integers(0, 1 << 63, size=(count, 2), dtype=np.uint64)
+        a[:, 0] |= np.uint64(1)
+        return a.tobytes()
+
+    say(f"phase-2 contribution at 2^{args.log2n}: pointsC1 and pointsH1 of {n} points each, {args.repeats} repeats "
+        f"({time.strftime('%Y-%m-%d')}; library kernels {device_code_sha16()})")
+    delta = scalars(1)                                    # delta1 and delta2: the same multiple of the two generators
+    key0 = {"delta1": ctx.fixed_base(1, delta, mont=False), "delta2": ctx.fixed_base(2, delta, mont=False),
+            "pointsC1": ctx.fixed_base(1, scalars(n), mont=False), "pointsH1": ctx.fixed_base(1, scalars(n), mont=False)}
+    chal = [ctx.fixed_base(2, scalars(1), mont=False) for _ in range(3)]
+    zc, zh = multipliers(n), multipliers(n)
+
+    def timed(what, fn):
+        ctx.profile(True)
+        ctx.profile_reset()
+        t0 = time.perf_counter()
+        out = fn()
+        dt = time.perf_counter() - t0
+        rep = ctx.profile_report()
+        ctx.profile(False)
+        kern = "  ".join(f"{k} {v['total_ms']:.2f} ({v['calls']})" for k, v in sorted(rep.items()))
+        say(f"  {what}: {dt * 1e3:8.1f} ms wall   kernels, ms (launches): {kern}")
+        return out, dt
+
+    ctx.key_contribute(key0, scalars(1), scalars(1), chal[0], mont=False)          # warm-up: allocations, code objects
+    walls = {"contribute": [], "verify": []}
+    for rep in range(args.repeats):
+        key, recs = key0, []
+        for j in range(3):
+            d, s = scalars(1), scalars(1)
+            (key, rec), dt = timed(f"g16_key_contribute #{rep}.{j}", lambda: ctx.key_contribute(key, d, s, chal[j], mont=False))
+            recs.append(rec)
+            walls["contribute"].append(dt)
+        report, dt = timed(f"g16_contributions_verify #{rep} (3 records)",
+                           lambda: ctx.contributions_verify(key0, key, recs, chal, zc, zh))
+        walls["verify"].append(dt)
+        if not report.ok:
+            raise SystemExit(f"an honest chain does not verify: {report}")
+    moved = dict(key)
+    moved["pointsH1"] = key["pointsH1"][64:128] + key["pointsH1"][:64] + key["pointsH1"][128:]
+    report = ctx.contributions_verify(key0, moved, recs, chal, zc, zh)
+    if report.relation != [1, 1, 1, 1, 1, 1, 0]:
+        raise SystemExit(f"two swapped points of pointsH1 are not found: {report}")
+    for k, v in walls.items():
+        v.sort()
+        say(f"  median {k}: {v[len(v) // 2] * 1e3:.1f} ms wall (min {v[0] * 1e3:.1f}, max {v[-1] * 1e3:.1f}, {len(v)} calls)")
+    say("  every chain verified; two swapped points of the final pointsH1 give H1 = 0 and nothing else")
+    ctx.close()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--circuit-setup", action="store_true", help="measure g16_circuit_setup (see the module text)")
+    ap.add_argument("--contribute", action="store_true",
+                    help="measure g16_key_contribute and g16_contributions_verify (see the module text)")
     ap.add_argument("--log2n", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fake_setup_ab.txt"))
     args = ap.parse_args()
     if args.circuit_setup:
         return circuit_setup_main(args)
+    if args.contribute:
+        return contribute_main(args)
     lines = []
 
     def say(s=""):

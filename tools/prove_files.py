@@ -20,6 +20,13 @@ snarkjs, ptau or network).  Given external files the checked recipe is
       --setup-ptau PTAU -r R1CS  first make the key: the circuit setup of `snarkjs zkey new` on the GPU (circuitSetup:
           gamma = delta = 1, sound only after a phase-2 contribution) written to the --zkey path; without --wtns the
           run ends there, with it the proof is made from the new key
+      --contribute [--contribute-name N] [--contribute-out OUT]  one phase-2 contribution to the --zkey key (setup.contribute:
+          fresh secrets from `secrets`, forgotten when the process ends; the transcript rule is this project's own, not
+          snarkjs's: nim_groth16_amd/phase2.py), written with its log (section 10) to OUT, by default back to the --zkey
+          path; without --wtns the run ends there, with it the proof is made from the contributed key
+      --verify-contributions INITIAL.zkey  before the key is loaded: do the records of its section 10 lead from the
+          initial key (the caller's anchor: made with --setup-ptau or tied to its circuit with --audit-circuit) to this
+          key?  The report is printed; a chain that fails gives exit code 2 and no proof, like --audit-circuit
     snarkjs groth16 verify verification_key.json public.json proof.json        # offline, wherever snarkjs exists
 (the reference's own recipe: groth16/example/prove.sh:52-59)."""
 import argparse
@@ -57,6 +64,14 @@ def main():
     ap.add_argument("--audit-circuit", nargs=2, metavar=("R1CS", "PTAU"), default=None,
                     help="audit the key against its circuit and powers of tau before loading it; no proof from a key "
                          "that does not belong to them")
+    ap.add_argument("--contribute", action="store_true",
+                    help="make one phase-2 contribution to the key and write it (see --contribute-out)")
+    ap.add_argument("--contribute-name", default="", help="the name recorded with the contribution")
+    ap.add_argument("--contribute-out", metavar="OUT", default=None,
+                    help="where --contribute writes the contributed key (default: back to the --zkey path)")
+    ap.add_argument("--verify-contributions", metavar="INITIAL", default=None,
+                    help="check the key's contribution chain against this initial key before loading it; no proof from "
+                         "a key whose chain fails")
     ap.add_argument("-y", "--verify", action="store_true",
                     help="also verify the proof against the zkey's verification key (cli_main.nim -y)")
     args = ap.parse_args()
@@ -74,6 +89,34 @@ def main():
             return
     elif args.r1cs:
         ap.error("-r R1CS goes together with --setup-ptau")
+    if args.contribute:
+        from nim_groth16_amd.files import parseContributions, writeZKey
+        from nim_groth16_amd.setup import contribute
+        zk = parseZKey(args.zkey, ctx=ctx, rawCoeffs=True)
+        zk.contributions = parseContributions(args.zkey)
+        out = args.contribute_out or args.zkey
+        done = contribute(zk, name=args.contribute_name, ctx=ctx)
+        writeZKey(out, done)
+        print(f"contribution {len(done.contributions.records)}" +
+              (f" ({args.contribute_name})" if args.contribute_name else "") + f": wrote {out}")
+        args.zkey = out
+        if not args.wtns and not args.verify_contributions:
+            return
+    if args.verify_contributions:
+        from nim_groth16_amd.files import parseContributions
+        from nim_groth16_amd.setup import verifyContributions
+        zk = parseZKey(args.zkey, ctx=ctx, rawCoeffs=True)
+        zk.contributions = parseContributions(args.zkey)
+        try:
+            report = verifyContributions(parseZKey(args.verify_contributions, ctx=ctx, rawCoeffs=True), zk, ctx=ctx)
+        except ValueError as e:                  # a part of the key that no contribution touches differs
+            print(f"contribution chain: FAILED\n  {e}")
+            raise SystemExit(2)
+        print(report)
+        if not report.ok:
+            raise SystemExit(2)
+        if not args.wtns:
+            return
     if not args.wtns:
         ap.error("the following arguments are required: -w/--wtns")
     t0 = time.time()
