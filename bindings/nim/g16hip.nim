@@ -538,3 +538,69 @@ proc g16_key_contribute(ctx: ptr G16Ctx, key: ptr G16Phase2Key, d, s: pointer, f
 proc g16_contributions_verify(ctx: ptr G16Ctx, initial, final: ptr G16Phase2Key, records: ptr G16Contribution,
                               challenges_g2: pointer, count: csize_t, c1_multipliers, h1_multipliers: pointer,
                               res: ptr G16ChainReport): int32 {.importc, header: "g16hip.h".}
+
+# --- a scalar per point, and the phase-1 contribution (include/g16hip.h "scaling an array of points", "phase-1
+# contribution") ---------------------------------------------------------------------------------------------------------
+# g16_ptau_contribute takes the powers of (tau, alpha, beta) to those of (t tau, a alpha, b beta).  As in phase 2 the library
+# hashes and draws nothing; the transcript rule of nim_groth16_amd/phase1.py is the project's own, not snarkjs's.
+# g16_ptau_verify checks a .ptau and a chain of such records under caller-drawn 128-bit multipliers.
+type
+  G16PtauOut* {.importc: "g16_ptau_out", header: "g16hip.h", bycopy.} = object
+    tauG1*, tauG2*, alphaTauG1*, betaTauG1*, betaG2*: pointer
+  G16PtauPok* {.importc: "g16_ptau_pok", header: "g16hip.h", bycopy.} = object
+    g1_s*, g1_sx*: array[64, uint8]
+    g2_spx*: array[128, uint8]
+  G16PtauContribution* {.importc: "g16_ptau_contribution", header: "g16hip.h", bycopy.} = object
+    tauG1*, alphaG1*, betaG1*: array[64, uint8]
+    tauG2*, betaG2*: array[128, uint8]
+    pok*: array[3, G16PtauPok]
+proc g16_points_scale_each_g1(ctx: ptr G16Ctx, points: pointer, n: csize_t, scalars: pointer, flags: uint32,
+                              res: pointer): int32 {.importc, header: "g16hip.h".}
+proc g16_points_scale_each_g2(ctx: ptr G16Ctx, points: pointer, n: csize_t, scalars: pointer, flags: uint32,
+                              res: pointer): int32 {.importc, header: "g16hip.h".}
+proc g16_ptau_contribute(ctx: ptr G16Ctx, ptau: ptr G16PtauDesc, t, a, b, s3: pointer, flags: uint32,
+                         challenges_g2: pointer, res: ptr G16PtauOut, record: ptr G16PtauContribution): int32 {.
+                         importc, header: "g16hip.h".}
+
+proc scaleEach*(points: seq[G1], scalars: seq[Fr]): seq[G1] =
+  ## res[i] = scalars[i] * points[i]; the points on the curve, (0,0) anywhere
+  assert points.len == scalars.len
+  result = newSeq[G1](points.len)
+  if points.len > 0:
+    check g16_points_scale_each_g1(gctx, unsafeAddr points[0], csize_t(points.len), unsafeAddr scalars[0],
+                                   G16_SCALARS_MONT, addr result[0])
+
+proc scaleEach*(points: seq[G2], scalars: seq[Fr]): seq[G2] =
+  assert points.len == scalars.len
+  result = newSeq[G2](points.len)
+  if points.len > 0:
+    check g16_points_scale_each_g2(gctx, unsafeAddr points[0], csize_t(points.len), unsafeAddr scalars[0],
+                                   G16_SCALARS_MONT, addr result[0])
+
+proc ptauContribute*(ptau: G16PtauDesc, t, a, b: Fr, pokSecrets: array[3, Fr], challenges: array[3, G2],
+                     res: G16PtauOut): G16PtauContribution =
+  ## one phase-1 contribution into the caller's buffers `res` (sized as the arrays of `ptau`); the six scalars are
+  ## non-zero, the three challenge points the caller's (for t, a, b in this order).  Returns the record.
+  var o = res
+  check g16_ptau_contribute(gctx, unsafeAddr ptau, unsafeAddr t, unsafeAddr a, unsafeAddr b, unsafeAddr pokSecrets[0],
+                            G16_SCALARS_MONT, unsafeAddr challenges[0], addr o, addr result)
+
+type
+  G16PtauReport* {.importc: "g16_ptau_report", header: "g16hip.h", bycopy.} = object
+    failed*: uint32
+    relation*: array[10, int32]
+    first_record*: array[2, csize_t]
+    first_bad*, bad_count*: array[14, array[3, csize_t]]
+    first_infinity*: array[14, csize_t]
+proc g16_ptau_verify(ctx: ptr G16Ctx, ptau: ptr G16PtauDesc, records: ptr G16PtauContribution, challenges_g2: pointer,
+                     count: csize_t, multipliers: pointer, res: ptr G16PtauReport): int32 {.importc, header: "g16hip.h".}
+
+proc ptauVerify*(ptau: G16PtauDesc, records: seq[G16PtauContribution], challenges: seq[G2], multipliers: seq[array[16, uint8]],
+                 checkChain = true): G16PtauReport =
+  ## is `ptau` the powers of some tau, alpha, beta, and (checkChain) do the records lead to it from the generators?
+  ## challenges: three per record; multipliers: 2^(power+1) - 2 non-zero 128-bit values drawn by the caller
+  assert challenges.len == 3 * records.len and multipliers.len == (2 shl ptau.power.int) - 2
+  var one: G16PtauContribution
+  let recs = if not checkChain: nil elif records.len > 0: unsafeAddr records[0] else: addr one
+  check g16_ptau_verify(gctx, unsafeAddr ptau, recs, (if records.len > 0: unsafeAddr challenges[0] else: nil),
+                        csize_t(if checkChain: records.len else: 0), unsafeAddr multipliers[0], addr result)

@@ -668,7 +668,7 @@ typedef struct {
  * canonical; ptau->power < log2_domain + 1 (the rule of `snarkjs zkey new`: tau^(2n-1) is needed and tauG1 holds
  * 2^(power+1) - 1 powers); a sharded key description; everything g16_key_audit rejects.
  * What the call does NOT cover:
- *   - the ptau is the trusted anchor: its self-consistency (`snarkjs powersoftau verify`) is out of scope;
+ *   - the ptau is the trusted anchor here: its self-consistency (`snarkjs powersoftau verify`) is g16_ptau_verify's, below;
  *   - the phase-2 contribution chain (section 10 of a .zkey) is not walked here: g16_contributions_verify, below, checks
  *     its records against an initial key that this call has tied to the circuit; the hashes stay with the caller;
  *   - gamma and delta are taken from the key: a legitimately contributed key (delta changed, pointsC1 and pointsH1
@@ -677,7 +677,7 @@ int32_t g16_circuit_audit(g16_ctx* ctx, const g16_pkey_desc* desc, const g16_vke
                           size_t section4_bytes, const g16_r1cs_desc* r1cs, const g16_ptau_desc* ptau,
                           const void* wire_multipliers, const void* h_multipliers, g16_circuit_report* out);
 
-/* ---- scaling an array of points by ONE scalar ------------------------------------------------------------------------
+/* ---- scaling an array of points: by ONE scalar, or by a scalar per point ------------------------------------------------
  * out[i] = k * points[i]; host pointers, affine Montgomery in and out, (0,0) legal anywhere; k: 32 bytes, canonical,
  * flags = G16_SCALARS_MONT or G16_SCALARS_STD; k == 0 is legal (all infinity); n < 2^31.  out may be points.
  * The points must be on the curve (g16_points_audit_*): the G1 path multiplies through the endomorphism
@@ -687,6 +687,20 @@ int32_t g16_circuit_audit(g16_ctx* ctx, const g16_pkey_desc* desc, const g16_vke
  * a lane for the affine output.  Outputs are canonical affine bytes.  The call changes no context state. */
 int32_t g16_points_scale_g1(g16_ctx* ctx, const void* points, size_t n, const void* k, uint32_t flags, void* out);
 int32_t g16_points_scale_g2(g16_ctx* ctx, const void* points, size_t n, const void* k, uint32_t flags, void* out);
+/* A scalar PER POINT: out[i] = scalars[i] * points[i] (what a powers-of-tau contribution does to tauG1: point i times
+ * t^i).  scalars: n x 32 bytes, every one canonical, all in the form `flags` names (G16_SCALARS_MONT or G16_SCALARS_STD);
+ * a zero scalar is legal (that output is (0,0)); n < 2^31; out may be points.  Points, outputs and context state: as for
+ * g16_points_scale_g1/g2 above (on the curve, (0,0) legal anywhere, canonical affine bytes out, no state changed).
+ * G1: every lane splits its own scalar as k = k1 + k2 lambda on the device, halves below 2^128, and walks the columns of
+ * (k1, k2) from its own top bit down: one doubling per column and one mixed addition of +-P, +-phi P or +-(P +- phi P)
+ * where the column is not empty -- at most 128 doublings and 128 additions against the 254 and 254 of the plain ladder;
+ * G2: the plain ladder over the lane's scalar.  One field inversion per four points, as above.
+ * G16_EINVAL, checked on the host before anything is queued: a null pointer, flags other than the two, n >= 2^31, a
+ * scalar >= r (g16_last_error names its index: "scalar 17 is not canonical (>= r)"). */
+int32_t g16_points_scale_each_g1(g16_ctx* ctx, const void* points, size_t n, const void* scalars, uint32_t flags,
+                                 void* out);
+int32_t g16_points_scale_each_g2(g16_ctx* ctx, const void* points, size_t n, const void* scalars, uint32_t flags,
+                                 void* out);
 
 /* ---- phase-2 contribution: what makes the key of g16_circuit_setup(delta = NULL) sound ------------------------------
  * `snarkjs zkey contribute` and the walk of `snarkjs zkey verify` over the contribution chain, as arithmetic: the library
@@ -765,6 +779,101 @@ typedef struct {
 int32_t g16_contributions_verify(g16_ctx* ctx, const g16_phase2_key* initial, const g16_phase2_key* final_,
                                  const g16_contribution* records, const void* challenges_g2, size_t count,
                                  const void* c1_multipliers, const void* h1_multipliers, g16_chain_report* out);
+
+/* ---- phase-1 contribution: powers of tau nobody knows ------------------------------------------------------------------
+ * `snarkjs powersoftau contribute` as arithmetic: from the powers of (tau, alpha, beta) to those of (t tau, a alpha,
+ * b beta), starting from a file of generators (tau = alpha = beta = 1).  As in phase 2 the library hashes nothing and
+ * draws nothing: t, a, b, the three proof-of-knowledge secrets and the three challenge points are the CALLER's (Python:
+ * nim_groth16_amd/phase1.py derives the challenges from a BLAKE2b transcript -- the project's own rule, NOT snarkjs's).
+ * Host pointers, affine Montgomery points throughout.  g16_ptau_verify, below, checks a .ptau and a chain of these records
+ * (`snarkjs powersoftau verify`): the check that g16_circuit_audit and g16_circuit_setup presuppose of their ptau. */
+typedef struct {                      /* host buffers the caller owns, sized as the input's arrays; may not overlap them */
+  void *tauG1, *tauG2, *alphaTauG1, *betaTauG1, *betaG2;
+} g16_ptau_out;
+typedef struct {                      /* a proof of knowledge of x: 256 bytes */
+  uint8_t g1_s[64], g1_sx[64], g2_spx[128];     /* s gen1, x s gen1, x * challenge */
+} g16_ptau_pok;
+typedef struct {                      /* one phase-1 record: 1216 bytes */
+  uint8_t tauG1[64], alphaG1[64], betaG1[64];   /* after this contribution: tauG1[1], alphaTauG1[0], betaTauG1[0] */
+  uint8_t tauG2[128], betaG2[128];              /* tauG2[1], betaG2 */
+  g16_ptau_pok pok[3];                          /* x = t, a, b in this order */
+} g16_ptau_contribution;
+/* tauG1[i] *= t^i (i < 2^(power+1) - 1), tauG2[i] *= t^i, alphaTauG1[i] *= a t^i, betaTauG1[i] *= b t^i (i < 2^power),
+ * betaG2 *= b.  The scalars c t^i are made in HBM by the geometric-sequence kernel of the setup and never visit the host;
+ * every point meets its own scalar in the kernel of g16_points_scale_each_g1/g2.
+ * t, a, b: 32 bytes each; s3: the three proof-of-knowledge secrets for t, a, b (3 x 32 B); all canonical and non-zero, in
+ * the form `flags` names (G16_SCALARS_MONT or G16_SCALARS_STD).  challenges_g2: three G2 points (3 x 128 B), for t, a, b.
+ * Before any arithmetic all five arrays and the three challenges go through the element passes of g16_points_audit_*:
+ * canonical and on the curve, the G2 ones also in the order-r subgroup.  An element that fails is G16_EINVAL and
+ * g16_last_error names array, index and check in the audit's words ("ptau tauG2[3] is not in the order-r subgroup",
+ * "challenges[1] is not on the curve"); so is a (0,0) element anywhere ("ptau alphaTauG1[7] is the point at infinity").
+ * G16_EINVAL also: a null pointer; flags other than the two; a scalar zero or >= r; power == 0 or power > 25.
+ * No output is promised after a failure.  The call changes no context state (a context proves the same bytes before and
+ * after) and runs on the context's stream with one wait after the element passes and one at the end.
+ * HBM: the element passes stage one whole array at a time in the context's staging buffer, which grows to the longest
+ * (tauG1: 2^(power+1) x 64 bytes, 4 GiB at power 25) and stays with the context; the arithmetic then takes the long arrays
+ * through the device in chunks of at most 2^22 points, one chunk at a time: 2^22 x (128 + 32) bytes = 640 MiB at the peak
+ * (a G2 chunk and its scalars), whatever the power. */
+int32_t g16_ptau_contribute(g16_ctx* ctx, const g16_ptau_desc* ptau, const void* t, const void* a, const void* b,
+                            const void* s3, uint32_t flags, const void* challenges_g2, g16_ptau_out* out,
+                            g16_ptau_contribution* record);
+
+/* The check of a .ptau (`snarkjs powersoftau verify` as arithmetic): is this the powers of SOME tau, alpha, beta, and, when
+ * records are given, did this chain of contributions lead to it from the generators?  records: `count` records in order,
+ * or NULL (no chain to check); challenges_g2: 3 challenge points per record (t, a, b), re-derived by the caller.  The
+ * arrays of a report, in order: the file's five (G16_PTAU_*), then per record the five after-values and, three per record,
+ * g1_s, g1_sx, g2_spx and the challenges: */
+#define G16_PTAU_REPORT_ARRAYS 14
+enum {
+  G16_PTAUV_REC_TAU_G1 = 5, G16_PTAUV_REC_ALPHA_G1, G16_PTAUV_REC_BETA_G1, G16_PTAUV_REC_TAU_G2, G16_PTAUV_REC_BETA_G2, /* count */
+  G16_PTAUV_G1_S, G16_PTAUV_G1_SX, G16_PTAUV_G2_SPX, G16_PTAUV_CHALLENGES                                          /* 3 count */
+};
+#define G16_PTAU_RELATIONS 10
+enum {
+  G16_PTAUV_ELEMENTS = 0, G16_PTAUV_FIRST, G16_PTAUV_TAU_G1, G16_PTAUV_TAU_G2, G16_PTAUV_ALPHA, G16_PTAUV_BETA,
+  G16_PTAUV_BETA_G2, G16_PTAUV_POK, G16_PTAUV_STEP, G16_PTAUV_LAST
+};
+typedef struct {
+  uint32_t failed;                                /* bit k set: relation k is 0; 0 = nothing fails */
+  int32_t relation[G16_PTAU_RELATIONS];           /* 1 = holds, 0 = fails, -1 = not run */
+  size_t first_record[2];                         /* the first record whose POK / STEP fails, (size_t)-1: none */
+  size_t first_bad[G16_PTAU_REPORT_ARRAYS][3];    /* per array and check, as g16_points_audit_* */
+  size_t bad_count[G16_PTAU_REPORT_ARRAYS][3];
+  size_t first_infinity[G16_PTAU_REPORT_ARRAYS];  /* first (0,0) element, (size_t)-1: none */
+} g16_ptau_report;
+/* Write m = 2^(power+1) - 2, n = 2^power, z_i the multipliers.
+ *   ELEMENTS  every element of the fourteen arrays is canonical and on its curve, the G2 ones in the order-r subgroup, none (0,0)
+ *   FIRST     tauG1[0] == gen1, tauG2[0] == gen2, byte for byte
+ *   TAU_G1    e(sum_{i<m} z_i tauG1[i], tauG2[1]) == e(sum_{i<m} z_i tauG1[i+1], gen2)
+ *   TAU_G2    e(tauG1[1], sum_{i<n-1} z_i tauG2[i]) == e(gen1, sum_{i<n-1} z_i tauG2[i+1])
+ *   ALPHA, BETA  the form of TAU_G1 over alphaTauG1 / betaTauG1, i < n - 1
+ *   BETA_G2   e(betaTauG1[0], gen2) == e(gen1, betaG2)
+ *   POK       per record and x in (t, a, b): e(g1_s, g2_spx) == e(g1_sx, challenge)
+ *   STEP      per record: e(before, g2_spx_x) == e(after, challenge_x) for tauG1 (x = t), alphaG1 (a), betaG1 (b);
+ *             e(g1_sx_x, before) == e(g1_s_x, after) for tauG2 (x = t) and betaG2 (b); record 0 steps from the generators
+ *   LAST      the last record's five values are the file's tauG1[1], alphaTauG1[0], betaTauG1[0], tauG2[1], betaG2 byte for
+ *             byte; count == 0: the file's five are generators
+ * POK, STEP, LAST are -1 when records == NULL.  A relation is -1 when an array it reads failed ELEMENTS (FIRST, TAU_G1,
+ * TAU_G2: tauG1, tauG2; ALPHA / BETA: the array and tauG2; BETA_G2: betaTauG1, betaG2; POK: g1_s, g1_sx, g2_spx, challenges;
+ * STEP: those and the five record arrays; LAST: the five record arrays and the file's five).  Each sum is the one-shot MSM,
+ * twice per relation over the same widened multipliers with the point pointer at offsets 0 and 1; the multipliers of the
+ * three shorter arrays are the prefix of the one array; every pairing equation goes into ONE launch of the circuit audit's
+ * four-pair product.  No new arithmetic.
+ * multipliers: m x 16 bytes under the rules of g16_verify_batch: little-endian 128-bit integers, every one non-zero, drawn by
+ * the CALLER from a CSPRNG after every input is fixed.  A zero one is G16_EINVAL and g16_last_error names its index.
+ * Soundness: write tauG1[i] = a_i gen1 and tauG2[1] = T gen2.  TAU_G1 says sum z_i (T a_i - a_(i+1)) = 0: if any step
+ * a_(i+1) != T a_i, a non-zero linear form in the z_i over Fr (r > 2^128), which vanishes with probability at most
+ * 1/(2^128 - 1) over multipliers uniform in the non-zero 128-bit values and independent of the inputs; with FIRST (a_0 = 1)
+ * tauG1[i] = T^i gen1.  TAU_G2 likewise forces tauG2[i+1] = a_1 tauG2[i] with a_1 the logarithm of tauG1[1]; its i = 0 term
+ * with FIRST gives tauG2[1] = a_1 gen2, i.e. T = a_1: the two relations tie tauG1[1] and tauG2[1] to each other, so ONE tau
+ * runs through both arrays.  ALPHA and BETA force alphaTauG1[i] = T^i alphaTauG1[0] and the same for beta; BETA_G2, POK,
+ * STEP, LAST, FIRST are exact.  Bound 1/(2^128 - 1) per relation.
+ * G16_EINVAL also: a null pointer (records may be NULL; then count must be 0); power == 0 or > 25 (the limit of
+ * g16_ptau_contribute: what one writes the other can check); count >= 2^16.
+ * The call changes no context state; one wait after the element passes and one at the end.  HBM: the context's staging
+ * buffers grow to tauG1 (2^(power+1) x 64 B) and the widened multipliers (2^(power+1) x 32 B). */
+int32_t g16_ptau_verify(g16_ctx* ctx, const g16_ptau_desc* ptau, const g16_ptau_contribution* records,
+                        const void* challenges_g2, size_t count, const void* multipliers, g16_ptau_report* out);
 
 /* ---- profiling ---------------------------------------------------------------------------------- */
 /* on = 1: every kernel launch is bracketed by HIP events on the stream it is launched on; on = 2: only the

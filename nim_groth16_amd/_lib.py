@@ -35,7 +35,8 @@ SYMBOLS = [
     "g16_points_audit_g1", "g16_points_audit_g2", "g16_points_pairs_check", "g16_key_audit",
     "g16_pkey_b1_fold", "g16_pkey_b1_sparse", "g16_circuit_audit",
     "g16_points_intt_g1", "g16_points_intt_g2", "g16_circuit_setup",
-    "g16_points_scale_g1", "g16_points_scale_g2", "g16_key_contribute", "g16_contributions_verify",
+    "g16_points_scale_g1", "g16_points_scale_g2", "g16_points_scale_each_g1", "g16_points_scale_each_g2",
+    "g16_key_contribute", "g16_contributions_verify", "g16_ptau_contribute", "g16_ptau_verify",
 ]
 VERIFY_SUBGROUP = 16
 GT_BYTES = 384
@@ -232,6 +233,78 @@ class Phase2Out(ctypes.Structure):
     """g16_phase2_out (include/g16hip.h)"""
     _fields_ = [("delta1", ctypes.c_void_p), ("delta2", ctypes.c_void_p), ("pointsC1", ctypes.c_void_p),
                 ("pointsH1", ctypes.c_void_p), ("record", ctypes.POINTER(ContributionC))]
+
+
+class PtauOut(ctypes.Structure):
+    """g16_ptau_out (include/g16hip.h)"""
+    _fields_ = [(name, ctypes.c_void_p) for name in PTAU_SECTIONS]
+
+
+class PtauPokC(ctypes.Structure):
+    _fields_ = [("g1_s", ctypes.c_uint8 * 64), ("g1_sx", ctypes.c_uint8 * 64), ("g2_spx", ctypes.c_uint8 * 128)]
+
+
+class PtauContributionC(ctypes.Structure):
+    """g16_ptau_contribution (include/g16hip.h): 1216 bytes"""
+    _fields_ = [("tauG1", ctypes.c_uint8 * 64), ("alphaG1", ctypes.c_uint8 * 64), ("betaG1", ctypes.c_uint8 * 64),
+                ("tauG2", ctypes.c_uint8 * 128), ("betaG2", ctypes.c_uint8 * 128), ("pok", PtauPokC * 3)]
+
+
+PTAU_CONTRIBUTION_BYTES = 1216
+assert ctypes.sizeof(PtauContributionC) == PTAU_CONTRIBUTION_BYTES
+
+
+# the check of a .ptau (include/g16hip.h): the arrays and the relations of a report in order
+PTAU_REPORT_ARRAYS = PTAU_SECTIONS + ("record tauG1", "record alphaG1", "record betaG1", "record tauG2", "record betaG2",
+                                      "g1_s", "g1_sx", "g2_spx", "challenges")
+PTAU_RELATIONS = ("ELEMENTS", "FIRST", "TAU_G1", "TAU_G2", "ALPHA", "BETA", "BETA_G2", "POK", "STEP", "LAST")
+
+
+class PtauReportC(ctypes.Structure):
+    """g16_ptau_report (include/g16hip.h)"""
+    _fields_ = [("failed", ctypes.c_uint32), ("relation", ctypes.c_int32 * len(PTAU_RELATIONS)),
+                ("first_record", ctypes.c_size_t * 2),
+                ("first_bad", (ctypes.c_size_t * 3) * len(PTAU_REPORT_ARRAYS)),
+                ("bad_count", (ctypes.c_size_t * 3) * len(PTAU_REPORT_ARRAYS)),
+                ("first_infinity", ctypes.c_size_t * len(PTAU_REPORT_ARRAYS))]
+
+
+class PtauReport:
+    """What g16_ptau_verify found: relation[k] = 1 (holds), 0 (fails) or -1 (not run) for PTAU_RELATIONS[k]; first_record =
+    the first record whose POK / STEP fails, or None; first_bad / bad_count [array][check] for PTAU_REPORT_ARRAYS as in a
+    KeyReport (the three-per-record arrays count 3 j + x); first_infinity[array] = the first (0,0) element, or None."""
+
+    def __init__(self, failed, relation, first_record, first_bad, bad_count, first_infinity):
+        self.failed, self.relation, self.first_record = failed, list(relation), list(first_record)
+        self.first_bad, self.bad_count, self.first_infinity = first_bad, bad_count, list(first_infinity)
+
+    @property
+    def ok(self) -> bool:
+        return self.failed == 0
+
+    def as_dict(self) -> dict:
+        return {"failed": self.failed, "relation": self.relation, "first_record": self.first_record,
+                "first_bad": self.first_bad, "bad_count": self.bad_count, "first_infinity": self.first_infinity}
+
+    def findings(self):
+        out = []
+        what = ("is not a canonical encoding", "is not on the curve", "is not in the order-r subgroup")
+        for a, name in enumerate(PTAU_REPORT_ARRAYS):
+            for k in range(3):
+                if self.bad_count[a][k]:
+                    more = self.bad_count[a][k] - 1
+                    out.append(f"{name}[{self.first_bad[a][k]}] {what[k]}" + (f" (and {more} more)" if more else ""))
+            if self.first_infinity[a] is not None:
+                out.append(f"{name}[{self.first_infinity[a]}] is the point at infinity")
+        for k, name in enumerate(PTAU_RELATIONS):
+            if k and self.relation[k] == 0:
+                rec = f" (first at record {self.first_record[k - 7]})" if name in ("POK", "STEP") else ""
+                out.append(f"{name} fails{rec}")
+        return out
+
+    def __str__(self):
+        rel = "  ".join(f"{n} {'ok' if v == 1 else 'FAILS' if v == 0 else 'not run'}" for n, v in zip(PTAU_RELATIONS, self.relation))
+        return rel + "".join("\n  " + f for f in self.findings())
 
 
 # contribution chain (include/g16hip.h): the arrays and the relations of a report in order
@@ -468,9 +541,15 @@ def load_library():
                                       ctypes.POINTER(SetupPoints)]
     lib.g16_points_scale_g1.argtypes = [vp, vp, sz, vp, u32, vp]
     lib.g16_points_scale_g2.argtypes = [vp, vp, sz, vp, u32, vp]
+    lib.g16_points_scale_each_g1.argtypes = [vp, vp, sz, vp, u32, vp]
+    lib.g16_points_scale_each_g2.argtypes = [vp, vp, sz, vp, u32, vp]
     lib.g16_key_contribute.argtypes = [vp, ctypes.POINTER(Phase2Key), vp, vp, u32, vp, ctypes.POINTER(Phase2Out)]
     lib.g16_contributions_verify.argtypes = [vp, ctypes.POINTER(Phase2Key), ctypes.POINTER(Phase2Key),
                                              ctypes.POINTER(ContributionC), vp, sz, vp, vp, ctypes.POINTER(ChainReportC)]
+    lib.g16_ptau_contribute.argtypes = [vp, ctypes.POINTER(PtauDesc), vp, vp, vp, vp, u32, vp, ctypes.POINTER(PtauOut),
+                                        ctypes.POINTER(PtauContributionC)]
+    lib.g16_ptau_verify.argtypes = [vp, ctypes.POINTER(PtauDesc), ctypes.POINTER(PtauContributionC), vp, sz, vp,
+                                    ctypes.POINTER(PtauReportC)]
     for name in SYMBOLS:
         if name not in ("g16_ctx_destroy", "g16_last_error", "g16_points_release", "g16_points_count",
                         "g16_points_inf_count",
@@ -780,6 +859,18 @@ class Context:
                        SCALARS_MONT if mont else SCALARS_STD, out))
         return out.raw[: len(points)]
 
+    def points_scale_each(self, group: int, points: bytes, scalars: bytes, mont: bool = True) -> bytes:
+        """g16_points_scale_each_g1/g2: out[i] = scalars[i] * points[i], one 32-byte scalar per point (canonical, all in
+        one form; zero is legal) and affine points of the curve, (0,0) anywhere"""
+        psz = 64 if group == 1 else 128
+        assert len(points) % psz == 0 and len(scalars) == 32 * (len(points) // psz), \
+            f"points of {psz} bytes and one 32-byte scalar for each"
+        out = ctypes.create_string_buffer(max(1, len(points)))
+        fn = self._lib.g16_points_scale_each_g1 if group == 1 else self._lib.g16_points_scale_each_g2
+        self._check(fn(self._h, _buf(bytes(points)), len(points) // psz, _buf(bytes(scalars)),
+                       SCALARS_MONT if mont else SCALARS_STD, out))
+        return out.raw[: len(points)]
+
     @staticmethod
     def _phase2_key(key: dict):
         """{delta1, delta2, pointsC1, pointsH1: bytes} -> (Phase2Key, the buffers it points into)"""
@@ -808,6 +899,59 @@ class Context:
                                                  SCALARS_MONT if mont else SCALARS_STD, _buf(bytes(challenge_g2)),
                                                  ctypes.byref(o)))
         return {name: bufs[name].raw[: len(keep[name])] for name in keep}, bytes(rec)
+
+    def ptau_contribute(self, ptau: dict, t: bytes, a: bytes, b: bytes, s3: bytes, challenges_g2: bytes, mont: bool = True,
+                        power: int = None):
+        """g16_ptau_contribute.  ptau: {tauG1, tauG2, alphaTauG1, betaTauG1, betaG2: bytes} of the power `power` (None:
+        from the length of tauG2); t, a, b: 32-byte secrets, s3: the three proof-of-knowledge secrets (96 bytes), all
+        non-zero; challenges_g2: the three 128-byte challenge points for t, a, b (the caller derives them: phase1.py).
+        -> ({tauG1, ...} of the contributed powers, the 1216-byte record)"""
+        assert len(t) == len(a) == len(b) == 32 and len(s3) == 96 and len(challenges_g2) == 384
+        keep = {name: bytes(ptau[name]) for name in PTAU_SECTIONS}
+        if power is None:
+            power = max(0, (len(keep["tauG2"]) // 128).bit_length() - 1)
+            assert [len(keep[n]) for n in PTAU_SECTIONS] == [64 * ((2 << power) - 1), 128 << power, 64 << power,
+                                                             64 << power, 128], "not the arrays of one power"
+        desc = PtauDesc(power, *[ctypes.cast(ctypes.c_char_p(keep[n]), ctypes.c_void_p) if keep[n] else None
+                                 for n in PTAU_SECTIONS])
+        bufs = {name: ctypes.create_string_buffer(max(1, len(v))) for name, v in keep.items()}
+        o = PtauOut(*[ctypes.cast(bufs[n], ctypes.c_void_p) for n in PTAU_SECTIONS])
+        rec = PtauContributionC()
+        self._check(self._lib.g16_ptau_contribute(self._h, ctypes.byref(desc), _buf(bytes(t)), _buf(bytes(a)), _buf(bytes(b)),
+                                                  _buf(bytes(s3)), SCALARS_MONT if mont else SCALARS_STD,
+                                                  _buf(bytes(challenges_g2)), ctypes.byref(o), ctypes.byref(rec)))
+        return {name: bufs[name].raw[: len(keep[name])] for name in PTAU_SECTIONS}, bytes(rec)
+
+    def ptau_verify(self, ptau: dict, records, challenges_g2, multipliers, power: int = None) -> PtauReport:
+        """g16_ptau_verify.  ptau: {tauG1, ...: bytes}; records: the 1216-byte records in order, or None (no chain to
+        check); challenges_g2: 384 bytes per record; multipliers: 2^(power+1) - 2 ints in [1, 2^128) (or their 16-byte
+        encodings, joined), drawn by the caller after every input is fixed."""
+        keep = {name: bytes(ptau[name]) for name in PTAU_SECTIONS}
+        if power is None:
+            power = max(0, (len(keep["tauG2"]) // 128).bit_length() - 1)
+            assert [len(keep[n]) for n in PTAU_SECTIONS] == [64 * ((2 << power) - 1), 128 << power, 64 << power,
+                                                             64 << power, 128], "not the arrays of one power"
+        desc = PtauDesc(power, *[ctypes.cast(ctypes.c_char_p(keep[n]), ctypes.c_void_p) for n in PTAU_SECTIONS])
+        m = (2 << power) - 2
+        if isinstance(multipliers, (bytes, bytearray)):
+            zs = bytes(multipliers)
+        else:
+            zs = b"".join(int(z).to_bytes(16, "little") for z in multipliers)
+        assert len(zs) == 16 * m or not 1 <= power <= 25, f"{m} multipliers of 16 bytes each"
+        recs, ch, count = None, None, 0
+        if records is not None:
+            count = len(records)
+            assert all(len(r) == PTAU_CONTRIBUTION_BYTES for r in records)
+            recs = (PtauContributionC * max(1, count)).from_buffer_copy(b"".join(records) or bytes(PTAU_CONTRIBUTION_BYTES))
+            ch = b"".join(challenges_g2)
+            assert len(ch) == 384 * count, "three 128-byte challenge points per record"
+        rep = PtauReportC()
+        self._check(self._lib.g16_ptau_verify(self._h, ctypes.byref(desc), recs, _buf(ch) if ch else None, count, _buf(zs),
+                                              ctypes.byref(rep)))
+        none = ctypes.c_size_t(-1).value
+        opt = lambda row: [None if f == none else f for f in row]     # noqa: E731
+        return PtauReport(rep.failed, list(rep.relation), opt(rep.first_record), [opt(row) for row in rep.first_bad],
+                          [list(row) for row in rep.bad_count], opt(rep.first_infinity))
 
     def contributions_verify(self, initial: dict, final: dict, records, challenges_g2, c1_multipliers,
                              h1_multipliers) -> ChainReport:

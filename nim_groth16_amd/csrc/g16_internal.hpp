@@ -407,6 +407,10 @@ struct ScaleJob;
 // d_out_aff[i] = k * d_pts[i], canonical affine; d_out_aff may be d_pts
 template <class C>
 int32_t scale_uniform_device(g16_ctx* ctx, const void* d_pts, size_t n, const ScaleJob& job, void* d_out_aff);
+// d_out_aff[i] = d_scalars[i] * d_pts[i] (scale_each.cuh, instantiated in scale_each_g1.hip / scale_each_g2.hip); d_scalars:
+// n x 32 bytes in HBM, canonical, Montgomery form if `mont`; d_out_aff may be d_pts
+template <class C>
+int32_t scale_each_device(g16_ctx* ctx, const void* d_pts, size_t n, const void* d_scalars, uint32_t mont, void* d_out_aff);
 }  // namespace g16
 // the job of k (standard form, < r): its plan into `plan` (the host copy the upload reads: it must outlive the stream's
 // work) and into d_steps (ScalePlan::MAX_STEPS words of device memory)

@@ -93,12 +93,12 @@ FF_HD g2_acc scale_ladder(const g2_aff& p, const ScaleArgs& a) {
   return scalar_mul<G2>(p, a.k);
 }
 
-// The SCALE_GROUP points of one lane: pts[first + j * stride], j < SCALE_GROUP, those below n.  `park(k)`: the lane's
-// k-th parking slot, k < 3 (SCALE_GROUP - 1) (LDS on the device).  In place (out == pts) is fine: a lane writes only
-// what it alone has read.
-template <class C, class Park>
-FF_HD void scale_lane(const typename C::Aff* pts, uint64_t n, uint64_t first, uint64_t stride,
-                      const ScaleArgs& args, Park park, typename C::Aff* out) {
+// The SCALE_GROUP points of one lane: index first + j * stride, j < SCALE_GROUP, those below n.  `ladder(i)`: the
+// multiple of point i in XYZZ form, whatever scalar it takes (the one of scale_uniform here, the point's own in
+// scale_each.cuh).  `park(k)`: the lane's k-th parking slot, k < 3 (SCALE_GROUP - 1) (LDS on the device).  In place
+// (out == the array `ladder` reads) is fine: a lane writes only what it alone has read.
+template <class C, class Ladder, class Park>
+FF_HD void scale_group(uint64_t n, uint64_t first, uint64_t stride, Ladder ladder, Park park, typename C::Aff* out) {
   using F = typename C::Field;
   using E = typename C::E;
   E a = F::zero(), b = F::zero(), d = F::one(), c = F::one();
@@ -106,7 +106,7 @@ FF_HD void scale_lane(const typename C::Aff* pts, uint64_t n, uint64_t first, ui
   for (int j = 0; j < SCALE_GROUP; ++j) {
     const uint64_t i = first + (uint64_t)j * stride;
     typename C::Acc acc = C::acc_inf();
-    if (i < n) acc = scale_ladder(pts[i], args);
+    if (i < n) acc = ladder(i);
     d = F::mul(acc.zz, acc.zzz);
     if (F::is_zero(d)) {
       a = F::zero(), b = F::zero(), d = F::one();
@@ -128,6 +128,11 @@ FF_HD void scale_lane(const typename C::Aff* pts, uint64_t n, uint64_t first, ui
     if (i < n) out[i] = typename C::Aff{F::mul(a, inv), F::mul(b, inv)};
     inv = F::mul(inv, d);
   }
+}
+template <class C, class Park>
+FF_HD void scale_lane(const typename C::Aff* pts, uint64_t n, uint64_t first, uint64_t stride,
+                      const ScaleArgs& args, Park park, typename C::Aff* out) {
+  scale_group<C>(n, first, stride, [&](uint64_t i) { return scale_ladder(pts[i], args); }, park, out);
 }
 
 #if defined(__HIPCC__)

@@ -1,5 +1,5 @@
-// Scaling an array of points by one scalar (include/g16hip.h, "scaling an array of points"): host layer of
-// g16_points_scale_g1/g2 and the job every caller of scale_uniform_device builds first.  The schedule of the G1 ladder is
+// Scaling an array of points by one scalar or by a scalar per point (include/g16hip.h, "scaling an array of points"): host
+// layer of g16_points_scale_g1/g2 and g16_points_scale_each_g1/g2, and the job every caller of scale_uniform_device builds first.  The schedule of the G1 ladder is
 // made here, once per call, from the scalar (scale_plan.hpp); kernels: scale.cuh.
 #include "g16_internal.hpp"
 #include "ec.cuh"
@@ -61,8 +61,47 @@ int32_t points_scale(g16_ctx* ctx, const void* points, size_t n, const void* k, 
   return G16_OK;
 }
 
+// a scalar per point: the scalars are checked here, the split of each is the lane's own work (scale_each.cuh)
+template <class C>
+int32_t points_scale_each(g16_ctx* ctx, const void* points, size_t n, const void* scalars, uint32_t flags, void* out) {
+  if (!ctx) return G16_EINVAL;
+  auto bad = [&](const std::string& msg) {
+    ctx->err = "g16_points_scale_each: " + msg;
+    return G16_EINVAL;
+  };
+  if (n && (!points || !scalars || !out)) return bad("null pointer argument");
+  if (flags != G16_SCALARS_MONT && flags != G16_SCALARS_STD) return bad("flags must be G16_SCALARS_MONT or G16_SCALARS_STD");
+  if (n >= (size_t(1) << 31)) return bad("n out of range (must be < 2^31)");
+  for (size_t i = 0; i < n; ++i) {
+    u256 kv;
+    memcpy(&kv, (const char*)scalars + 32 * i, 32);
+    if (!Fr::is_canonical(kv)) return bad("scalar " + std::to_string(i) + " is not canonical (>= r)");
+  }
+  if (!n) return G16_OK;
+  CTX_ENTER(ctx);
+  DevMem<typename C::Aff> d_pts;
+  DevMem<u256> d_k;
+  SyncOnExit drain{ctx->stream};
+  HIPCHK(ctx, dev_alloc(d_pts, n * sizeof(typename C::Aff)));
+  HIPCHK(ctx, dev_alloc(d_k, n * sizeof(u256)));
+  HIPCHK(ctx, hipMemcpyAsync(d_pts.get(), points, n * sizeof(typename C::Aff), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(d_k.get(), scalars, n * sizeof(u256), hipMemcpyHostToDevice, ctx->stream));
+  if (int32_t rc = scale_each_device<C>(ctx, d_pts.get(), n, d_k.get(), flags == G16_SCALARS_MONT, d_pts.get())) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(out, d_pts.get(), n * sizeof(typename C::Aff), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return G16_OK;
+}
+
 }  // namespace
 
+extern "C" int32_t g16_points_scale_each_g1(g16_ctx* ctx, const void* points, size_t n, const void* scalars,
+                                            uint32_t flags, void* out) {
+  return points_scale_each<G1>(ctx, points, n, scalars, flags, out);
+}
+extern "C" int32_t g16_points_scale_each_g2(g16_ctx* ctx, const void* points, size_t n, const void* scalars,
+                                            uint32_t flags, void* out) {
+  return points_scale_each<G2>(ctx, points, n, scalars, flags, out);
+}
 extern "C" int32_t g16_points_scale_g1(g16_ctx* ctx, const void* points, size_t n, const void* k, uint32_t flags,
                                        void* out) {
   return points_scale<G1>(ctx, points, n, k, flags, out);

@@ -7,7 +7,9 @@ g16_circuit_audit).  The iden3 container with magic `ptau`, version 1:
     section 4   alphaTauG1   2^power G1 points           alpha tau^k gen1
     section 5   betaTauG1    2^power G1 points           beta tau^k gen1
     section 6   betaG2       one G2 point                beta gen2
-    sections 7 (contributions) and 12-15 (the Lagrange forms a prepared file carries) are skipped if present
+    section 7   the contribution log, in THIS project's layout (phase1.py; parsePtauContributions / contributionsSection):
+                count u32 | count records of 1216 bytes (g16_ptau_contribution) | count names, each length u32 | UTF-8
+    sections 12-15 (the Lagrange forms a prepared file carries) are skipped if present; parsePtau skips section 7 too
 
 Points are uncompressed, little-endian, in Montgomery form: byte for byte what a .zkey's point sections hold and what
 the GPU library takes, so they are passed through unparsed.
@@ -66,3 +68,48 @@ def writePtau(fname: str, ptau: Ptau, extraSections=()) -> None:
     s1 = struct.pack("<I", 32) + F.primeP.to_bytes(32, "little") + struct.pack("<II", ptau.power, cer)
     writeContainer("ptau", 1, fname, [(1, s1)] + [(sid, getattr(ptau, name)) for sid, name, _ in _SECTIONS] +
                    list(extraSections))
+
+
+PTAU_RECORD_BYTES = 1216
+
+
+def contributionsSection(records, names) -> bytes:
+    """section 7 from the records (1216 bytes each) and the contributors' names: pass it to writePtau as
+    extraSections=[(7, ...)]"""
+    assert len(records) == len(names) and all(len(r) == PTAU_RECORD_BYTES for r in records)
+    out = [struct.pack("<I", len(records))] + [bytes(r) for r in records]
+    for name in names:
+        raw = name.encode("utf-8")
+        out.append(struct.pack("<I", len(raw)) + raw)
+    return b"".join(out)
+
+
+def parsePtauContributions(fname: str):
+    """-> (records, names) of section 7, or None if the file has none.  ValueError if the section is not in this project's
+    layout (a snarkjs-written file: its records are not ours, see phase1.py)."""
+    sec = parseContainer("ptau", 1, fname)
+    if 7 not in sec:
+        return None
+    s = bytes(sec[7][0])
+    if len(s) < 4:
+        raise ValueError("section 7 is shorter than its count")
+    (count,) = struct.unpack_from("<I", s, 0)
+    pos = 4 + PTAU_RECORD_BYTES * count
+    if len(s) < pos:
+        raise ValueError("section 7 is truncated: it ends inside its records")
+    records = [s[4 + PTAU_RECORD_BYTES * j:4 + PTAU_RECORD_BYTES * (j + 1)] for j in range(count)]
+    names = []
+    for _ in range(count):
+        if len(s) < pos + 4:
+            raise ValueError("section 7 is truncated: it ends inside its names")
+        (ln,) = struct.unpack_from("<I", s, pos)
+        if len(s) < pos + 4 + ln:
+            raise ValueError("section 7 is truncated: it ends inside its names")
+        try:
+            names.append(s[pos + 4:pos + 4 + ln].decode("utf-8"))
+        except UnicodeDecodeError:
+            raise ValueError("section 7: a name is not UTF-8") from None
+        pos += 4 + ln
+    if pos != len(s):
+        raise ValueError("section 7: bytes left over after the names")
+    return records, names

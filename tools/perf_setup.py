@@ -24,7 +24,18 @@ records) on the part of a key a contribution touches at 2^log2n: pointsC1 and po
 multiples of gen1; no circuit is needed: the two calls read nothing else of a key), wall time of the Python call and the
 library's per-kernel times.  The chain is checked to verify, and to fail once a point of the final key is moved.
 
-  python tools/perf_setup.py --contribute [--log2n 20] [--repeats 3] [--out FILE]"""
+  python tools/perf_setup.py --contribute [--log2n 20] [--repeats 3] [--out FILE]
+
+--ptau-contribute: the phase-1 contribution instead -- the whole g16_ptau_contribute on a fakePtau of power log2n (tauG1 of
+2^(log2n+1) - 1 points, the three shorter arrays of 2^log2n), wall time of the Python call and the library's per-kernel
+times; the result of every call is compared with the fakePtau of the product of the secrets, byte for byte.
+
+  python tools/perf_setup.py --ptau-contribute [--log2n 21] [--repeats 3] [--out FILE]
+
+--ptau-verify: g16_ptau_verify on the same fakePtau with a chain of no records (the sums and the five fixed products are
+what grows with the power), wall time and per-kernel times; then the file with one element of tauG1 doubled must fail.
+
+  python tools/perf_setup.py --ptau-verify [--log2n 21] [--repeats 3] [--out FILE]"""
 import argparse
 import gc
 import os
@@ -202,11 +213,117 @@ def contribute_main(args):
         f.write("\n".join(lines) + "\n")
 
 
+def ptau_contribute_main(args):
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+
+    from nim_groth16_amd import bn128 as F
+    from nim_groth16_amd._lib import PTAU_SECTIONS, device_code_sha16
+    ctx = Context(0)
+    ctx.selftest()
+    power = args.log2n
+    rng = SplitMix64(21)
+    waste = [rng.fr() or 1 for _ in range(3)]
+    say(f"phase-1 contribution at power {power}: tauG1 of {(2 << power) - 1} points, tauG2 / alphaTauG1 / betaTauG1 of "
+        f"{1 << power}, {args.repeats} repeats ({time.strftime('%Y-%m-%d')}; library kernels {device_code_sha16()})")
+    t0 = time.perf_counter()
+    pt = FS.fakePtau(waste[0], waste[1], waste[2], power, ctx)
+    say(f"fakePtau, power {power}: {time.perf_counter() - t0:.1f} s")
+    arrays = {k: getattr(pt, k) for k in PTAU_SECTIONS}
+    chal = ctx.fixed_base(2, F.frSeqToMontBytes([7, 8, 9]))
+    small = {k: getattr(FS.fakePtau(1, 1, 1, 3, ctx), k) for k in PTAU_SECTIONS}
+    enc = F.frToMontBytes
+    ctx.ptau_contribute(small, enc(2), enc(3), enc(4), F.frSeqToMontBytes([5, 6, 7]), chal)   # warm-up: code objects
+    walls = []
+    for rep in range(args.repeats):
+        x = [rng.fr() or 1 for _ in range(6)]
+        ctx.profile(True)
+        ctx.profile_reset()
+        t0 = time.perf_counter()
+        new, _ = ctx.ptau_contribute(arrays, enc(x[0]), enc(x[1]), enc(x[2]), F.frSeqToMontBytes(x[3:]), chal, power=power)
+        dt = time.perf_counter() - t0
+        rep_k = ctx.profile_report()
+        ctx.profile(False)
+        kern = "  ".join(f"{k} {v['total_ms']:.2f} ({v['calls']})" for k, v in sorted(rep_k.items()))
+        say(f"  g16_ptau_contribute #{rep}: {dt * 1e3:8.1f} ms wall   kernels, ms (launches): {kern}")
+        walls.append(dt)
+        waste = [a * b % F.primeR for a, b in zip(waste, x[:3])]
+        want = FS.fakePtau(waste[0], waste[1], waste[2], power, ctx)
+        if any(new[k] != getattr(want, k) for k in PTAU_SECTIONS):
+            raise SystemExit("the contributed powers are not those of the product of the secrets")
+        arrays = new
+        del want
+    walls.sort()
+    say(f"  median: {walls[len(walls) // 2] * 1e3:.1f} ms wall (min {walls[0] * 1e3:.1f}, max {walls[-1] * 1e3:.1f}, "
+        f"{len(walls)} calls); every result equals fakePtau of the product of the secrets byte for byte")
+    ctx.close()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+def ptau_verify_main(args):
+    import numpy as np
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+
+    from nim_groth16_amd._lib import PTAU_SECTIONS, device_code_sha16
+    ctx = Context(0)
+    ctx.selftest()
+    power = args.log2n
+    rng = SplitMix64(22)
+    pt = FS.fakePtau(rng.fr(), rng.fr(), rng.fr(), power, ctx)
+    arrays = {k: getattr(pt, k) for k in PTAU_SECTIONS}
+    z = np.random.default_rng(23).integers(0, 1 << 63, size=((2 << power) - 2, 2), dtype=np.uint64)
+    z[:, 0] |= np.uint64(1)
+    z = z.tobytes()
+    say(f"g16_ptau_verify at power {power}, no records, {args.repeats} repeats ({time.strftime('%Y-%m-%d')}; library kernels "
+        f"{device_code_sha16()})")
+    small = {k: getattr(FS.fakePtau(2, 3, 5, 3, ctx), k) for k in PTAU_SECTIONS}
+    ctx.ptau_verify(small, None, None, [3] * 14)                                   # warm-up: code objects
+    walls = []
+    for rep in range(args.repeats):
+        ctx.profile(True)
+        ctx.profile_reset()
+        t0 = time.perf_counter()
+        report = ctx.ptau_verify(arrays, None, None, z, power=power)
+        dt = time.perf_counter() - t0
+        rep_k = ctx.profile_report()
+        ctx.profile(False)
+        kern = "  ".join(f"{k} {v['total_ms']:.2f} ({v['calls']})" for k, v in sorted(rep_k.items()))
+        say(f"  g16_ptau_verify #{rep}: {dt * 1e3:8.1f} ms wall   kernels, ms (launches): {kern}")
+        walls.append(dt)
+        if report.relation != [1] * 7 + [-1] * 3:
+            raise SystemExit(f"honest powers do not verify: {report}")
+    bad = dict(arrays)
+    k = 12345 % ((2 << power) - 1)
+    dbl = ctx.points_scale(1, arrays["tauG1"][64 * k:64 * k + 64], (2).to_bytes(32, "little"), mont=False)
+    bad["tauG1"] = arrays["tauG1"][:64 * k] + dbl + arrays["tauG1"][64 * k + 64:]
+    report = ctx.ptau_verify(bad, None, None, z, power=power)
+    if report.relation[2] != 0:
+        raise SystemExit(f"a doubled element of tauG1 is not found: {report}")
+    walls.sort()
+    say(f"  median: {walls[len(walls) // 2] * 1e3:.1f} ms wall (min {walls[0] * 1e3:.1f}, max {walls[-1] * 1e3:.1f}); honest "
+        f"powers verify, tauG1[{k}] doubled gives TAU_G1 = 0")
+    ctx.close()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--circuit-setup", action="store_true", help="measure g16_circuit_setup (see the module text)")
     ap.add_argument("--contribute", action="store_true",
                     help="measure g16_key_contribute and g16_contributions_verify (see the module text)")
+    ap.add_argument("--ptau-contribute", action="store_true", help="measure g16_ptau_contribute (see the module text)")
+    ap.add_argument("--ptau-verify", action="store_true", help="measure g16_ptau_verify (see the module text)")
     ap.add_argument("--log2n", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fake_setup_ab.txt"))
@@ -215,6 +332,10 @@ def main():
         return circuit_setup_main(args)
     if args.contribute:
         return contribute_main(args)
+    if args.ptau_contribute:
+        return ptau_contribute_main(args)
+    if args.ptau_verify:
+        return ptau_verify_main(args)
     lines = []
 
     def say(s=""):
