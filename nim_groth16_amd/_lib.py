@@ -85,6 +85,21 @@ AUDIT_SECTIONS = ("alpha1", "beta1", "delta1", "beta2", "gamma2", "delta2", "poi
 AUDIT_CHECKS = ("canonical", "curve", "subgroup")
 AUDIT_RELATIONS = ("pointsB1~pointsB2", "beta1~beta2", "delta1~delta2")
 AUDIT_CANONICAL, AUDIT_CURVE, AUDIT_SUBGROUP, AUDIT_RELATION, AUDIT_SPEC_INFINITY = 1, 2, 4, 8, 16
+# what an element that fails AUDIT_CHECKS[k] is said to be, in every report and error text (CHECK_TEXT, relation_plan.hpp)
+CHECK_TEXTS = ("is not a canonical encoding", "is not on the curve", "is not in the order-r subgroup")
+
+
+def _element_findings(names, first_bad, bad_count, first_infinity=None, prefix=""):
+    """one line per first finding of the element passes over the arrays `names`: index and check, then the first (0,0)"""
+    out = []
+    for a, name in enumerate(names):
+        for k, what in enumerate(CHECK_TEXTS):
+            if bad_count[a][k]:
+                more = bad_count[a][k] - 1
+                out.append(f"{prefix}{name}[{first_bad[a][k]}] {what}" + (f" (and {more} more)" if more else ""))
+        if first_infinity is not None and first_infinity[a] is not None:
+            out.append(f"{prefix}{name}[{first_infinity[a]}] is the point at infinity")
+    return out
 
 
 class KeyReportC(ctypes.Structure):
@@ -114,14 +129,7 @@ class KeyReport:
 
     def findings(self):
         """one line per first finding: section, index and check; failed relations; spec points at infinity"""
-        out = []
-        for s, name in enumerate(AUDIT_SECTIONS):
-            for k, check in enumerate(AUDIT_CHECKS):
-                if self.bad_count[s][k]:
-                    what = {"canonical": "is not a canonical encoding", "curve": "is not on the curve",
-                            "subgroup": "is not in the order-r subgroup"}[check]
-                    more = self.bad_count[s][k] - 1
-                    out.append(f"{name}[{self.first_bad[s][k]}] {what}" + (f" (and {more} more)" if more else ""))
+        out = _element_findings(AUDIT_SECTIONS, self.first_bad, self.bad_count)
         for k, name in enumerate(AUDIT_RELATIONS):
             if self.relation[k] == 0:
                 out.append(f"{name}: not the same multiples of the two generators")
@@ -187,14 +195,7 @@ class CircuitReport:
                 "relation": self.relation, "failed": self.failed, "first_row": self.first_row}
 
     def findings(self):
-        out = list(self.key.findings())
-        for s, name in enumerate(PTAU_SECTIONS):
-            for k, check in enumerate(AUDIT_CHECKS):
-                if self.ptau_bad_count[s][k]:
-                    what = {"canonical": "is not a canonical encoding", "curve": "is not on the curve",
-                            "subgroup": "is not in the order-r subgroup"}[check]
-                    more = self.ptau_bad_count[s][k] - 1
-                    out.append(f"ptau {name}[{self.ptau_first_bad[s][k]}] {what}" + (f" (and {more} more)" if more else ""))
+        out = self.key.findings() + _element_findings(PTAU_SECTIONS, self.ptau_first_bad, self.ptau_bad_count, prefix="ptau ")
         for m in range(2):
             if self.relation[m] == 0:
                 out.append(f"coeffs: matrix {'AB'[m]} differs from the r1cs first at row {self.first_row[m]}")
@@ -287,15 +288,7 @@ class PtauReport:
                 "first_bad": self.first_bad, "bad_count": self.bad_count, "first_infinity": self.first_infinity}
 
     def findings(self):
-        out = []
-        what = ("is not a canonical encoding", "is not on the curve", "is not in the order-r subgroup")
-        for a, name in enumerate(PTAU_REPORT_ARRAYS):
-            for k in range(3):
-                if self.bad_count[a][k]:
-                    more = self.bad_count[a][k] - 1
-                    out.append(f"{name}[{self.first_bad[a][k]}] {what[k]}" + (f" (and {more} more)" if more else ""))
-            if self.first_infinity[a] is not None:
-                out.append(f"{name}[{self.first_infinity[a]}] is the point at infinity")
+        out = _element_findings(PTAU_REPORT_ARRAYS, self.first_bad, self.bad_count, self.first_infinity)
         for k, name in enumerate(PTAU_RELATIONS):
             if k and self.relation[k] == 0:
                 rec = f" (first at record {self.first_record[k - 7]})" if name in ("POK", "STEP") else ""
@@ -348,15 +341,7 @@ class ChainReport:
         out = []
         if self.transcript == 0:
             out.append("the transcript hashes are not those of the initial key and the records")
-        for a, name in enumerate(CHAIN_ARRAYS):
-            for k, check in enumerate(AUDIT_CHECKS):
-                if self.bad_count[a][k]:
-                    what = {"canonical": "is not a canonical encoding", "curve": "is not on the curve",
-                            "subgroup": "is not in the order-r subgroup"}[check]
-                    more = self.bad_count[a][k] - 1
-                    out.append(f"{name}[{self.first_bad[a][k]}] {what}" + (f" (and {more} more)" if more else ""))
-            if self.first_infinity[a] is not None:
-                out.append(f"{name}[{self.first_infinity[a]}] is the point at infinity")
+        out += _element_findings(CHAIN_ARRAYS, self.first_bad, self.bad_count, self.first_infinity)
         if self.relation[1] == 0:
             out.append(f"record {self.first_record[0]}: the proof of knowledge does not hold")
         if self.relation[2] == 0:

@@ -3,39 +3,26 @@
 // asserts the curve equations while it loads a .zkey (mkG1 / mkG2, curves.nim:95-107); this is that and more, as one
 // call that reports where a key fails instead of aborting.  Kernels: audit.cuh.
 #include "audit.cuh"
-#include "g16_internal.hpp"
+#include "checker.hpp"
 
 using namespace g16;
 
-void g16_curve_consts_g2(void* gen2, void* twist_b);   // msm_g2_misc.hip: gen2 (128 B), twistCoeffB (64 B)
-
 namespace {
 
+// the constant of the curve equation
 template <class C>
-struct Consts;
+auto curve_b();
 template <>
-struct Consts<G1> {
-  static g1_aff gen() { return g1_aff{Fp::one(), Fp::dbl(Fp::one())}; }               // (1, 2), curves.nim:112-113
-  static u256 b() { return Fp::add(Fp::dbl(Fp::one()), Fp::one()); }                   // y^2 = x^3 + 3
-};
+auto curve_b<G1>() {
+  return Fp::add(Fp::dbl(Fp::one()), Fp::one());   // y^2 = x^3 + 3
+}
 template <>
-struct Consts<G2> {
-  static g2_aff gen() {
-    g2_aff g;
-    fp2_t b;
-    g16_curve_consts_g2(&g, &b);
-    return g;
-  }
-  static fp2_t b() {
-    g2_aff g;
-    fp2_t b;
-    g16_curve_consts_g2(&g, &b);
-    return b;
-  }
-};
-
-constexpr size_t NONE = (size_t)-1;
-constexpr int NSEC = G16_AUDIT_SECTIONS;
+auto curve_b<G2>() {
+  g2_aff g;
+  fp2_t b;
+  g16_curve_consts_g2(&g, &b);
+  return b;
+}
 
 void counts_reset(AuditCounts* c, int n) {
   for (int i = 0; i < n; ++i)
@@ -52,15 +39,12 @@ void counts_out(const AuditCounts& c, size_t first_bad[3], size_t bad_count[3]) 
 template <class C>
 int32_t audit_array(g16_ctx* ctx, const void* points, size_t n, AuditCounts* d_out) {
   if (!n) return G16_OK;
-  constexpr size_t psz = sizeof(typename C::Aff);
-  int32_t rc;
-  if ((rc = ensure(ctx, ctx->stage_p, n * psz))) return rc;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->stage_p.p(), points, n * psz, hipMemcpyHostToDevice, ctx->stream));
+  if (int32_t rc = stage_points<C>(ctx, points, n)) return rc;
   constexpr int order = sizeof(typename C::Aff) == sizeof(g2_aff) ? 1 : 0;
   KLAUNCH(ctx, order ? "audit_points_g2" : "audit_points_g1", (audit_points<C, order>),
           (uint32_t)((n + AUDIT_BLOCK - 1) / AUDIT_BLOCK), AUDIT_BLOCK, order ? AUDIT_Q_WORDS * AUDIT_BLOCK * 4 : 0,
           (const typename C::Aff*)ctx->stage_p.p(),
-          (uint32_t)n, Consts<C>::b(), d_out);
+          (uint32_t)n, curve_b<C>(), d_out);
   HIPCHK(ctx, hipGetLastError());
   return G16_OK;
 }
@@ -107,23 +91,40 @@ int32_t g16_widen_multipliers(g16_ctx* ctx, const char* who, const void* multipl
   return G16_OK;
 }
 
-// the element passes of `nsec` arrays on their own (the ptau arrays of the circuit audit): one wait at the end
+// the element passes of `nsec` arrays and, for the key audit, of the coefficient values (g16_internal.hpp)
 int32_t g16_audit_sections(g16_ctx* ctx, const g16_audit_section* sec, int nsec, size_t (*first_bad)[3],
-                           size_t (*bad_count)[3]) {
-  std::vector<AuditCounts> h(nsec);
-  counts_reset(h.data(), nsec);
+                           size_t (*bad_count)[3], const g16_audit_coeffs* coeffs) {
+  const int rows = nsec + (coeffs ? 1 : 0);
+  if (rows > ElementPass::MAX) return fail(ctx, "g16_audit_sections", "too many arrays");
+  AuditCounts h[ElementPass::MAX];
+  counts_reset(h, rows);
   DevMem<AuditCounts> d_counts;
-  SyncOnExit drain{ctx->stream};
-  HIPCHK(ctx, dev_alloc(d_counts, nsec * sizeof(AuditCounts)));
-  HIPCHK(ctx, hipMemcpyAsync(d_counts.get(), h.data(), nsec * sizeof(AuditCounts), hipMemcpyHostToDevice, ctx->stream));
-  for (int s = 0; s < nsec; ++s) {
-    const int32_t rc = sec[s].group == 1 ? audit_array<G1>(ctx, sec[s].p, sec[s].n, d_counts.get() + s)
-                                         : audit_array<G2>(ctx, sec[s].p, sec[s].n, d_counts.get() + s);
-    if (rc) return rc;
-  }
-  HIPCHK(ctx, hipMemcpyAsync(h.data(), d_counts.get(), nsec * sizeof(AuditCounts), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  for (int s = 0; s < nsec; ++s) counts_out(h[s], first_bad[s], bad_count[s]);
+  DevMem<> d_coeffs;
+  // every array uploaded whole, one after the other, through the context's staging buffer
+  const int32_t rc = [&]() -> int32_t {
+    HIPCHK(ctx, dev_alloc(d_counts, rows * sizeof(AuditCounts)));
+    HIPCHK(ctx, hipMemcpyAsync(d_counts.get(), h, rows * sizeof(AuditCounts), hipMemcpyHostToDevice, ctx->stream));
+    for (int s = 0; s < nsec; ++s)
+      if (int32_t e = sec[s].group == 1 ? audit_array<G1>(ctx, sec[s].p, sec[s].n, d_counts.get() + s)
+                                        : audit_array<G2>(ctx, sec[s].p, sec[s].n, d_counts.get() + s))
+        return e;
+    if (coeffs && coeffs->count) {
+      const size_t bytes = coeffs->count * coeffs->stride;
+      HIPCHK(ctx, dev_alloc(d_coeffs, bytes));
+      HIPCHK(ctx, hipMemcpyAsync(d_coeffs.get(), coeffs->base, bytes, hipMemcpyHostToDevice, ctx->stream));
+      KLAUNCH(ctx, "audit_coeffs", audit_coeffs, (uint32_t)((coeffs->count + 255) / 256), 256, 0,
+              (const uint32_t*)d_coeffs.get(), (uint32_t)coeffs->count, (uint32_t)(coeffs->stride / 4),
+              (uint32_t)(coeffs->value_offset / 4), d_counts.get() + nsec);
+      HIPCHK(ctx, hipGetLastError());
+    }
+    HIPCHK(ctx, hipMemcpyAsync(h, d_counts.get(), rows * sizeof(AuditCounts), hipMemcpyDeviceToHost, ctx->stream));
+    return G16_OK;
+  }();
+  // the one wait, on every path: before the two buffers go, and before a caller decides from the counts what may run next
+  const hipError_t waited = hipStreamSynchronize(ctx->stream);
+  if (rc) return rc;
+  if (int32_t e = g16_hip_check(ctx->err, "hipStreamSynchronize(ctx->stream)", waited)) return e;
+  for (int s = 0; s < rows; ++s) counts_out(h[s], first_bad[s], bad_count[s]);
   return G16_OK;
 }
 
@@ -140,19 +141,15 @@ struct RelBuf {
 int32_t relation_sums(g16_ctx* ctx, const void* g1_points, const void* g2_points, size_t n, const uint64_t* scalars,
                       RelBuf* d_rel) {
   int32_t rc;
-  if ((rc = ensure(ctx, ctx->stage_s, n * 32))) return rc;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->stage_s.p(), scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
-  if ((rc = ensure(ctx, ctx->stage_p, n * 128))) return rc;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->stage_p.p(), g1_points, n * 64, hipMemcpyHostToDevice, ctx->stream));
-  if ((rc = msm_device<G1>(ctx, ctx->stage_s.p(), G16_SCALARS_STD, ctx->stage_p.p(), n, &d_rel->a[0], nullptr, 0)))
-    return rc;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->stage_p.p(), g2_points, n * 128, hipMemcpyHostToDevice, ctx->stream));
-  return msm_device<G2>(ctx, ctx->stage_s.p(), G16_SCALARS_STD, ctx->stage_p.p(), n, &d_rel->b[0], nullptr, 0);
+  if ((rc = stage_scalars(ctx, scalars, n))) return rc;
+  if ((rc = ensure(ctx, ctx->stage_p, n * sizeof(g2_aff)))) return rc;   // once, for both uploads
+  if ((rc = staged_msm<G1>(ctx, ctx->stage_s.p(), G16_SCALARS_STD, g1_points, n, &d_rel->a[0]))) return rc;
+  return staged_msm<G2>(ctx, ctx->stage_s.p(), G16_SCALARS_STD, g2_points, n, &d_rel->b[0]);
 }
 
 int32_t launch_relations(g16_ctx* ctx, RelBuf* d_rel, uint32_t first, uint32_t count) {
   KLAUNCH(ctx, "audit_relation", audit_relation, count, 64, 0, (const g1_aff*)d_rel->a + first,
-          (const g2_aff*)d_rel->b + first, G1::neg(Consts<G1>::gen()), Consts<G2>::gen(), d_rel->result + first);
+          (const g2_aff*)d_rel->b + first, G1::neg(host_gen1()), host_gen2(), d_rel->result + first);
   HIPCHK(ctx, hipGetLastError());
   return G16_OK;
 }
@@ -253,62 +250,33 @@ int32_t g16_key_audit_body(g16_ctx* ctx, const g16_pkey_desc* d, const g16_vkey_
   if (multipliers && (rc = g16_widen_multipliers(ctx, "g16_key_audit", multipliers, d->nvars, scalars))) return rc;
   CTX_ENTER(ctx);
 
-  struct Section {
-    int group;
-    const void* p;
-    size_t n;
-  };
-  const Section sec[NSEC - 1] = {
+  const g16_audit_section sec[G16_AUDIT_SECTIONS - 1] = {
       {1, d->alpha1, 1}, {1, d->beta1, 1}, {1, d->delta1, 1}, {2, d->beta2, 1}, {2, vk ? vk->gamma2 : nullptr, vk ? 1u : 0u},
       {2, d->delta2, 1}, {1, vk ? vk->pointsIC : nullptr, vk ? (size_t)d->npubs + 1 : 0}, {1, d->pointsA1, d->nvars},
       {1, d->pointsB1, d->nvars}, {2, d->pointsB2, d->nvars}, {1, d->pointsC1, (size_t)d->nvars - d->npubs - 1},
       {1, d->pointsH1, dom}};
-  AuditCounts h[NSEC];
-  counts_reset(h, NSEC);
-  DevMem<AuditCounts> d_counts;
-  DevMem<RelBuf> d_rel;
-  DevMem<> d_coeffs;
-  SyncOnExit drain{ctx->stream};   // before the three go
-  HIPCHK(ctx, dev_alloc(d_counts, sizeof h));
-  HIPCHK(ctx, dev_alloc(d_rel, sizeof(RelBuf)));
-  HIPCHK(ctx, hipMemcpyAsync(d_counts.get(), h, sizeof h, hipMemcpyHostToDevice, ctx->stream));
-  // the element passes: every array uploaded whole, one after the other, through the context's staging buffer
-  for (int s = 0; s < NSEC - 1; ++s) {
-    rc = sec[s].group == 1 ? audit_array<G1>(ctx, sec[s].p, sec[s].n, d_counts.get() + s)
-                           : audit_array<G2>(ctx, sec[s].p, sec[s].n, d_counts.get() + s);
-    if (rc) return rc;
-  }
-  if (ccount) {
-    const size_t bytes = ccount * cstride;
-    HIPCHK(ctx, dev_alloc(d_coeffs, bytes));
-    HIPCHK(ctx, hipMemcpyAsync(d_coeffs.get(), cbase, bytes, hipMemcpyHostToDevice, ctx->stream));
-    KLAUNCH(ctx, "audit_coeffs", audit_coeffs, (uint32_t)((ccount + 255) / 256), 256, 0,
-            (const uint32_t*)d_coeffs.get(), (uint32_t)ccount, (uint32_t)(cstride / 4), (uint32_t)(coff / 4),
-            d_counts.get() + (NSEC - 1));
-    HIPCHK(ctx, hipGetLastError());
-  }
-  HIPCHK(ctx, hipMemcpyAsync(h, d_counts.get(), sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+  const g16_audit_coeffs coeffs{cbase, ccount, cstride, coff};
   // The relations run only on sections whose every element passed: the sums and the Miller loops are defined for
-  // canonical points of the curve and its order-r subgroup, nothing else.  Hence this wait between the two halves.
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  d_coeffs.reset();
+  // canonical points of the curve and its order-r subgroup, nothing else.  Hence the wait of the pass between the two halves.
+  DevMem<RelBuf> d_rel;
+  SyncOnExit drain{ctx->stream};   // before d_rel goes
+  HIPCHK(ctx, dev_alloc(d_rel, sizeof(RelBuf)));
+  ElementPass pass;
+  if ((rc = pass.run(ctx, KEY_ARRAYS, sec, &coeffs))) return rc;
 
   memset(out, 0, sizeof *out);
-  for (int s = 0; s < NSEC; ++s) {
-    counts_out(h[s], out->first_bad[s], out->bad_count[s]);
+  pass.to_report(out->first_bad, out->bad_count);
+  for (int s = 0; s < G16_AUDIT_SECTIONS; ++s) {
     static const uint32_t bit[3] = {G16_AUDIT_CANONICAL, G16_AUDIT_CURVE, G16_AUDIT_SUBGROUP};
     for (int k = 0; k < 3; ++k)
-      if (h[s].bad_count[k]) out->failed |= bit[k];
+      if (out->bad_count[s][k]) out->failed |= bit[k];
   }
-  for (int s = 0; s < 6; ++s) {
-    static const unsigned char zeros[128] = {0};
-    if (sec[s].n && !memcmp(sec[s].p, zeros, sec[s].group == 1 ? 64 : 128)) out->spec_infinity |= 1u << s;
-  }
+  out->spec_infinity = pass.infinite;   // (0,0) is on the curve: it fails no check and keeps no relation from running
   if (out->spec_infinity) out->failed |= G16_AUDIT_SPEC_INFINITY;
-  auto clean = [&](int s) { return !(h[s].bad_count[0] | h[s].bad_count[1] | h[s].bad_count[2]); };
-  // relation 0: pointsB1 ~ pointsB2 (sections 8, 9), 1: beta1 ~ beta2 (1, 3), 2: delta1 ~ delta2 (2, 5)
-  const bool run[3] = {multipliers && clean(8) && clean(9), clean(1) && clean(3), clean(2) && clean(5)};
-  int32_t rel[4] = {-1, -1, -1, -1};
+  bool run[3];
+  relations_run(KEY_RELATIONS, ~pass.dirty, multipliers ? NEED_MULTIPLIERS : 0, run);
+  int32_t* rel = out->relation;
+  rel[0] = rel[1] = rel[2] = -1;
   if (run[0] || run[1] || run[2]) {
     // a relation that is not run keeps (0,0) on both sides: its workgroup multiplies two ones
     HIPCHK(ctx, hipMemsetAsync(d_rel.get(), 0, sizeof(RelBuf), ctx->stream));
@@ -327,9 +295,6 @@ int32_t g16_key_audit_body(g16_ctx* ctx, const g16_pkey_desc* d, const g16_vkey_
     for (int j = 0; j < 3; ++j)
       if (run[j]) rel[j] = got[j];
   }
-  for (int j = 0; j < 3; ++j) {
-    out->relation[j] = rel[j];
-    if (rel[j] == 0) out->failed |= G16_AUDIT_RELATION;
-  }
+  fold_report(KEY_RELATIONS, run, nullptr, 0, rel, nullptr, out->failed);
   return G16_OK;
 }

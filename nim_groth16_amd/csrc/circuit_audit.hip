@@ -3,18 +3,15 @@
 // the R1CS must give the same vectors; an inverse NTT turns A z into the coefficients of sum_i z_i A_i(X), whose MSM
 // against the powers tau^k gen1 must be the prover's own MSM(z, pointsA1); pointsB1 / B2 / C1 / IC / H1 follow the same
 // way, the last three through one pairing product each.  Nothing here is new arithmetic: the sparse products are
-// spmv.hip, the transforms ntt.hip, the sums the one-shot MSM, the element checks audit.hip.  Kernels: circuit_audit.cuh.
-#include <new>
-
+// spmv.hip, the transforms ntt.hip, the sums the one-shot MSM, the element checks audit.hip, all in the shape of a checker
+// (checker.hpp).  Kernels: circuit_audit.cuh.
 #include "circuit_audit.cuh"
-#include "g16_internal.hpp"
+#include "checker.hpp"
 
 using namespace g16;
 
-void g16_curve_consts_g2(void* gen2, void* twist_b);   // msm_g2_misc.hip: gen2 (128 B), twistCoeffB (64 B)
-
 // `count` pairing products of four pairs each, one workgroup per product (pairing_product<4>, circuit_audit.cuh); shared
-// with the contribution chain (contribute.hip)
+// with every ProductTable (checker.hpp)
 int32_t g16_pairing_products4(g16_ctx* ctx, const void* d_P, const void* d_Q, uint32_t count, uint32_t neg_mask,
                               int32_t* d_result) {
   if (!count) return G16_OK;
@@ -26,15 +23,12 @@ int32_t g16_pairing_products4(g16_ctx* ctx, const void* d_P, const void* d_Q, ui
 
 namespace {
 
-constexpr size_t NONE = (size_t)-1;
-
-// device scratch of the point relations
-struct PairBuf {
+// device scratch of the point relations that compare two sums.  C1, IC and H1 are rows 0, 1, 2 of a ProductTable: C1 and
+// IC { MSM(z|., points), R1, R2, R3 } x { delta2 / gamma2, gen2, gen2, gen2 }, H1 { MSM(y, pointsH1), MSM(c, tauG1) } x
+// { delta2, gen2 }
+struct SumBuf {
   g1_aff lhs1[2], rhs1[2];   // A1, B1: MSM(z, points) and MSM(coef, tauG1)
   g2_aff lhs2, rhs2;         // B2
-  g1_aff P4[3][4];           // C1, IC: { MSM(z|., points), R1, R2, R3 }; H1: { MSM(y, pointsH1), MSM(c, tauG1), -, - }
-  g2_aff Q4[3][4];           //         { delta2 / gamma2, gen2, gen2, gen2 };    { delta2, gen2, -, - }
-  int32_t result[4];         // C1, IC, H1
 };
 
 uint32_t ceil_log2(uint64_t x) {
@@ -49,31 +43,30 @@ inline uint32_t grid_of(size_t n) { return (uint32_t)((n + CA_BLOCK - 1) / CA_BL
 // g16_key_audit's, which runs first and queues nothing before it has checked them)
 int32_t validate(g16_ctx* ctx, const g16_pkey_desc* d, const g16_r1cs_desc* r, const g16_ptau_desc* t,
                  const void* wire_multipliers, const void* h_multipliers, g16_circuit_report* out) {
-  auto bad = [&](const std::string& msg) {
-    ctx->err = "g16_circuit_audit: " + msg;
-    return G16_EINVAL;
-  };
-  if (!d || !r || !t || !wire_multipliers || !h_multipliers || !out) return bad("null argument");
-  if (!t->tauG1 || !t->tauG2 || !t->alphaTauG1 || !t->betaTauG1 || !t->betaG2) return bad("null ptau section");
+  static const char who[] = "g16_circuit_audit";
+  if (!d || !r || !t || !wire_multipliers || !h_multipliers || !out) return fail(ctx, who, "null argument");
+  if (!t->tauG1 || !t->tauG2 || !t->alphaTauG1 || !t->betaTauG1 || !t->betaG2) return fail(ctx, who, "null ptau section");
   for (int k = 0; k < 3; ++k)
-    if (r->nnz[k] && (!r->row[k] || !r->col[k] || !r->val[k])) return bad("null matrix pointer");
-  if (d->shard_count > 1) return bad("a sharded key description (audit the whole key: shard_count 0 or 1)");
-  if (d->log2_domain > 27 || d->nvars == 0 || d->nvars >= (1u << 27)) return bad("bad proving-key description");
-  if (r->nvars != d->nvars || r->npubs != d->npubs) return bad("the r1cs has other wire counts (nvars, npubs) than the key");
-  if (r->flavour != d->flavour) return bad("the flavour of the r1cs description is not the key's");
-  if (r->flags != G16_SCALARS_MONT && r->flags != G16_SCALARS_STD) return bad("r1cs flags must be G16_SCALARS_MONT or _STD");
+    if (r->nnz[k] && (!r->row[k] || !r->col[k] || !r->val[k])) return fail(ctx, who, "null matrix pointer");
+  if (d->shard_count > 1) return fail(ctx, who, "a sharded key description (audit the whole key: shard_count 0 or 1)");
+  if (d->log2_domain > 27 || d->nvars == 0 || d->nvars >= (1u << 27)) return fail(ctx, who, "bad proving-key description");
+  if (r->nvars != d->nvars || r->npubs != d->npubs)
+    return fail(ctx, who, "the r1cs has other wire counts (nvars, npubs) than the key");
+  if (r->flavour != d->flavour) return fail(ctx, who, "the flavour of the r1cs description is not the key's");
+  if (r->flags != G16_SCALARS_MONT && r->flags != G16_SCALARS_STD)
+    return fail(ctx, who, "r1cs flags must be G16_SCALARS_MONT or _STD");
   if (ceil_log2((uint64_t)r->nconstraints + r->npubs + 1) != d->log2_domain)
-    return bad("ceilingLog2(nconstraints + npubs + 1) of the r1cs is not the key's log2_domain");
+    return fail(ctx, who, "ceilingLog2(nconstraints + npubs + 1) of the r1cs is not the key's log2_domain");
   if (t->power < d->log2_domain + 1 || t->power > 28)
-    return bad("the powers of tau are too short: power >= log2_domain + 1 is needed (tau^(2n-1); and power <= 28)");
+    return fail(ctx, who, "the powers of tau are too short: power >= log2_domain + 1 is needed (tau^(2n-1); and power <= 28)");
   for (int k = 0; k < 3; ++k)
     for (size_t i = 0; i < r->nnz[k]; ++i) {
       if (r->row[k][i] >= r->nconstraints || r->col[k][i] >= r->nvars)
-        return bad("r1cs matrix " + std::to_string(k) + " entry " + std::to_string(i) + " out of range");
+        return fail(ctx, who, "r1cs matrix " + std::to_string(k) + " entry " + std::to_string(i) + " out of range");
       u256 v;
       memcpy(&v, (const char*)r->val[k] + 32 * i, 32);
       if (!Fr::is_canonical(v))
-        return bad("r1cs matrix " + std::to_string(k) + " entry " + std::to_string(i) + ": value is not canonical (>= r)");
+        return fail(ctx, who, "r1cs matrix " + std::to_string(k) + " entry " + std::to_string(i) + ": value is not canonical (>= r)");
     }
   return G16_OK;
 }
@@ -146,16 +139,6 @@ int32_t upload_points(g16_ctx* ctx, DevMem<T>& dst, const void* src, size_t coun
   return G16_OK;
 }
 
-// sum_i s_i P_i for a HOST point array (through the context's point staging buffer) and device scalars
-template <class C>
-int32_t msm_host_points(g16_ctx* ctx, const void* d_scalars, uint32_t flags, const void* points, size_t n, void* d_out) {
-  if (!n) return G16_OK;   // the slot keeps (0,0)
-  constexpr size_t psz = sizeof(typename C::Aff);
-  if (int32_t rc = ensure(ctx, ctx->stage_p, n * psz)) return rc;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->stage_p.p(), points, n * psz, hipMemcpyHostToDevice, ctx->stream));
-  return msm_device<C>(ctx, d_scalars, flags, ctx->stage_p.p(), n, d_out, nullptr, 0);
-}
-
 int32_t circuit_audit(g16_ctx* ctx, const g16_pkey_desc* d, const g16_vkey_desc* vk, const void* section4,
                       const g16_r1cs_desc* r, const g16_ptau_desc* t, const void* wire_multipliers,
                       const void* h_multipliers, g16_circuit_report* out) {
@@ -167,38 +150,18 @@ int32_t circuit_audit(g16_ctx* ctx, const g16_pkey_desc* d, const g16_vkey_desc*
   // 1. the element passes over what is read of the five ptau arrays
   const g16_audit_section psec[G16_PTAU_SECTIONS] = {
       {1, t->tauG1, 2 * n}, {2, t->tauG2, n}, {1, t->alphaTauG1, n}, {1, t->betaTauG1, n}, {2, t->betaG2, 1}};
-  if ((rc = g16_audit_sections(ctx, psec, G16_PTAU_SECTIONS, out->ptau_first_bad, out->ptau_bad_count))) return rc;
-  auto key_clean = [&](int s) {
-    return !(out->key.bad_count[s][0] | out->key.bad_count[s][1] | out->key.bad_count[s][2]);
-  };
-  auto ptau_clean = [&](int s) {
-    return !(out->ptau_bad_count[s][0] | out->ptau_bad_count[s][1] | out->ptau_bad_count[s][2]);
-  };
-  for (int s = 0; s < G16_PTAU_SECTIONS; ++s)
-    if (!ptau_clean(s)) out->failed |= G16_CIRCUIT_PTAU;
-  const bool tg1 = ptau_clean(G16_PTAU_TAU_G1), tg2 = ptau_clean(G16_PTAU_TAU_G2),
-             ta = ptau_clean(G16_PTAU_ALPHA_TAU_G1), tb = ptau_clean(G16_PTAU_BETA_TAU_G1),
-             tbg2 = ptau_clean(G16_PTAU_BETA_G2);
+  ElementPass pass;
+  if ((rc = pass.run(ctx, CIRCUIT_PTAU_ARRAYS, psec))) return rc;
+  pass.to_report(out->ptau_first_bad, out->ptau_bad_count);
+  if (pass.dirty) out->failed |= G16_CIRCUIT_PTAU;
   bool run[G16_CIRCUIT_RELATIONS];
-  run[G16_REL_COEFFS_A] = run[G16_REL_COEFFS_B] = key_clean(G16_SEC_COEFFS);
-  run[G16_REL_SPEC] = key_clean(G16_SEC_ALPHA1) && key_clean(G16_SEC_BETA1) && key_clean(G16_SEC_BETA2) && tg1 && tg2 &&
-                      ta && tb && tbg2;
-  run[G16_REL_A1] = key_clean(G16_SEC_POINTS_A1) && tg1;
-  run[G16_REL_B1] = key_clean(G16_SEC_POINTS_B1) && tg1;
-  run[G16_REL_B2] = key_clean(G16_SEC_POINTS_B2) && tg2;
-  run[G16_REL_C1] = key_clean(G16_SEC_POINTS_C1) && key_clean(G16_SEC_DELTA2) && tg1 && ta && tb;
-  run[G16_REL_IC] = vk && key_clean(G16_SEC_POINTS_IC) && key_clean(G16_SEC_GAMMA2) && tg1 && ta && tb;
-  run[G16_REL_H1] = key_clean(G16_SEC_POINTS_H1) && key_clean(G16_SEC_DELTA2) && tg1;
-  int32_t rel[G16_CIRCUIT_RELATIONS];
-  for (int k = 0; k < G16_CIRCUIT_RELATIONS; ++k) rel[k] = -1;
+  relations_run(CIRCUIT_RELATIONS, ~(dirty_mask(out->key.bad_count, G16_AUDIT_SECTIONS) | pass.dirty << CIRCUIT_PTAU_BIT),
+                vk ? NEED_VK : 0, run);
+  int32_t* rel = out->relation;   // every one -1: not run
 
   // 2. SPEC: bytes on the host
-  g1_aff gen1{Fp::one(), Fp::dbl(Fp::one())};
-  g2_aff gen2;
-  {
-    fp2_t twist_b;
-    g16_curve_consts_g2(&gen2, &twist_b);
-  }
+  const g1_aff gen1 = host_gen1();
+  const g2_aff gen2 = host_gen2();
   if (run[G16_REL_SPEC])
     rel[G16_REL_SPEC] = !memcmp(d->alpha1, t->alphaTauG1, 64) && !memcmp(d->beta1, t->betaTauG1, 64) &&
                         !memcmp(d->beta2, t->betaG2, 128) && !memcmp(t->tauG1, &gen1, 64) && !memcmp(t->tauG2, &gen2, 128);
@@ -210,7 +173,8 @@ int32_t circuit_audit(g16_ctx* ctx, const g16_pkey_desc* d, const g16_vkey_desc*
   DevMem<uint32_t> d_first;
   DevMem<g1_aff> d_tau1, d_alpha, d_beta;
   DevMem<g2_aff> d_tau2;
-  DevMem<PairBuf> d_pb;
+  DevMem<SumBuf> d_pb;
+  ProductTable pt(3);
   SyncOnExit drain{ctx->stream};
   if ((rc = key_matrix(ctx, d, section4, m_key))) return rc;
   if ((rc = r1cs_matrices(ctx, r, L, m_ab, m_c))) return rc;
@@ -224,8 +188,8 @@ int32_t circuit_audit(g16_ctx* ctx, const g16_pkey_desc* d, const g16_vkey_desc*
   HIPCHK(ctx, dev_alloc(d_h, 2 * n * 32));
   HIPCHK(ctx, dev_alloc(d_ystd, n * 32));
   HIPCHK(ctx, dev_alloc(d_first, 8));
-  HIPCHK(ctx, dev_alloc(d_pb, sizeof(PairBuf)));
-  HIPCHK(ctx, hipMemsetAsync(d_pb.get(), 0, sizeof(PairBuf), ctx->stream));
+  HIPCHK(ctx, dev_alloc(d_pb, sizeof(SumBuf)));
+  HIPCHK(ctx, hipMemsetAsync(d_pb.get(), 0, sizeof(SumBuf), ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(d_first.get(), 0xff, 8, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(d_key.get(), 0, 6 * n * 32, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(d_ab.get(), 0, 6 * n * 32, ctx->stream));
@@ -275,7 +239,16 @@ int32_t circuit_audit(g16_ctx* ctx, const g16_pkey_desc* d, const g16_vkey_desc*
   if (snarkjs && (rc = g16_ntt_device(ctx, d_h.get(), d_h.get(), L + 1, 1))) return rc;
 
   // 7. the sums
-  PairBuf* pb = d_pb.get();
+  SumBuf* pb = d_pb.get();
+  // C1 over z|priv (row 0), IC over z|pub (row 1).  No private wire: both sides are infinity, nothing to run.
+  const bool pair4[2] = {run[G16_REL_C1] && npriv > 0, run[G16_REL_IC]};
+  for (int j = 0; j < 2; ++j)
+    if (pair4[j]) {
+      pt.set(j, 0, nullptr, j == 0 ? d->delta2 : vk->gamma2);
+      for (int k = 1; k < 4; ++k) pt.set(j, k, nullptr, &gen2);
+    }
+  if (run[G16_REL_H1]) pt.set(2, 0, nullptr, d->delta2), pt.set(2, 1, nullptr, &gen2);
+  if ((rc = pt.upload(ctx))) return rc;
   const bool need_tau1 = run[G16_REL_A1] || run[G16_REL_B1] || run[G16_REL_C1] || run[G16_REL_IC] || run[G16_REL_H1];
   if (need_tau1 && (rc = upload_points(ctx, d_tau1, t->tauG1, 2 * n))) return rc;
   if (run[G16_REL_B2] && (rc = upload_points(ctx, d_tau2, t->tauG2, n))) return rc;
@@ -284,48 +257,38 @@ int32_t circuit_audit(g16_ctx* ctx, const g16_pkey_desc* d, const g16_vkey_desc*
     return rc;
   const u256 *coefA = d_sum.get(), *coefB = d_sum.get() + n;
   if (run[G16_REL_A1]) {
-    if ((rc = msm_host_points<G1>(ctx, z_all, G16_SCALARS_STD, d->pointsA1, nv, &pb->lhs1[0]))) return rc;
+    if ((rc = staged_msm<G1>(ctx, z_all, G16_SCALARS_STD, d->pointsA1, nv, &pb->lhs1[0]))) return rc;
     if ((rc = msm_device<G1>(ctx, coefA, G16_SCALARS_MONT, d_tau1.get(), n, &pb->rhs1[0], nullptr, 0))) return rc;
   }
   if (run[G16_REL_B1]) {
-    if ((rc = msm_host_points<G1>(ctx, z_all, G16_SCALARS_STD, d->pointsB1, nv, &pb->lhs1[1]))) return rc;
+    if ((rc = staged_msm<G1>(ctx, z_all, G16_SCALARS_STD, d->pointsB1, nv, &pb->lhs1[1]))) return rc;
     if ((rc = msm_device<G1>(ctx, coefB, G16_SCALARS_MONT, d_tau1.get(), n, &pb->rhs1[1], nullptr, 0))) return rc;
   }
   if (run[G16_REL_B2]) {
-    if ((rc = msm_host_points<G2>(ctx, z_all, G16_SCALARS_STD, d->pointsB2, nv, &pb->lhs2))) return rc;
+    if ((rc = staged_msm<G2>(ctx, z_all, G16_SCALARS_STD, d->pointsB2, nv, &pb->lhs2))) return rc;
     if ((rc = msm_device<G2>(ctx, coefB, G16_SCALARS_MONT, d_tau2.get(), n, &pb->rhs2, nullptr, 0))) return rc;
   }
-  // C1 over z|priv (j = 0), IC over z|pub (j = 1).  No private wire: both sides are infinity, nothing to run.
-  const bool pair4[2] = {run[G16_REL_C1] && npriv > 0, run[G16_REL_IC]};
   for (int j = 0; j < 2; ++j) {
     if (!pair4[j]) continue;
     const int h = j == 0 ? 1 : 0;   // the half of the product buffers: 0 = pub, 1 = priv
     const u256 *cA = d_ab.get() + 3 * n * h, *cB = cA + n, *cC = d_cc.get() + 3 * n * h;
     if (j == 0)
-      rc = msm_host_points<G1>(ctx, z_priv + npubs + 1, G16_SCALARS_STD, d->pointsC1, npriv, &pb->P4[0][0]);
+      rc = staged_msm<G1>(ctx, z_priv + npubs + 1, G16_SCALARS_STD, d->pointsC1, npriv, pt.d_P(0, 0));
     else
-      rc = msm_host_points<G1>(ctx, z_pub, G16_SCALARS_STD, vk->pointsIC, (size_t)npubs + 1, &pb->P4[1][0]);
+      rc = staged_msm<G1>(ctx, z_pub, G16_SCALARS_STD, vk->pointsIC, (size_t)npubs + 1, pt.d_P(1, 0));
     if (rc) return rc;
-    if ((rc = msm_device<G1>(ctx, cA, G16_SCALARS_MONT, d_beta.get(), n, &pb->P4[j][1], nullptr, 0))) return rc;
-    if ((rc = msm_device<G1>(ctx, cB, G16_SCALARS_MONT, d_alpha.get(), n, &pb->P4[j][2], nullptr, 0))) return rc;
-    if ((rc = msm_device<G1>(ctx, cC, G16_SCALARS_MONT, d_tau1.get(), n, &pb->P4[j][3], nullptr, 0))) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(&pb->Q4[j][0], j == 0 ? d->delta2 : vk->gamma2, 128, hipMemcpyHostToDevice, ctx->stream));
-    for (int k = 1; k < 4; ++k)
-      HIPCHK(ctx, hipMemcpyAsync(&pb->Q4[j][k], &gen2, 128, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = msm_device<G1>(ctx, cA, G16_SCALARS_MONT, d_beta.get(), n, pt.d_P(j, 1), nullptr, 0))) return rc;
+    if ((rc = msm_device<G1>(ctx, cB, G16_SCALARS_MONT, d_alpha.get(), n, pt.d_P(j, 2), nullptr, 0))) return rc;
+    if ((rc = msm_device<G1>(ctx, cC, G16_SCALARS_MONT, d_tau1.get(), n, pt.d_P(j, 3), nullptr, 0))) return rc;
   }
   if (run[G16_REL_H1]) {
-    if ((rc = msm_host_points<G1>(ctx, d_ystd.get(), G16_SCALARS_STD, d->pointsH1, n, &pb->P4[2][0]))) return rc;
-    if ((rc = msm_device<G1>(ctx, d_h.get(), G16_SCALARS_MONT, d_tau1.get(), 2 * n, &pb->P4[2][1], nullptr, 0))) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(&pb->Q4[2][0], d->delta2, 128, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&pb->Q4[2][1], &gen2, 128, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = staged_msm<G1>(ctx, d_ystd.get(), G16_SCALARS_STD, d->pointsH1, n, pt.d_P(2, 0)))) return rc;
+    if ((rc = msm_device<G1>(ctx, d_h.get(), G16_SCALARS_MONT, d_tau1.get(), 2 * n, pt.d_P(2, 1), nullptr, 0))) return rc;
   }
   // 8. the pairing products, e(-L, delta2 / gamma2) * prod e(R_k, gen2) == 1, as ONE launch of three workgroups: each is
-  //    the latency of one lane's Miller loop and final exponentiation, so side by side they cost what one does.  A pair
-  //    that is not used, and a product that is not run, keeps (0,0): its lane returns one.
-  if ((pair4[0] || pair4[1] || run[G16_REL_H1]) &&
-      (rc = g16_pairing_products4(ctx, &pb->P4[0][0], &pb->Q4[0][0], 3, 1u, pb->result)))
-    return rc;
-  PairBuf got;
+  //    the latency of one lane's Miller loop and final exponentiation, so side by side they cost what one does.
+  if ((pair4[0] || pair4[1] || run[G16_REL_H1]) && (rc = pt.run(ctx, 1u))) return rc;
+  SumBuf got;
   HIPCHK(ctx, hipMemcpyAsync(&got, pb, sizeof got, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 
@@ -338,14 +301,10 @@ int32_t circuit_audit(g16_ctx* ctx, const g16_pkey_desc* d, const g16_vkey_desc*
   if (run[G16_REL_A1]) rel[G16_REL_A1] = !memcmp(&got.lhs1[0], &got.rhs1[0], sizeof(g1_aff));
   if (run[G16_REL_B1]) rel[G16_REL_B1] = !memcmp(&got.lhs1[1], &got.rhs1[1], sizeof(g1_aff));
   if (run[G16_REL_B2]) rel[G16_REL_B2] = !memcmp(&got.lhs2, &got.rhs2, sizeof(g2_aff));
-  if (run[G16_REL_C1]) rel[G16_REL_C1] = npriv ? got.result[0] : 1;
-  if (run[G16_REL_IC]) rel[G16_REL_IC] = got.result[1];
-  if (run[G16_REL_H1]) rel[G16_REL_H1] = got.result[2];
-  for (int k = 0; k < G16_CIRCUIT_RELATIONS; ++k) {
-    out->relation[k] = rel[k];
-    if (rel[k] != 0) continue;
-    out->failed |= k <= G16_REL_COEFFS_B ? G16_CIRCUIT_COEFFS : k == G16_REL_SPEC ? G16_CIRCUIT_SPEC : G16_CIRCUIT_POINTS;
-  }
+  if (run[G16_REL_C1]) rel[G16_REL_C1] = npriv ? pt.result(0) : 1;
+  if (run[G16_REL_IC]) rel[G16_REL_IC] = pt.result(1);
+  if (run[G16_REL_H1]) rel[G16_REL_H1] = pt.result(2);
+  fold_report(CIRCUIT_RELATIONS, run, nullptr, 0, rel, nullptr, out->failed);
   return G16_OK;
 }
 
@@ -371,10 +330,7 @@ extern "C" int32_t g16_circuit_audit(g16_ctx* ctx, const g16_pkey_desc* desc, co
   if ((rc = g16_key_audit_body(ctx, desc, vk, section4, section4_bytes, wire_multipliers, &out->key))) return rc;
   if (out->key.failed) out->failed |= G16_CIRCUIT_KEY;
   CTX_ENTER(ctx);
-  try {   // the matrices are arranged in host vectors: no exception may cross the C ABI
-    return circuit_audit(ctx, desc, vk, section4, r1cs, ptau, wire_multipliers, h_multipliers, out);
-  } catch (const std::bad_alloc&) {
-    ctx->err = "out of host memory while arranging the matrices";
-    return G16_ENOMEM;
-  }
+  return no_throw(   // the matrices are arranged in host vectors
+      ctx, [&] { return circuit_audit(ctx, desc, vk, section4, r1cs, ptau, wire_multipliers, h_multipliers, out); },
+      "out of host memory while arranging the matrices");
 }

@@ -4,15 +4,10 @@
 // g16_points_intt_g1/g2 and g16_circuit_setup; kernels: circuit_setup.cuh, launch shapes: circuit_setup_plan.hpp.  The
 // element checks of the ptau are the circuit audit's (g16_audit_sections, audit.hip), the twiddles and coset factors
 // come from the geometric-sequence kernel of the fake setup (setup.hip).
-#include <new>
-
-#include "g16_internal.hpp"
-#include "ec.cuh"
+#include "checker.hpp"
 #include "setup.cuh"
 
 using namespace g16;
-
-void g16_curve_consts_g2(void* gen2, void* twist_b);   // msm_g2_misc.hip: gen2 (128 B), twistCoeffB (64 B)
 
 namespace {
 
@@ -91,36 +86,36 @@ bool load_scalar(const void* p, bool mont, u256& out) {
 // everything g16_circuit_setup rejects before it queues anything; delta comes back in Montgomery form (one: NULL)
 int32_t validate(g16_ctx* ctx, const g16_r1cs_desc* r, const g16_ptau_desc* t, const void* delta,
                  const g16_setup_points* o, uint32_t& log2_dom, u256& delta_mont) {
-  auto bad = [&](const std::string& msg) {
-    ctx->err = "g16_circuit_setup: " + msg;
-    return G16_EINVAL;
-  };
-  if (!r || !t || !o) return bad("null argument");
-  if (!t->tauG1 || !t->tauG2 || !t->alphaTauG1 || !t->betaTauG1 || !t->betaG2) return bad("null ptau section");
+  static const char who[] = "g16_circuit_setup";
+  if (!r || !t || !o) return fail(ctx, who, "null argument");
+  if (!t->tauG1 || !t->tauG2 || !t->alphaTauG1 || !t->betaTauG1 || !t->betaG2) return fail(ctx, who, "null ptau section");
   for (int k = 0; k < 3; ++k)
-    if (r->nnz[k] && (!r->row[k] || !r->col[k] || !r->val[k])) return bad("null matrix pointer");
-  if (r->flavour != G16_FLAVOUR_JENSGROTH && r->flavour != G16_FLAVOUR_SNARKJS) return bad("unknown flavour");
-  if (r->flags != G16_SCALARS_MONT && r->flags != G16_SCALARS_STD) return bad("r1cs flags must be G16_SCALARS_MONT or _STD");
-  if (r->nvars <= r->npubs) return bad("nvars must exceed npubs (wire 0 is the constant one)");
+    if (r->nnz[k] && (!r->row[k] || !r->col[k] || !r->val[k])) return fail(ctx, who, "null matrix pointer");
+  if (r->flavour != G16_FLAVOUR_JENSGROTH && r->flavour != G16_FLAVOUR_SNARKJS) return fail(ctx, who, "unknown flavour");
+  if (r->flags != G16_SCALARS_MONT && r->flags != G16_SCALARS_STD)
+    return fail(ctx, who, "r1cs flags must be G16_SCALARS_MONT or _STD");
+  if (r->nvars <= r->npubs) return fail(ctx, who, "nvars must exceed npubs (wire 0 is the constant one)");
   if (!o->alpha1 || !o->beta1 || !o->delta1 || !o->beta2 || !o->gamma2 || !o->delta2 || !o->pointsIC || !o->pointsA1 ||
       !o->pointsB1 || !o->pointsB2 || !o->pointsH1 || (r->nvars > r->npubs + 1 && !o->pointsC1))
-    return bad("null output pointer");
+    return fail(ctx, who, "null output pointer");
   log2_dom = setup_log2_domain(r->nconstraints, r->npubs);
-  if (log2_dom > PINTT_MAX_LOG2) return bad("domain too large (must not exceed 2^24)");
+  if (log2_dom > PINTT_MAX_LOG2) return fail(ctx, who, "domain too large (must not exceed 2^24)");
   if (t->power < log2_dom + 1 || t->power > 28)
-    return bad("the powers of tau are too short: power >= log2_domain + 1 is needed (tau^(2n-1); and power <= 28)");
-  if ((uint64_t)r->nnz[0] + r->nnz[1] + r->nnz[2] + r->npubs + 1 >= 0xffffffffu) return bad("too many matrix entries");
+    return fail(ctx, who, "the powers of tau are too short: power >= log2_domain + 1 is needed (tau^(2n-1); and power <= 28)");
+  if ((uint64_t)r->nnz[0] + r->nnz[1] + r->nnz[2] + r->npubs + 1 >= 0xffffffffu)
+    return fail(ctx, who, "too many matrix entries");
   delta_mont = Fr::one();
-  if (delta && !load_scalar(delta, r->flags == G16_SCALARS_MONT, delta_mont)) return bad("delta is not canonical (>= r)");
-  if (Fr::is_zero(delta_mont)) return bad("delta must not be zero");
+  if (delta && !load_scalar(delta, r->flags == G16_SCALARS_MONT, delta_mont))
+    return fail(ctx, who, "delta is not canonical (>= r)");
+  if (Fr::is_zero(delta_mont)) return fail(ctx, who, "delta must not be zero");
   for (int k = 0; k < 3; ++k)
     for (size_t i = 0; i < r->nnz[k]; ++i) {
       if (r->row[k][i] >= r->nconstraints || r->col[k][i] >= r->nvars)
-        return bad("r1cs matrix " + std::to_string(k) + " entry " + std::to_string(i) + " out of range");
+        return fail(ctx, who, "r1cs matrix " + std::to_string(k) + " entry " + std::to_string(i) + " out of range");
       u256 v;
       memcpy(&v, (const char*)r->val[k] + 32 * i, 32);
       if (!Fr::is_canonical(v))
-        return bad("r1cs matrix " + std::to_string(k) + " entry " + std::to_string(i) + ": value is not canonical (>= r)");
+        return fail(ctx, who, "r1cs matrix " + std::to_string(k) + " entry " + std::to_string(i) + ": value is not canonical (>= r)");
     }
   return G16_OK;
 }
@@ -173,20 +168,6 @@ int32_t job_run(g16_ctx* ctx, const SparseJob& j, const void* d_pts, const u256*
   return cs_segsum_device<C>(ctx, d_terms, j.d_off(), j.d_wires(), j.plan, d_out);
 }
 
-// the first failing element of the ptau arrays, in the words of the circuit-audit report
-bool ptau_finding(const size_t (*first_bad)[3], const size_t (*bad_count)[3], std::string& text) {
-  static const char* const names[G16_PTAU_SECTIONS] = {"tauG1", "tauG2", "alphaTauG1", "betaTauG1", "betaG2"};
-  static const char* const what[3] = {"is not a canonical encoding", "is not on the curve", "is not in the order-r subgroup"};
-  for (int s = 0; s < G16_PTAU_SECTIONS; ++s)
-    for (int k = 0; k < 3; ++k) {
-      if (!bad_count[s][k]) continue;
-      text = std::string("ptau ") + names[s] + "[" + std::to_string(first_bad[s][k]) + "] " + what[k];
-      if (bad_count[s][k] > 1) text += " (and " + std::to_string(bad_count[s][k] - 1) + " more)";
-      return true;
-    }
-  return false;
-}
-
 int32_t circuit_setup(g16_ctx* ctx, const g16_r1cs_desc* r, const g16_ptau_desc* t, bool with_delta, const u256& delta,
                       uint32_t L, g16_setup_points* o) {
   const uint32_t nv = r->nvars, npubs = r->npubs, ncons = r->nconstraints, np1 = npubs + 1;
@@ -199,25 +180,16 @@ int32_t circuit_setup(g16_ctx* ctx, const g16_r1cs_desc* r, const g16_ptau_desc*
   {
     const g16_audit_section psec[G16_PTAU_SECTIONS] = {
         {1, t->tauG1, 2 * n}, {2, t->tauG2, n}, {1, t->alphaTauG1, n}, {1, t->betaTauG1, n}, {2, t->betaG2, 1}};
-    size_t first_bad[G16_PTAU_SECTIONS][3], bad_count[G16_PTAU_SECTIONS][3];
-    if ((rc = g16_audit_sections(ctx, psec, G16_PTAU_SECTIONS, first_bad, bad_count))) return rc;
-    std::string text;
-    if (ptau_finding(first_bad, bad_count, text)) {
-      ctx->err = "g16_circuit_setup: " + text;
-      return G16_EINVAL;
-    }
+    ElementPass pass;
+    if ((rc = pass.run(ctx, CIRCUIT_SETUP_ARRAYS, psec)) || (rc = pass.first_finding(ctx, "g16_circuit_setup"))) return rc;
   }
 
   // 2. the scalars every stage shares, in device memory: standard form unless noted
   enum { K_INV_N = 0, K_DELTA, K_DELTA_INV, K_COUNT };
   const u256 delta_inv = Fr::inv(delta);
   const u256 consts[K_COUNT] = {Fr::from_mont(inv_pow2(L)), Fr::from_mont(delta), Fr::from_mont(delta_inv)};
-  g1_aff gen1{Fp::one(), Fp::dbl(Fp::one())};
-  g2_aff gen2;
-  {
-    fp2_t twist_b;
-    g16_curve_consts_g2(&gen2, &twist_b);
-  }
+  g1_aff gen1 = host_gen1();
+  g2_aff gen2 = host_gen2();
   const size_t nnzA = r->nnz[0], nnzB = r->nnz[1], nnzC = r->nnz[2], nval = nnzA + np1 + nnzB + nnzC;
   std::vector<u256> ones(np1, mont ? Fr::one() : std_u32(1));   // the dummy entries' values, in the form of the others
 
@@ -374,10 +346,7 @@ extern "C" int32_t g16_circuit_setup(g16_ctx* ctx, const g16_r1cs_desc* r1cs, co
   u256 delta_mont;
   if (int32_t rc = validate(ctx, r1cs, ptau, delta, out, log2_dom, delta_mont)) return rc;
   CTX_ENTER(ctx);
-  try {   // the entry lists are sorted in host vectors: no exception may cross the C ABI
-    return circuit_setup(ctx, r1cs, ptau, delta != nullptr, delta_mont, log2_dom, out);
-  } catch (const std::bad_alloc&) {
-    ctx->err = "out of host memory while arranging the matrices";
-    return G16_ENOMEM;
-  }
+  return no_throw(   // the entry lists are sorted in host vectors
+      ctx, [&] { return circuit_setup(ctx, r1cs, ptau, delta != nullptr, delta_mont, log2_dom, out); },
+      "out of host memory while arranging the matrices");
 }

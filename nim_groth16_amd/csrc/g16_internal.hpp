@@ -360,14 +360,20 @@ int32_t g16_widen_multipliers(g16_ctx* ctx, const char* who, const void* multipl
 int32_t g16_key_audit_body(g16_ctx* ctx, const g16_pkey_desc* d, const g16_vkey_desc* vk, const void* section4,
                            size_t section4_bytes, const void* multipliers, g16_key_report* out);
 // the element passes (audit_points) over `nsec` host arrays, group 1 = G1, 2 = G2 (with the order-r check); results as
-// g16_points_audit_*.  The caller has entered the context.
+// g16_points_audit_*.  `coeffs` (the key audit): then the pass over the values of `count` coefficient records, `stride`
+// bytes apart with the value `value_offset` bytes in; its results are row `nsec`.  One wait, at the end, on every path.
+// The caller has entered the context.  Callers go through ElementPass (checker.hpp).
 struct g16_audit_section {
   int group;
   const void* p;
   size_t n;
 };
+struct g16_audit_coeffs {
+  const void* base;
+  size_t count, stride, value_offset;
+};
 int32_t g16_audit_sections(g16_ctx* ctx, const g16_audit_section* sec, int nsec, size_t (*first_bad)[3],
-                           size_t (*bad_count)[3]);
+                           size_t (*bad_count)[3], const g16_audit_coeffs* coeffs = nullptr);
 
 // d_result[j] = ( prod_{k<4} e(+-d_P[4j+k], d_Q[4j+k]) == 1 ), j < count; bit k of neg_mask negates pair k; a pair with (0,0)
 // on either side contributes one (circuit_audit.hip: the kernel of the circuit audit's point relations)
