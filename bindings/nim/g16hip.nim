@@ -396,6 +396,58 @@ proc g16_circuit_audit(ctx: ptr G16Ctx, desc: ptr G16PKeyDesc, vk: ptr G16VKeyDe
 
 proc ok*(r: CircuitReport): bool = r.failed == 0
 
+# --- witness check (include/g16hip.h "witness check"): which constraints does an untrusted witness break? ---------------
+# What `snarkjs wtns check circuit.r1cs witness.wtns` answers: every value < r, witness[0] == 1, and
+# (A z)_i (B z)_i == (C z)_i for every constraint.  A service loads the circuit once (loadR1cs), checks every witness
+# (checkWitness) and proves only when the report is ok.  Like the rest of this shim it has NOT been compiled: no `nim` in
+# the image; the same calls run through ctypes and through tools/g16prove.cpp in tests/test_gpu_witness_check.py.
+# Needs `import groth16/files/r1cs` beside the imports above.
+const
+  G16_WITNESS_CANONICAL* = 1'u32     ## some value is >= r
+  G16_WITNESS_ONE* = 2'u32           ## witness[0] is not 1
+  G16_WITNESS_CONSTRAINTS* = 4'u32   ## some constraint fails
+  G16_WITNESS_LIST* = 16
+type
+  G16R1cs {.importc: "g16_r1cs", header: "g16hip.h", incompleteStruct.} = object
+  R1csSystem* = ptr G16R1cs
+  WitnessReport* {.importc: "g16_witness_report", header: "g16hip.h".} = object
+    failed*: uint32                                   ## OR of G16_WITNESS_*: 0 = fit to prove with
+    constraints*: int32                               ## 1 all hold, 0 some fail, -1 not run (a value is not canonical)
+    noncanonical_count*, first_noncanonical*: csize_t ## first: high(csize_t) = none
+    bad_count*: csize_t
+    first_bad*: array[G16_WITNESS_LIST, csize_t]      ## the smallest failing constraints, ascending; high(csize_t) = none
+    az*, bz*, cz*: array[32, byte]                    ## the sums at first_bad[0]: little-endian, standard form
+
+proc g16_r1cs_create(ctx: ptr G16Ctx, desc: ptr G16R1csDesc, res: ptr ptr G16R1cs): int32 {.importc, header: "g16hip.h".}
+proc g16_r1cs_destroy(r: ptr G16R1cs) {.importc, header: "g16hip.h".}
+proc g16_r1cs_info(r: ptr G16R1cs, res: ptr array[4, csize_t]): int32 {.importc, header: "g16hip.h".}
+proc g16_witness_check(ctx: ptr G16Ctx, r: ptr G16R1cs, witness: pointer, flags: uint32,
+                       res: ptr WitnessReport): int32 {.importc, header: "g16hip.h".}
+
+proc ok*(r: WitnessReport): bool = r.failed == 0
+
+proc loadR1cs*(r1cs: R1CS): R1csSystem =
+  ## the circuit resident on the GPU; release it with destroyR1cs
+  var rows, cols: array[3, seq[uint32]]
+  var vals: array[3, seq[Fr]]
+  for i, ct in r1cs.constraints:                            # files/r1cs.nim:62-80 -> triplets per matrix
+    for k, lc in [ct.A, ct.B, ct.C]:
+      for term in lc:
+        rows[k].add(uint32(i)); cols[k].add(uint32(term.wireIdx)); vals[k].add(term.value)
+  var d = G16R1csDesc(nvars: uint32(r1cs.cfg.nWires), npubs: uint32(r1cs.cfg.nPubOut + r1cs.cfg.nPubIn),
+    nconstraints: uint32(r1cs.constraints.len), flavour: uint32(ord(Snarkjs)), flags: G16_SCALARS_MONT)
+  for k in 0..2:
+    d.nnz[k] = csize_t(rows[k].len)
+    if rows[k].len > 0:
+      d.row[k] = addr rows[k][0]; d.col[k] = addr cols[k][0]; d.val[k] = addr vals[k][0]
+  check g16_r1cs_create(gctx, addr d, addr result)
+
+proc destroyR1cs*(r: R1csSystem) = g16_r1cs_destroy(r)
+
+proc checkWitness*(r: R1csSystem, witness: Witness): WitnessReport =
+  ## witness.values: seq[Fr], Montgomery limbs in memory
+  check g16_witness_check(gctx, r, unsafeAddr witness.values[0], G16_SCALARS_MONT, addr result)
+
 # --- drop-in for fakeCircuitSetup (groth16/fake_setup.nim:201-326): one g16_fake_setup call ----------------------------
 # The Lagrange values, the column sums, the combinations and the H scalars are formed on the device and stay in HBM; the
 # points come back into the seqs of the ZKey.  ZKey.coeffs is the reference's own r1csToCoeffs (fake_setup.nim:46-65).

@@ -677,6 +677,56 @@ int32_t g16_circuit_audit(g16_ctx* ctx, const g16_pkey_desc* desc, const g16_vke
                           size_t section4_bytes, const g16_r1cs_desc* r1cs, const g16_ptau_desc* ptau,
                           const void* wire_multipliers, const void* h_multipliers, g16_circuit_report* out);
 
+/* ---- witness check: which constraints does an UNTRUSTED witness break? -------------------------------------------------
+ * What `snarkjs wtns check circuit.r1cs witness.wtns` answers.  The proving calls take a witness as it is: a value >= r
+ * is multiplied as if it were a residue, and a witness that breaks a constraint gives a proof that does not verify with
+ * nothing that says why (the prover forms Cz := Az * Bz and never sees the real C z).  A service creates the constraint
+ * system once, checks every witness against it, and proves only when the report has failed == 0.
+ *
+ * g16_r1cs: a constraint system resident in HBM; immutable, belongs to the device of the creating context like a
+ *   g16_pkey; any context of that device may check against it, several at once, and it may be destroyed before or after
+ *   any context.
+ * desc: the struct of the circuit audit under its rules -- entries of one (constraint, wire) add up, explicit zeros are
+ *   legal, values in the form desc->flags names.  snarkjs's dummy A entries are NOT added (they belong to a key's
+ *   domain, not to the circuit) and rows >= nconstraints do not exist.  npubs (< nvars) and flavour are validated as
+ *   elsewhere and otherwise unused.  nconstraints == 0 is legal: every check then reports constraints = 1.
+ * G16_EINVAL from g16_r1cs_create, on the host, before anything is queued: a null pointer; an entry out of range; a value
+ *   >= r; unknown flags or flavour.  g16_last_error names matrix and entry in the circuit audit's words
+ *   ("r1cs matrix 2 entry 5 out of range"). */
+typedef struct g16_r1cs g16_r1cs;
+int32_t g16_r1cs_create(g16_ctx* ctx, const g16_r1cs_desc* desc, g16_r1cs** out);
+void g16_r1cs_destroy(g16_r1cs* r);
+/* out: nvars, nconstraints, nnz(A) + nnz(B) + nnz(C), distinct values (0: no value dictionary) */
+int32_t g16_r1cs_info(const g16_r1cs* r, size_t out[4]);
+
+#define G16_WITNESS_CANONICAL 1u   /* some value is >= r */
+#define G16_WITNESS_ONE 2u         /* witness[0] is not the canonical encoding of 1 in the form named by flags */
+#define G16_WITNESS_CONSTRAINTS 4u /* some constraint fails */
+#define G16_WITNESS_LIST 16
+typedef struct {
+  uint32_t failed;                      /* OR of G16_WITNESS_*; 0 = fit to prove with */
+  int32_t constraints;                  /* 1 = all hold, 0 = some fail, -1 = not run (a value is not canonical) */
+  size_t noncanonical_count, first_noncanonical; /* first = (size_t)-1 when none */
+  size_t bad_count;                     /* constraints i with (A z)_i (B z)_i != (C z)_i */
+  size_t first_bad[G16_WITNESS_LIST];   /* the min(bad_count, 16) SMALLEST failing indices, ascending; rest (size_t)-1 */
+  uint8_t az[32], bz[32], cz[32];       /* the three sums at first_bad[0]: canonical little-endian, standard form; zero
+                                           when no constraint fails or the pass did not run */
+} g16_witness_report;
+/* witness: nvars x 32 bytes; flags: G16_SCALARS_MONT or G16_SCALARS_STD, optionally | G16_SCALARS_DEVICE (the pointer
+ * is then a device pointer of the context's device).  Precedence, as in the audits:
+ *   1. the canonical pass over every value: the limb pattern (MONT) / the integer (STD) must be < r.  If any value fails,
+ *      constraints = -1, the counts and the list stay empty and the sums zero: the field arithmetic would silently reduce
+ *      or mis-multiply such a value, so nothing is reported about values that are not residues;
+ *   2. ONE: a byte comparison of witness[0] with the canonical encoding of 1 in the named form.  Reported on its own; it
+ *      does not stop the constraint pass;
+ *   3. the constraint pass: A z, B z and C z over the nconstraints rows as one row-balanced sparse product, then one lane
+ *      per constraint compares (A z)_i (B z)_i with (C z)_i.
+ * The list is deterministic: the same witness gives the same report, byte for byte, on every call.
+ * The call changes no context state (a context proves the same bytes before and after), runs on the context's stream
+ * with one wait at the end, and keeps the sums in the calling context's workspace: what crosses back to the host is the
+ * report.  G16_EINVAL: a null pointer, unknown flags, a system of another device. */
+int32_t g16_witness_check(g16_ctx* ctx, const g16_r1cs* r, const void* witness, uint32_t flags, g16_witness_report* out);
+
 /* ---- scaling an array of points: by ONE scalar, or by a scalar per point ------------------------------------------------
  * out[i] = k * points[i]; host pointers, affine Montgomery in and out, (0,0) legal anywhere; k: 32 bytes, canonical,
  * flags = G16_SCALARS_MONT or G16_SCALARS_STD; k == 0 is legal (all infinity); n < 2^31.  out may be points.

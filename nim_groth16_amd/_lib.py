@@ -8,6 +8,7 @@ import weakref
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
+_R = 21888242871839275222246405745257275088548364400416034343698204186575808495617   # the order of Fr (bn128.primeR)
 G16_OK, G16_EINVAL, G16_ENODEV, G16_EHIP, G16_ENOMEM, G16_ESELFTEST, G16_EBUSY = 0, -1, -2, -3, -4, -5, -6
 SCALARS_MONT, SCALARS_STD, SCALARS_DEVICE, OUT_PARTIAL, OUT_DEVICE, NO_HOST_SYNC = 1, 0, 2, 4, 8, 32
 PARTIALS_BYTES = 768
@@ -37,6 +38,7 @@ SYMBOLS = [
     "g16_points_intt_g1", "g16_points_intt_g2", "g16_circuit_setup",
     "g16_points_scale_g1", "g16_points_scale_g2", "g16_points_scale_each_g1", "g16_points_scale_each_g2",
     "g16_key_contribute", "g16_contributions_verify", "g16_ptau_contribute", "g16_ptau_verify",
+    "g16_r1cs_create", "g16_r1cs_destroy", "g16_r1cs_info", "g16_witness_check",
 ]
 VERIFY_SUBGROUP = 16
 GT_BYTES = 384
@@ -212,6 +214,63 @@ class CircuitReport:
             skipped += [CIRCUIT_RELATIONS[k] for k in range(len(CIRCUIT_RELATIONS)) if self.relation[k] < 0]
             return "circuit audit: ok" + (f" (not run: {', '.join(skipped)})" if skipped else "")
         return "circuit audit: FAILED\n" + "\n".join("  " + f for f in self.findings())
+
+
+# witness check (include/g16hip.h): the bits of `failed`, the length of the list of failing constraints
+WITNESS_CANONICAL, WITNESS_ONE, WITNESS_CONSTRAINTS = 1, 2, 4
+WITNESS_LIST = 16
+
+
+class WitnessReportC(ctypes.Structure):
+    """g16_witness_report (include/g16hip.h)"""
+    _fields_ = [("failed", ctypes.c_uint32), ("constraints", ctypes.c_int32),
+                ("noncanonical_count", ctypes.c_size_t), ("first_noncanonical", ctypes.c_size_t),
+                ("bad_count", ctypes.c_size_t), ("first_bad", ctypes.c_size_t * WITNESS_LIST),
+                ("az", ctypes.c_uint8 * 32), ("bz", ctypes.c_uint8 * 32), ("cz", ctypes.c_uint8 * 32)]
+
+
+class WitnessReport:
+    """What g16_witness_check found.  constraints = 1 (all hold), 0 (some fail) or -1 (not run: a value is not
+    canonical); first_noncanonical is an index or None; first_bad the (at most WITNESS_LIST) smallest failing constraint
+    indices, ascending; az, bz, cz the three sums at first_bad[0] as integers (0 when there is none)."""
+
+    def __init__(self, failed, constraints, noncanonical_count, first_noncanonical, bad_count, first_bad, az, bz, cz):
+        self.failed, self.constraints = failed, constraints
+        self.noncanonical_count, self.first_noncanonical = noncanonical_count, first_noncanonical
+        self.bad_count, self.first_bad = bad_count, list(first_bad)
+        self.az, self.bz, self.cz = az, bz, cz
+
+    @property
+    def ok(self) -> bool:
+        """fit to prove with"""
+        return self.failed == 0
+
+    def as_dict(self) -> dict:
+        return {"failed": self.failed, "constraints": self.constraints, "noncanonical_count": self.noncanonical_count,
+                "first_noncanonical": self.first_noncanonical, "bad_count": self.bad_count, "first_bad": self.first_bad,
+                "az": self.az, "bz": self.bz, "cz": self.cz}
+
+    def findings(self):
+        """one line per finding: the first value that is not canonical, witness[0], the failing constraints"""
+        out = []
+        if self.noncanonical_count:
+            more = self.noncanonical_count - 1
+            out.append(f"witness[{self.first_noncanonical}] is not canonical (>= r)" + (f" (and {more} more)" if more else ""))
+        if self.failed & WITNESS_ONE:
+            out.append("witness[0] is not 1")
+        if self.bad_count:
+            ab = self.az * self.bz % _R
+            out.append(f"constraint {self.first_bad[0]}: (A z)(B z) = {ab:#x}, C z = {self.cz:#x}")
+            rest = self.first_bad[1:]
+            if rest:
+                more = self.bad_count - len(self.first_bad)
+                out.append("also failing: constraints " + ", ".join(map(str, rest)) + (f" (and {more} more)" if more else ""))
+        return out
+
+    def __str__(self):
+        if self.ok:
+            return "witness check: ok"
+        return "witness check: FAILED\n" + "\n".join("  " + f for f in self.findings())
 
 
 class Phase2Key(ctypes.Structure):
@@ -535,8 +594,13 @@ def load_library():
                                         ctypes.POINTER(PtauContributionC)]
     lib.g16_ptau_verify.argtypes = [vp, ctypes.POINTER(PtauDesc), ctypes.POINTER(PtauContributionC), vp, sz, vp,
                                     ctypes.POINTER(PtauReportC)]
+    lib.g16_r1cs_create.argtypes = [vp, ctypes.POINTER(R1csDesc), ctypes.POINTER(vp)]
+    lib.g16_r1cs_destroy.argtypes = [vp]
+    lib.g16_r1cs_destroy.restype = None
+    lib.g16_r1cs_info.argtypes = [vp, ctypes.POINTER(sz)]
+    lib.g16_witness_check.argtypes = [vp, vp, vp, u32, ctypes.POINTER(WitnessReportC)]
     for name in SYMBOLS:
-        if name not in ("g16_ctx_destroy", "g16_last_error", "g16_points_release", "g16_points_count",
+        if name not in ("g16_ctx_destroy", "g16_r1cs_destroy", "g16_last_error", "g16_points_release", "g16_points_count",
                         "g16_points_inf_count",
                         "g16_pkey_destroy", "g16_vkey_destroy", "g16_group_destroy", "g16_group_last_error",
                         "g16_group_pkey_destroy", "g16_prover_destroy", "g16_prover_last_error", "g16_host_free"):
@@ -721,6 +785,10 @@ class Context:
                         [list(row) for row in rep.key.bad_count])
         return CircuitReport(key, fix(rep.ptau_first_bad), [list(row) for row in rep.ptau_bad_count], list(rep.relation),
                              rep.failed, [None if f == none else f for f in rep.first_row])
+
+    def r1cs_load(self, desc: R1csDesc, keepalive=None) -> "R1csSystem":
+        """g16_r1cs_create: the constraint system of `desc` resident on this context's device"""
+        return R1csSystem(self, desc, keepalive)
 
     def fixed_base(self, group: int, scalars: bytes, mont: bool = True) -> bytes:
         """scalars[i] * generator -> affine points (fake_setup.nim:258-261 `y ** gen1/gen2`)."""
@@ -1153,6 +1221,53 @@ class ProvingKey:
     def _free(self):
         if self._h:                      # valid whether or not the creating context is still alive
             self.ctx._lib.g16_pkey_destroy(self._h)
+        self._h = None
+
+    destroy = _free
+
+    def __del__(self):
+        try:
+            self._free()
+        except Exception:
+            pass
+
+
+class R1csSystem:
+    """Device-resident constraint system (g16_r1cs): A, B and C of a circuit as one row-balanced sparse matrix.  Like a
+    ProvingKey it belongs to the device: any context of that device may check against it."""
+
+    def __init__(self, ctx: Context, desc: R1csDesc, keepalive=None):
+        self.ctx = ctx
+        self._h = None
+        h = ctypes.c_void_p()
+        ctx._check(ctx._lib.g16_r1cs_create(ctx._h, ctypes.byref(desc), ctypes.byref(h)))
+        self._h = h
+        self.nvars, self.nconstraints = desc.nvars, desc.nconstraints
+        ctx._children.add(self)
+        del keepalive
+
+    def info(self) -> dict:
+        out = (ctypes.c_size_t * 4)()
+        self.ctx._check(self.ctx._lib.g16_r1cs_info(self._h, out))
+        return {"nvars": out[0], "nconstraints": out[1], "nnz": out[2], "dict_values": out[3]}
+
+    def check(self, witness, mont: bool = True, device: bool = False, ctx=None) -> WitnessReport:
+        """g16_witness_check.  witness: nvars x 32 bytes (or a device pointer with device=True)"""
+        c = ctx or self.ctx
+        if isinstance(witness, (bytes, bytearray)) and len(witness) != 32 * self.nvars:
+            raise ValueError(f"wrong witness length: {len(witness)} bytes, expected {32 * self.nvars}")
+        rep = WitnessReportC()
+        flags = (SCALARS_MONT if mont else 0) | (SCALARS_DEVICE if device else 0)
+        c._check(c._lib.g16_witness_check(c._h, self._h, _buf(witness), flags, ctypes.byref(rep)))
+        none = ctypes.c_size_t(-1).value
+        le = lambda a: int.from_bytes(bytes(a), "little")     # noqa: E731
+        return WitnessReport(rep.failed, rep.constraints, rep.noncanonical_count,
+                             None if rep.first_noncanonical == none else rep.first_noncanonical, rep.bad_count,
+                             [f for f in rep.first_bad if f != none], le(rep.az), le(rep.bz), le(rep.cz))
+
+    def _free(self):
+        if self._h:                      # valid whether or not the creating context is still alive
+            self.ctx._lib.g16_r1cs_destroy(self._h)
         self._h = None
 
     destroy = _free

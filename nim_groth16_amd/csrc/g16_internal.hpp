@@ -340,6 +340,8 @@ int32_t g16_spmat_create(g16_ctx* ctx, uint32_t nmat, uint32_t nrows, size_t nnz
 void g16_spmat_destroy(g16_spmat* m);
 void g16_spmat_info(const g16_spmat* m, size_t out[10]);   // dictionary size (0: plain values), virtual rows per bin
 // nmat == 2: d_out = Az | Bz | Cz; need_cz = false: Cz may be left unwritten (the quotient forms it on the fly)
+// nmat == 3 (A, B and C of a circuit, witness_check.hip): d_out = A z | B z | C z, nrows each.  x_mont = 0 and no
+// dictionary: the sums are in standard form and stay so; every other case gives Montgomery sums
 int32_t g16_spmat_apply(g16_ctx* ctx, const g16_spmat* m, const void* d_x, uint32_t x_mont, void* d_out,
                         bool need_cz = true);
 int32_t g16_ntt_device(g16_ctx* ctx, const void* d_src, void* d_dst, uint32_t log2n, int inverse);

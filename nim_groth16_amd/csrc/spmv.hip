@@ -309,7 +309,8 @@ static int32_t spmat_create(g16_ctx* ctx, uint32_t nmat, uint32_t nrows, size_t 
 }
 
 // out = (nmat == 2 ? Az | Bz | Cz : y), device pointers, on the context's main stream.  x_mont = 0: x in standard form
-// (nmat == 2 only).  need_cz = false: the caller forms Cz itself (the quotient's first pass): Cz is not written.
+// (nmat == 2 or 3).  need_cz = false: the caller forms Cz itself (the quotient's first pass): Cz is not written.
+// nmat == 3: out = A z | B z | C z over the matrix's own rows, C z the real product (the witness check).
 int32_t g16_spmat_apply(g16_ctx* ctx, const g16_spmat* m, const void* d_x, uint32_t x_mont, void* d_out, bool need_cz) {
   const uint32_t nblk = m->bins.blk_off[NBINS];
   if (!nblk) return G16_OK;
@@ -317,14 +318,20 @@ int32_t g16_spmat_apply(g16_ctx* ctx, const g16_spmat* m, const void* d_x, uint3
   const u256* val = (m->ndict && !x_mont) ? m->d_val2.get() : m->d_val.get();
   const bool sums_mont = x_mont || m->ndict;
 #define SPMV_LAUNCH(NM, DI)                                                                                          \
-  KLAUNCH(ctx, NM == 2 ? "abc_spmv" : "spmv", (spmv_binned<NM, DI>), nblk, BLOCK, 0, m->bins, m->d_ptr.get(),         \
-          m->d_col.get(), val, m->d_vidx.get(), (const u256*)d_x, m->d_rows.get(), m->nrows, (u256*)d_out)
+  KLAUNCH(ctx, NM == 2 ? "abc_spmv" : NM == 3 ? "witness_spmv" : "spmv", (spmv_binned<NM, DI>), nblk, BLOCK, 0,       \
+          m->bins, m->d_ptr.get(), m->d_col.get(), val, m->d_vidx.get(), (const u256*)d_x, m->d_rows.get(), m->nrows,  \
+          (u256*)d_out)
   if (m->nmat == 2) {
     if (m->ndict) SPMV_LAUNCH(2, true);
     else SPMV_LAUNCH(2, false);
     if (need_cz || !sums_mont)
       KLAUNCH(ctx, "abc_cz", abc_pointwise_cz, (m->nrows + BLOCK - 1) / BLOCK, BLOCK, 0, (u256*)d_out,
               sums_mont ? 1u : 0u, need_cz ? 1u : 0u, m->nrows);
+  } else if (m->nmat == 3) {
+    // the witness check (witness_check.hip): A z | B z | C z over the rows of the circuit, in the form sums_mont names
+    // above; nothing converts them here, the row check compares them in either form
+    if (m->ndict) SPMV_LAUNCH(3, true);
+    else SPMV_LAUNCH(3, false);
   } else {
     if (m->ndict) SPMV_LAUNCH(1, true);
     else SPMV_LAUNCH(1, false);

@@ -153,3 +153,28 @@ def generateProof(nthreads: int, printTimings: bool, zkey: ZKey, wtns: Witness, 
     """prover.nim:312-319 (the reference draws r, s from a clock-seeded PRNG, rnd.nim:15-24; here from the OS)."""
     mask = Mask(secrets.randbelow(F.primeR), secrets.randbelow(F.primeR))
     return generateProofWithMask(nthreads, printTimings, zkey, wtns, mask, ctx)
+
+
+def loadR1cs(r1cs, ctx=None):
+    """The constraint system of a parsed .r1cs (files/r1cs.py) or a synthetic.SparseR1CS resident on the GPU
+    (g16_r1cs_create) -> _lib.R1csSystem: create it once, `check` every witness against it."""
+    from .files.zkey import r1csDesc
+    ctx = ctx or default_context()
+    rd, keep = r1csDesc(r1cs, Snarkjs)
+    return ctx.r1cs_load(rd, keep)
+
+
+def witnessCheck(r1cs, wtns: Witness, ctx=None):
+    """Which constraints does a witness break?  What `snarkjs wtns check circuit.r1cs witness.wtns` answers, on the GPU
+    (g16_witness_check, include/g16hip.h): every value < r, witness[0] == 1, and (A z)_i (B z)_i == (C z)_i for every
+    constraint.  r1cs: as parseR1CS returns it (or a synthetic.SparseR1CS, or an _lib.R1csSystem loaded before);
+    -> _lib.WitnessReport: `.ok`, and str() names the first value that is not canonical and the failing constraints."""
+    from ._lib import R1csSystem
+    system = r1cs if isinstance(r1cs, R1csSystem) else loadR1cs(r1cs, ctx)
+    if system.nvars * 32 != len(wtns.values):
+        raise ValueError(f"wrong witness length: {len(wtns.values) // 32} values, the r1cs has {system.nvars} wires")
+    try:
+        return system.check(wtns.values, mont=not wtns.std, ctx=ctx)
+    finally:
+        if system is not r1cs:
+            system.destroy()

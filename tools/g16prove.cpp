@@ -6,6 +6,7 @@
 //       -Wl,-rpath,$PWD/nim_groth16_amd/csrc -o g16prove
 //   ./g16prove -z circuit.zkey -w witness.wtns -o proof.json -i public.json [-n] [-y] [-t] [--gpus 0,1,2,3]
 //             [--table-stride S] [--audit-key] [--audit-circuit-r1cs circuit.r1cs --audit-circuit-ptau pot.ptau]
+//             [--check-witness-r1cs circuit.r1cs]
 //   ./g16prove -u -r circuit.r1cs [--toxic-seed N] -w witness.wtns -o proof.json -i public.json [-y] ...
 //   ./g16prove -u -r circuit.r1cs --ptau pot.ptau [--delta-seed N] [-z new.zkey] -w witness.wtns ...
 //
@@ -34,6 +35,10 @@
 // and, beyond it, the key's coefficients against the r1cs and every point array of the key against the powers of tau
 // (what `snarkjs zkey verify` checks before the contribution chain).  A key that does not belong to them gives exit code 2
 // and no proof.
+//
+// --check-witness-r1cs F: g16_witness_check before the proof -- every witness value < r, witness[0] == 1, and
+// (A z)_i (B z)_i == (C z)_i for every constraint of the circuit (`snarkjs wtns check`).  The findings are printed with the
+// indices of the failing constraints; a witness that fails gives exit code 2 and no proof.
 //
 // --gpus d0,d1,...: the proof sharded over those devices through the device group of the C ABI (g16_group_*: one host
 // thread per device inside the library; the reference's Taskpool shape, msm.nim:96-122).  A device may repeat.
@@ -209,10 +214,42 @@ std::vector<uint64_t> draw_multipliers(size_t n) {
   return zs;
 }
 
+std::string hex32(const uint8_t* le) {
+  std::string out = "0x";
+  char b[3];
+  bool lead = true;
+  for (int i = 31; i >= 0; --i) {
+    if (lead && !le[i] && i) continue;
+    snprintf(b, sizeof b, lead ? "%x" : "%02x", le[i]);
+    out += b, lead = false;
+  }
+  return out;
+}
+
+// the findings of a witness report, one per line (WitnessReport.findings of the Python binding)
+void print_report(const g16_witness_report& rep) {
+  if (rep.noncanonical_count) {
+    printf("  witness[%zu] is not canonical (>= r)", rep.first_noncanonical);
+    if (rep.noncanonical_count > 1) printf(" (and %zu more)", rep.noncanonical_count - 1);
+    printf("\n");
+  }
+  if (rep.failed & G16_WITNESS_ONE) printf("  witness[0] is not 1\n");
+  if (!rep.bad_count) return;
+  // a b mod r from the two standard-form sums: (a b / R) R^2 / R
+  const U256 ab = mont_mul(mont_mul(load(rep.az), load(rep.bz), PRIME_R, R_NINV), FR_R2, PRIME_R, R_NINV);
+  printf("  constraint %zu: (A z)(B z) = %s, C z = %s\n", rep.first_bad[0], hex32((const uint8_t*)ab.v).c_str(),
+         hex32(rep.cz).c_str());
+  size_t listed = 1;
+  for (; listed < G16_WITNESS_LIST && rep.first_bad[listed] != (size_t)-1; ++listed)
+    printf("%s%zu", listed == 1 ? "  also failing: constraints " : ", ", rep.first_bad[listed]);
+  if (rep.bad_count > listed) printf(" (and %zu more)", rep.bad_count - listed);
+  if (listed > 1) printf("\n");
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
-  const char *acr = nullptr, *acp = nullptr;
+  const char *acr = nullptr, *acp = nullptr, *cwr = nullptr;
   const char *zpath = nullptr, *wpath = nullptr, *rpath = nullptr, *opath = "proof.json", *ipath = "public.json";
   bool nomask = false, verify = false, timing = false, setup = false, audit = false;
   const char* ptau_path = nullptr;
@@ -252,6 +289,7 @@ int main(int argc, char** argv) {
     else if (a == "--audit-key") audit = true;
     else if (a == "--audit-circuit-r1cs") acr = next();
     else if (a == "--audit-circuit-ptau") acp = next();
+    else if (a == "--check-witness-r1cs") cwr = next();
     else if (a == "--gpus") {
       for (const char* q = next(); *q;) {
         char* end = nullptr;
@@ -348,6 +386,24 @@ int main(int argc, char** argv) {
       return 2;
     }
     printf("circuit audit: ok\n");
+  }
+  if (cwr) {   // ... and no proof from a witness that is not canonical or breaks a constraint of its circuit
+    R1csFile rf(cwr);
+    if (rf.nwires != nvars) die("the r1cs of --check-witness-r1cs has another number of wires than the key");
+    const g16_r1cs_desc rdsc = rf.desc(G16_FLAVOUR_SNARKJS);
+    g16_r1cs* sys = nullptr;
+    chk(g16_r1cs_create(ctx, &rdsc, &sys), "g16_r1cs_create");
+    g16_witness_report rep;
+    const int32_t rc = g16_witness_check(ctx, sys, wvals, G16_SCALARS_STD, &rep);
+    g16_r1cs_destroy(sys);
+    chk(rc, "g16_witness_check");
+    if (rep.failed) {
+      printf("witness check: FAILED\n");
+      print_report(rep);
+      g16_ctx_destroy(ctx);
+      return 2;
+    }
+    printf("witness check: ok\n");
   }
   const double t1a = now();
 

@@ -27,6 +27,9 @@ snarkjs, ptau or network).  Given external files the checked recipe is
       --verify-contributions INITIAL.zkey  before the key is loaded: do the records of its section 10 lead from the
           initial key (the caller's anchor: made with --setup-ptau or tied to its circuit with --audit-circuit) to this
           key?  The report is printed; a chain that fails gives exit code 2 and no proof, like --audit-circuit
+      --check-witness R1CS  before proving: is every witness value < r, is witness[0] one, and which constraints of this
+          circuit does the witness break (witnessCheck: `snarkjs wtns check` on the GPU)?  The findings are printed with
+          the constraint indices; a witness that fails gives exit code 2 and no proof
     snarkjs groth16 verify verification_key.json public.json proof.json        # offline, wherever snarkjs exists
 (the reference's own recipe: groth16/example/prove.sh:52-59)."""
 import argparse
@@ -72,6 +75,9 @@ def main():
     ap.add_argument("--verify-contributions", metavar="INITIAL", default=None,
                     help="check the key's contribution chain against this initial key before loading it; no proof from "
                          "a key whose chain fails")
+    ap.add_argument("--check-witness", metavar="R1CS", default=None,
+                    help="check the witness against this circuit on the GPU before proving; no proof from a witness that "
+                         "is not canonical or breaks a constraint")
     ap.add_argument("-y", "--verify", action="store_true",
                     help="also verify the proof against the zkey's verification key (cli_main.nim -y)")
     args = ap.parse_args()
@@ -131,6 +137,13 @@ def main():
     if args.audit_circuit:
         from nim_groth16_amd.files import auditCircuit, parsePtau, parseR1CS
         report = auditCircuit(zkey, parseR1CS(args.audit_circuit[0]), parsePtau(args.audit_circuit[1]), ctx)
+        print(report)
+        if not report.ok:
+            raise SystemExit(2)
+    if args.check_witness:
+        from nim_groth16_amd import witnessCheck
+        from nim_groth16_amd.files import parseR1CS
+        report = witnessCheck(parseR1CS(args.check_witness), wtns, ctx)
         print(report)
         if not report.ok:
             raise SystemExit(2)
